@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- scenes/s of HEAL's per-frame perception hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload scene5|pair|single]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload scene5|pair|single] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one synthetic OPV2V-shaped scene through the whole path with its inputs (device point
@@ -26,8 +26,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0      # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
-FP32_PEAK_TFLOPS = 157.3   # fp32 matrix/vector peak, same guide
+HBM_PEAK_GBS = 8000.0      # MI355X HBM3E
+FP32_PEAK_TFLOPS = 157.3   # fp32 matrix/vector peak
 
 WORKLOADS = {
     # name: (agent modalities in scene order, description)
@@ -508,6 +508,25 @@ def preflight(dist, rank, world, dev, backend, limit_s=float(os.environ.get("HEA
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res):
+    """Write the (boxes, scores) a caller of the timed step received as out_dir/{boxes,scores}.npy (float32).  No boxes is an
+    empty [0,8,3] / [0] pair.  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the boxes (same rows for both) is kept."""
+    boxes, scores = res
+    boxes = np.zeros((0, 8, 3), np.float32) if boxes is None else boxes.detach().float().cpu().numpy()
+    scores = np.zeros((0,), np.float32) if scores is None else scores.detach().float().cpu().numpy()
+    row_bytes = boxes[:1].nbytes + scores[:1].nbytes
+    if row_bytes and boxes.shape[0] * row_bytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(boxes.shape[0], DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        boxes, scores = boxes[keep], scores[keep]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("boxes", boxes), ("scores", scores)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr))
+    print(f"[bench] outputs of the last timed step -> {out_dir}: boxes {boxes.shape}, scores {scores.shape}", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -529,7 +548,14 @@ def main():
                          "(weak scaling; the throughput upper bound of SURVEY 8e)")
     ap.add_argument("--watchdog-s", type=int, default=1200,
                     help="hard wall-clock limit of this process: a hung collective ends the job instead of the box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (boxes [N,8,3], scores [N]) as "
+                         "DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared output for output")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if a.watchdog_s > 0:
         import threading
@@ -771,6 +797,9 @@ def main():
         res = (None, None)
     fence()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        # host copies now: a replay returns views of the graph's static output buffers, which the passes below overwrite
+        dump_outputs(a.dump_outputs, res)
     if use_graph:
         # per-operator HIP-event timing needs host-side launches: an instrumented eager pass over the
         # same K steps, right after the timed graph replays (events cannot be recorded inside a graph)

@@ -1,5 +1,5 @@
 import os, sys, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from heal_amd import ops
 n, width, cout, hw, g = 3, 128, 64, 64, 32
 x = torch.randn((n, width, hw, hw), device="cuda")

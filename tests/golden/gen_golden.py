@@ -650,7 +650,17 @@ def gen_pcdet_iou():
          iou_edge=cref.ref_boxes_iou_bev_cpu(edge, edge))
 
 
+def gen_pcdet_iou_400():
+    """The reference's boxes_iou_bev_cpu of pcdet_boxes_400() against itself (400 x 400 pairs, through oracle/_ref)."""
+    from oracle import cref
+    from tests.test_oracle_golden import pcdet_boxes_400
+    assert cref.build_ref() and cref.ref_lib() is not None
+    b = pcdet_boxes_400()
+    save("pcdet_iou_400", boxes=b, iou=cref.ref_boxes_iou_bev_cpu(b, b))
+
+
 GENS["pcdet_iou"] = gen_pcdet_iou
+GENS["pcdet_iou_400"] = gen_pcdet_iou_400
 GENS.update(GENS_EXTRA)
 GENS["oldstyle_small"] = gen_oldstyle_small
 GENS["hetero_small"] = gen_hetero_small

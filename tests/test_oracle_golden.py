@@ -136,17 +136,25 @@ def test_pcdet_iou_oracle_bit_exact_vs_reference_golden(golden):
     np.testing.assert_array_equal(cref.pcdet_matrix(g["edge"], g["edge"], "iou"), g["iou_edge"])
 
 
-def test_pcdet_iou_oracle_vs_live_reference_build():
-    """When oracle/_ref/libpcdet_iou_ref.so exists (built here from /root/reference, prebuilt on the GPU box), a
-    fresh random set is compared bit for bit as well -- more pairs than the committed fixture holds."""
-    from oracle import cref
-    if cref.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference)")
+def pcdet_boxes_400():
+    """400 seeded boxes within +-9 m (dense overlaps); tests/golden/gen_golden.py::gen_pcdet_iou_400 stores the reference's IoU."""
     rng = np.random.default_rng(5)
     b = np.zeros((400, 7), np.float32)
     b[:, 0:2] = rng.uniform(-9, 9, (400, 2)); b[:, 3] = rng.uniform(0.3, 6, 400); b[:, 4] = rng.uniform(0.3, 3, 400)
     b[:, 5] = 1.5; b[:, 6] = rng.uniform(-7, 7, 400)
-    np.testing.assert_array_equal(cref.pcdet_matrix(b, b, "iou"), cref.ref_boxes_iou_bev_cpu(b, b))
+    return b
+
+
+def test_pcdet_iou_oracle_vs_live_reference_build(golden):
+    """A second, larger random set compared bit for bit -- more pairs than pcdet_iou.npz holds: 400 seeded boxes against
+    themselves, with the reference's boxes_iou_bev_cpu outputs stored in tests/golden/pcdet_iou_400.npz
+    (tests/golden/gen_golden.py::gen_pcdet_iou_400)."""
+    from oracle import cref
+    g = golden("pcdet_iou_400")
+    b = pcdet_boxes_400()
+    np.testing.assert_array_equal(b, g["boxes"])
+    assert (g["iou"] > 0).sum() > 5000
+    np.testing.assert_array_equal(cref.pcdet_matrix(b, b, "iou"), g["iou"])
 
 
 def test_pcdet_known_answers_and_nms_rule():

@@ -1,14 +1,38 @@
-"""Host mirrors against the LIVE reference functions on seeded random inputs (build container only: skipped where
-/root/reference is absent).  Complements the committed golden fixtures: every pure-host function of
-opencood/utils/{box_utils,common_utils,transformation_utils,camera_utils}.py that the mirror restates is called on both
-sides with the same arguments (numpy and torch variants) and must return equal values, dtypes and container types."""
+"""Host mirrors against the reference functions on seeded random inputs.  Complements the committed golden fixtures: every
+pure-host function of opencood/utils/{box_utils,common_utils,transformation_utils,camera_utils}.py and of the loss /
+train-utility modules that the mirror restates is called on both sides with the same arguments (numpy and torch variants)
+and must return equal values, dtypes and container types.
+
+Where the reference tree is present the tests call it live.  Elsewhere the reference's side is REPLAYED from
+tests/golden/reference_live.pt.gz: call by call, what the reference returned when the same test ran against it (the inputs
+are seeded, so they are the same on both occasions).  Float results depend on the SIMD width torch's CPU kernels run with, so
+there is one recording per ATen CPU capability.  The loss tests' transcendental and reduction kernels also round differently
+from one CPU model to the next (a few float32 ulps): replayed, their float results are compared to REPLAY_RTOL; called live,
+every comparison is exact.  Recording needs the reference tree:
+
+    for c in avx512 avx2; do ATEN_CPU_CAPABILITY=$c HEAL_RECORD_REFERENCE=1 python -m pytest tests/test_reference_live.py; done
+
+The two "other seeds" tests run the golden generators themselves against the reference and are skipped where it is
+absent."""
+import contextlib
+import functools
+import gzip
+import io
 import os
+import warnings
 
 import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference/opencood"), reason="reference tree not present")
+REF_ROOT = "/root/reference"
+REF_YAML = os.path.join(REF_ROOT, "opencood", "hypes_yaml", "opv2v", "LiDAROnly", "lidar_pyramid.yaml")
+TAPE_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_live.pt.gz")
+RECORD = os.environ.get("HEAL_RECORD_REFERENCE", "0") == "1"
+HAVE_REFERENCE = os.path.isdir(os.path.join(REF_ROOT, "opencood"))
+needs_reference = pytest.mark.skipif(not HAVE_REFERENCE, reason="reference tree not present")
+REPLAY_RTOL = 1e-5     # recordings of two CPUs differ by <= 4e-7 relative (AVX2 vs AVX512 on one host, measured)
+REPLAY_FLOOR = 1e-3    # ... relative to max(|x|, 1e-6 max|x|): below REPLAY_FLOOR * max|x| an element is held to an absolute bound
 
 
 def _ref(mod):
@@ -16,7 +40,175 @@ def _ref(mod):
     return R.ref(mod)
 
 
-def _eq(a, b, tol=0.0):
+# ---- the tape: values the reference returned, in call order, per test --------------------------------------------------
+def _load_tapes():
+    with gzip.open(TAPE_FILE, "rb") as f:
+        return torch.load(io.BytesIO(f.read()), weights_only=True)
+
+
+def _save_tapes(tapes):
+    buf = io.BytesIO()
+    torch.save(tapes, buf)
+    with gzip.GzipFile(TAPE_FILE, "wb", compresslevel=9, mtime=0) as f:
+        f.write(buf.getvalue())
+
+
+def _capability():
+    return torch.backends.cpu.get_cpu_capability()
+
+
+def _bytes(entries):
+    buf = io.BytesIO()
+    torch.save(entries, buf)
+    return buf.getvalue()
+
+
+def _store(name, entries):
+    """{"common": {test: entries}, <capability>: {test: entries}}: a test whose recording is the same under every recorded
+    capability is kept once, under "common"."""
+    tapes = _load_tapes() if os.path.exists(TAPE_FILE) else {}
+    per_cap = {c: t[name] for c, t in tapes.items() if c not in ("common", "recorded") and name in t}
+    if name in tapes.get("common", {}):
+        per_cap.update({c: tapes["common"][name] for c in tapes.get("recorded", {}).get(name, [])})
+    per_cap[_capability()] = entries
+    for t in tapes.values():
+        t.pop(name, None)
+    if len({_bytes(e) for e in per_cap.values()}) == 1:
+        tapes.setdefault("common", {})[name] = entries
+    else:
+        for c, e in per_cap.items():
+            tapes.setdefault(c, {})[name] = e
+    tapes.setdefault("recorded", {})[name] = sorted(per_cap)
+    _save_tapes({c: dict(sorted(t.items())) for c, t in sorted(tapes.items())})
+
+
+class _Opaque(Exception):
+    pass
+
+
+def _encode(v):
+    if isinstance(v, torch.Tensor):
+        return ("pt", v.detach().clone())
+    if isinstance(v, np.ndarray):
+        if v.dtype == object:
+            raise _Opaque(type(v))
+        return ("nd", torch.from_numpy(np.ascontiguousarray(v).copy()))
+    if isinstance(v, np.generic):
+        return ("ns", torch.from_numpy(np.asarray(v).copy()))
+    if isinstance(v, (tuple, list)):
+        return ("tuple" if isinstance(v, tuple) else "list", [_encode(x) for x in v])
+    if isinstance(v, dict):
+        if not all(isinstance(k, str) for k in v):
+            raise _Opaque(type(v))
+        return ("dict", [[k, _encode(x)] for k, x in v.items()])
+    if v is None or isinstance(v, (bool, int, float, str)):
+        return ("py", v)
+    raise _Opaque(type(v))
+
+
+def _decode(e):
+    tag, v = e
+    if tag == "pt":
+        return v.clone()
+    if tag == "nd":
+        return v.numpy().copy()
+    if tag == "ns":
+        return v.numpy()[()]
+    if tag in ("tuple", "list"):
+        xs = [_decode(x) for x in v]
+        return tuple(xs) if tag == "tuple" else xs
+    if tag == "dict":
+        return {k: _decode(x) for k, x in v}
+    return v
+
+
+class _Tape:
+    """Recording: runs the reference and keeps what it returned.  Replaying: hands the kept values back in the same order."""
+
+    def __init__(self, name):
+        self.name = name
+        self.live = RECORD or HAVE_REFERENCE      # the reference itself is called
+        self.rtol = 0.0 if self.live else REPLAY_RTOL
+        self.entries, self.pos = [], 0
+        if not self.live:
+            tapes = _load_tapes()
+            assert name in tapes["recorded"], f"{name} has no recording in {TAPE_FILE}"
+            if _capability() not in tapes["recorded"][name]:
+                pytest.skip(f"no recording of the reference under ATen CPU capability {_capability()} "
+                            f"(recorded: {tapes['recorded'][name]})")
+            self.entries = tapes["common"][name] if name in tapes["common"] else tapes[_capability()][name]
+
+    def call(self, label, fn):
+        """The value of fn() (which runs the reference) when recording, the recorded value otherwise."""
+        return self._take(label, fn)[0]
+
+    def _take(self, label, fn):
+        """(value, opaque): opaque values (a module, a loss class instance) are not kept; calls on them are recorded instead."""
+        if self.live and not RECORD:
+            return fn(), False
+        if RECORD:
+            v = fn()
+            try:
+                self.entries.append((label, _encode(v)))
+            except _Opaque:
+                self.entries.append((label, ("obj", None)))
+                return v, True
+            return v, False
+        assert self.pos < len(self.entries), f"{self.name}: more reference calls than recorded ({label})"
+        got, e = self.entries[self.pos]
+        assert got == label, f"{self.name}: call {self.pos} is {label}, the recording has {got}"
+        self.pos += 1
+        return (None, True) if e[0] == "obj" else (_decode(e), False)
+
+    def ref(self, mod):
+        """The reference module `mod` (opencood.x.y), live or behind the tape."""
+        if self.live and not RECORD:
+            return _ref(mod)
+        return _Proxy(self, mod, _ref(mod) if RECORD else None)
+
+    def finish(self):
+        if RECORD:
+            _store(self.name, self.entries)
+        elif not self.live:
+            assert self.pos == len(self.entries), f"{self.name}: {len(self.entries) - self.pos} recorded calls were not made"
+
+
+class _Proxy:
+    def __init__(self, tape, path, live):
+        self._tape, self._path, self._live = tape, path, live
+
+    def __getattr__(self, name):
+        return _Proxy(self._tape, f"{self._path}.{name}", getattr(self._live, name) if RECORD else None)
+
+    def __call__(self, *args, **kwargs):
+        out, opaque = self._tape._take(self._path + "()", lambda: self._live(*args, **kwargs))
+        return _Proxy(self._tape, self._path + "()", out) if opaque else out
+
+
+@pytest.fixture
+def tape(request):
+    if RECORD and not os.path.isdir(os.path.join(REF_ROOT, "opencood")):
+        pytest.fail("HEAL_RECORD_REFERENCE=1 needs the reference tree")
+    t = _Tape(request.node.name)
+    failed = request.session.testsfailed
+    yield t
+    if request.session.testsfailed == failed:      # (a failed test stops early: its unread calls say nothing more)
+        t.finish()
+
+
+def _qualname(obj):
+    return f"{type(obj).__module__}.{type(obj).__qualname__}"
+
+
+def _same(a, b, rtol):
+    """torch.equal, or (rtol > 0) equal within rtol of b's magnitude for floating tensors."""
+    if rtol == 0 or not a.is_floating_point():
+        return torch.equal(a, b)
+    atol = rtol * REPLAY_FLOOR * float(b.abs().max())
+    return a.shape == b.shape and a.dtype == b.dtype and torch.allclose(a, b, rtol=rtol, atol=atol)
+
+
+def _eq(a, b, tol=0.0, rtol=0.0):
     assert type(a) is type(b), (type(a), type(b))
     if isinstance(a, torch.Tensor):
         assert a.dtype == b.dtype and a.shape == b.shape
@@ -25,12 +217,14 @@ def _eq(a, b, tol=0.0):
         assert a.dtype == b.dtype and a.shape == b.shape
         if tol:
             np.testing.assert_allclose(a, b, rtol=0, atol=tol)
+        elif rtol and np.issubdtype(a.dtype, np.floating) and a.size:
+            np.testing.assert_allclose(a, b, rtol=rtol, atol=rtol * REPLAY_FLOOR * float(np.nanmax(np.abs(b))))
         else:
             assert np.array_equal(a, b, equal_nan=True)
     elif isinstance(a, (tuple, list)):
         assert len(a) == len(b)
         for x, y in zip(a, b):
-            _eq(x, y, tol)
+            _eq(x, y, tol, rtol)
     else:
         assert a == b
 
@@ -41,9 +235,9 @@ def _boxes(rng, n):
                           1).astype(np.float32)
 
 
-def test_box_utils_live():
+def test_box_utils_live(tape):
     from heal_amd.opencood.utils import box_utils as mine
-    theirs = _ref("opencood.utils.box_utils")
+    theirs = tape.ref("opencood.utils.box_utils")
     rng = np.random.default_rng(0)
     b = _boxes(rng, 300)
     for order in ("hwl", "lwh"):
@@ -59,7 +253,7 @@ def test_box_utils_live():
     _eq(mine.box3d_to_2d(corners), theirs.box3d_to_2d(corners))
     _eq(mine.corner2d_to_standup_box(corners[:, :4, :2]), theirs.corner2d_to_standup_box(corners[:, :4, :2]))
     _eq(mine.corner_to_standup_box_torch(tc), theirs.corner_to_standup_box_torch(tc))
-    tfm = _ref("opencood.utils.transformation_utils").x1_to_x2([3, -2, 0.5, 1, 40, -2], [0, 1, 0, 0, -15, 0])
+    tfm = tape.ref("opencood.utils.transformation_utils").x1_to_x2([3, -2, 0.5, 1, 40, -2], [0, 1, 0, 0, -15, 0])
     _eq(mine.project_box3d(corners, tfm.astype(np.float32)), theirs.project_box3d(corners, tfm.astype(np.float32)))
     _eq(mine.project_box3d(tc, torch.from_numpy(tfm).float()), theirs.project_box3d(tc, torch.from_numpy(tfm).float()))
     _eq(mine.get_mask_for_boxes_within_range_torch(tc, [-30, -30, -3, 30, 30, 1]),
@@ -72,12 +266,12 @@ def test_box_utils_live():
     _eq(mine.remove_bbx_abnormal_z(tc), theirs.remove_bbx_abnormal_z(tc))
 
 
-def test_common_transformation_camera_utils_live():
+def test_common_transformation_camera_utils_live(tape):
     from heal_amd.opencood.utils import camera_utils as cam_mine
     from heal_amd.opencood.utils import common_utils as com_mine
     from heal_amd.opencood.utils import transformation_utils as tf_mine
-    com, tf, cam = _ref("opencood.utils.common_utils"), _ref("opencood.utils.transformation_utils"), \
-        _ref("opencood.utils.camera_utils")
+    com, tf, cam = tape.ref("opencood.utils.common_utils"), tape.ref("opencood.utils.transformation_utils"), \
+        tape.ref("opencood.utils.camera_utils")
     rng = np.random.default_rng(1)
     v = rng.uniform(-20, 20, 1000).astype(np.float32)
     for off, per in ((0.5, 2 * np.pi), (0.0, np.pi), (1.0, 2 * np.pi)):
@@ -118,13 +312,20 @@ def test_common_transformation_camera_utils_live():
     geom = torch.from_numpy(rng.integers(0, 50, (2000, 4)))
     _eq(cam_mine.cumsum_trick(x, geom, ranks), cam.cumsum_trick(x, geom, ranks))
     with torch.enable_grad():      # (the reference import switches gradients off globally)
-        xa, xb = x.clone().requires_grad_(True), x.clone().requires_grad_(True)
-        (ya, ga), (yb, gb) = cam_mine.QuickCumsum.apply(xa, geom, ranks), cam.QuickCumsum.apply(xb, geom, ranks)
-        _eq((ya.detach(), ga), (yb.detach(), gb))
+        xa = x.clone().requires_grad_(True)
+        ya, ga = cam_mine.QuickCumsum.apply(xa, geom, ranks)
         w = torch.from_numpy(rng.standard_normal(tuple(ya.shape)).astype(np.float32))
         (ya * w).sum().backward()
-        (yb * w).sum().backward()
-    _eq(xa.grad, xb.grad)
+
+    def quick_cumsum_theirs():     # forward and the gradient of sum(y * w) w.r.t. x, through the reference's autograd Function
+        with torch.enable_grad():
+            xb = x.clone().requires_grad_(True)
+            yb, gb = _ref("opencood.utils.camera_utils").QuickCumsum.apply(xb, geom, ranks)
+            (yb * w).sum().backward()
+        return yb.detach(), gb, xb.grad
+    yb, gb, xb_grad = tape.call("QuickCumsum", quick_cumsum_theirs)
+    _eq((ya.detach(), ga), (yb, gb))
+    _eq(xa.grad, xb_grad)
 
 
 class _Captured(dict):
@@ -134,6 +335,7 @@ class _Captured(dict):
         return list(self)
 
 
+@needs_reference
 @pytest.mark.parametrize("shift,with_decode", [(1000, True), (2000, False)])
 def test_oracle_against_live_reference_with_other_seeds(shift, with_decode, monkeypatch):
     """The committed fixtures pin the oracle on ONE seeded input per component; here the same generators
@@ -189,58 +391,60 @@ def _leafs(out):
 
 @pytest.mark.grad
 @pytest.mark.parametrize("use_fg_mask", [False, True])
-def test_losses_match_live_reference_values_and_gradients(use_fg_mask):
+def test_losses_match_live_reference_values_and_gradients(use_fg_mask, tape):
     """opencood/loss/point_pillar{,_depth,_pyramid}_loss.py: value, loss_dict and the gradient w.r.t. every head /
     occupancy / depth input, for the fused heads (suffix ""), the per-agent occupancy pass ("_single" on a 'collab'
     output) and the 'single' pyramid model, on CPU with the loss block of the reference's own lidar_pyramid.yaml."""
     from heal_amd.opencood.hypes_yaml import yaml_utils
     from heal_amd.opencood.tools.train_utils import create_loss
-    hypes = yaml_utils.load_yaml("/root/reference/opencood/hypes_yaml/opv2v/LiDAROnly/lidar_pyramid.yaml")
+    hypes = {"loss": tape.call("lidar_pyramid.yaml[loss]", lambda: yaml_utils.load_yaml(REF_YAML)["loss"])}
     hypes["loss"]["args"]["depth"]["use_fg_mask"] = use_fg_mask
     mine = create_loss(hypes)
-    theirs = _ref("opencood.tools.train_utils").create_loss(hypes)
-    assert type(mine).__name__ == type(theirs).__name__ == "PointPillarPyramidLoss"
+    theirs = _ref("opencood.tools.train_utils").create_loss(hypes) if tape.live else None
+    assert type(mine).__name__ == tape.call("create_loss", lambda: type(theirs).__name__) == "PointPillarPyramidLoss"
+
+    def run(crit, seed, mode, suffix):
+        out, tgt = _loss_inputs(seed)
+        out["pyramid"] = mode
+        leafs = _leafs(out)
+        loss = crit(out, tgt, suffix)
+        loss.backward()
+        return loss.detach(), [None if t.grad is None else t.grad.clone() for t in leafs], dict(crit.loss_dict)
     for seed, mode, suffix in ((0, "collab", ""), (1, "collab", "_single"), (2, "single", "")):
-        grads = []
-        for crit in (mine, theirs):
-            out, tgt = _loss_inputs(seed)
-            out["pyramid"] = mode
-            leafs = _leafs(out)
-            loss = crit(out, tgt, suffix)
-            loss.backward()
-            grads.append((loss.detach(), [None if t.grad is None else t.grad.clone() for t in leafs], dict(crit.loss_dict)))
-        (la, ga, da), (lb, gb, db) = grads
-        assert torch.equal(la, lb), (mode, suffix, la, lb)
+        la, ga, da = run(mine, seed, mode, suffix)
+        lb, gb, db = tape.call(f"loss({seed},{mode},{suffix})", lambda: run(theirs, seed, mode, suffix))
+        assert _same(la, lb, tape.rtol), (mode, suffix, la, lb)
         assert set(da) == set(db)
         for k in da:
-            assert float(da[k]) == float(db[k]), k
+            assert _same(torch.as_tensor(float(da[k])), torch.as_tensor(float(db[k])), tape.rtol), k
         for x, y in zip(ga, gb):
             assert (x is None) == (y is None)
             if x is not None:
-                assert torch.equal(x, y)
+                assert _same(x, y, tape.rtol)
 
 
 @pytest.mark.grad
-def test_loss_components_match_live_reference():
+def test_loss_components_match_live_reference(tape):
     mine, theirs = __import__("heal_amd.opencood.loss.point_pillar_loss", fromlist=["x"]), \
-        _ref("opencood.loss.point_pillar_loss")
+        tape.ref("opencood.loss.point_pillar_loss")
+    eq = functools.partial(_eq, rtol=tape.rtol)
     g = torch.Generator().manual_seed(5)
     p, t = torch.randn((3, 500, 7), generator=g), torch.randn((3, 500, 7), generator=g)
     w = torch.rand((3, 500, 1), generator=g)
-    _eq(mine.weighted_smooth_l1_loss(p, t, 3.0, w), theirs.weighted_smooth_l1_loss(p, t, 3.0, w))
+    eq(mine.weighted_smooth_l1_loss(p, t, 3.0, w), theirs.weighted_smooth_l1_loss(p, t, 3.0, w))
     lab = (torch.rand((3, 500, 1), generator=g) > 0.9).float()
-    _eq(mine.sigmoid_focal_loss(p[..., :1], lab, weights=w, alpha=0.25, gamma=2.0),
+    eq(mine.sigmoid_focal_loss(p[..., :1], lab, weights=w, alpha=0.25, gamma=2.0),
         theirs.sigmoid_focal_loss(p[..., :1], lab, weights=w, alpha=0.25, gamma=2.0))
-    _eq(mine.PointPillarLoss.add_sin_difference(p, t), theirs.PointPillarLoss.add_sin_difference(p, t))
+    eq(mine.PointPillarLoss.add_sin_difference(p, t), theirs.PointPillarLoss.add_sin_difference(p, t))
     bins = torch.randint(0, 2, (3, 500), generator=g)
-    _eq(mine.one_hot_f(bins, 2), theirs.one_hot_f(bins, 2))
-    _eq(mine.softmax_cross_entropy_with_logits(p[..., :2].reshape(-1, 2), mine.one_hot_f(bins, 2).view(-1, 2)),
+    eq(mine.one_hot_f(bins, 2), theirs.one_hot_f(bins, 2))
+    eq(mine.softmax_cross_entropy_with_logits(p[..., :2].reshape(-1, 2), mine.one_hot_f(bins, 2).view(-1, 2)),
         theirs.softmax_cross_entropy_with_logits(p[..., :2].reshape(-1, 2), theirs.one_hot_f(bins, 2).view(-1, 2)))
     dmine, dtheirs = __import__("heal_amd.opencood.loss.point_pillar_depth_loss", fromlist=["x"]), \
-        _ref("opencood.loss.point_pillar_depth_loss")
+        tape.ref("opencood.loss.point_pillar_depth_loss")
     logit, idx = torch.randn((4, 12, 6, 8), generator=g), torch.randint(0, 12, (4, 6, 8), generator=g)
     for red in ("none", "mean", "sum"):
-        _eq(dmine.FocalLoss(0.25, 2.0, red)(logit, idx), dtheirs.FocalLoss(0.25, 2.0, red)(logit, idx))
+        eq(dmine.FocalLoss(0.25, 2.0, red)(logit, idx), dtheirs.FocalLoss(0.25, 2.0, red)(logit, idx))
     # smooth_target: the reference pins its kernel to "cuda" at construction (:131), so the known answer is computed here
     sm = dmine.FocalLoss(0.25, 2.0, "none", smooth_target=True)(logit, idx)
     oh = torch.nn.functional.one_hot(idx, 12).float()
@@ -252,14 +456,14 @@ def test_loss_components_match_live_reference():
 
 
 @pytest.mark.grad
-def test_checkpoint_optimizer_scheduler_helpers_match_live_reference(tmp_path, capsys):
+def test_checkpoint_optimizer_scheduler_helpers_match_live_reference(tmp_path, capsys, tape):
     """tools/train_utils.py: load_saved_model (best-val file, last-epoch file, empty directory), setup_optimizer and
     setup_lr_schedular with the optimizer / scheduler blocks of the reference's own lidar_pyramid.yaml."""
-    import warnings
     from heal_amd.opencood.hypes_yaml import yaml_utils
     from heal_amd.opencood.tools import train_utils as mine
-    theirs = _ref("opencood.tools.train_utils")
-    hypes = yaml_utils.load_yaml("/root/reference/opencood/hypes_yaml/opv2v/LiDAROnly/lidar_pyramid.yaml")
+    theirs = _ref("opencood.tools.train_utils") if tape.live else None
+    hypes = tape.call("lidar_pyramid.yaml[optimizer,lr_scheduler]",
+                      lambda: {k: yaml_utils.load_yaml(REF_YAML)[k] for k in ("optimizer", "lr_scheduler")})
 
     def net(seed):
         torch.manual_seed(seed)
@@ -275,30 +479,46 @@ def test_checkpoint_optimizer_scheduler_helpers_match_live_reference(tmp_path, c
     torch.save(src.state_dict(), d_best / "net_epoch_bestval_at23.pth")
     torch.save(net(9).state_dict(), d_best / "net_epoch30.pth")
     for d in (d_last, d_best, d_empty):
-        a, b = net(100), net(100)
+        a = net(100)
         ea, _ = mine.load_saved_model(str(d), a)
         out_mine = capsys.readouterr().out
-        eb, _ = theirs.load_saved_model(str(d), b)
-        out_theirs = capsys.readouterr().out
+
+        def load_theirs():     # epoch, the model's state after loading, what it printed
+            b = net(100)
+            with contextlib.redirect_stdout(io.StringIO()) as buf:
+                eb_, _ = theirs.load_saved_model(str(d), b)
+            return eb_, list(b.state_dict().items()), buf.getvalue()
+        eb, state_b, out_theirs = tape.call(f"load_saved_model({d.name})", load_theirs)
         assert ea == eb == {"last": 12, "best": 23, "empty": 0}[d.name]
-        for (k, x), (_, y) in zip(a.state_dict().items(), b.state_dict().items()):
+        assert len(state_b) == len(a.state_dict())
+        for (k, x), (_, y) in zip(a.state_dict().items(), state_b):
             assert torch.equal(x, y), (d.name, k)
         assert out_mine.splitlines()[0] == out_theirs.splitlines()[0] if out_theirs else not out_mine
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         for init_epoch in (None, 0, 17):
-            m1, m2 = net(3), net(3)
-            o1, o2 = mine.setup_optimizer(hypes, m1), theirs.setup_optimizer(hypes, m2)
-            assert type(o1) is type(o2) and o1.defaults == o2.defaults
-            s1, s2 = mine.setup_lr_schedular(hypes, o1, init_epoch), theirs.setup_lr_schedular(hypes, o2, init_epoch)
-            assert type(s1) is type(s2) and s1.get_last_lr() == s2.get_last_lr() and s1.last_epoch == s2.last_epoch
+            o1 = mine.setup_optimizer(hypes, net(3))
+            s1 = mine.setup_lr_schedular(hypes, o1, init_epoch)
+
+            def setup_theirs():
+                o2 = theirs.setup_optimizer(hypes, net(3))
+                s2 = theirs.setup_lr_schedular(hypes, o2, init_epoch)
+                return _qualname(o2), o2.defaults, _qualname(s2), s2.get_last_lr(), s2.last_epoch
+            o2_type, o2_defaults, s2_type, s2_lr, s2_epoch = tape.call(f"setup(init_epoch={init_epoch})", setup_theirs)
+            assert _qualname(o1) == o2_type and o1.defaults == o2_defaults
+            assert _qualname(s1) == s2_type and s1.get_last_lr() == s2_lr and s1.last_epoch == s2_epoch
         for core in ("step", "exponential"):
             h = {"lr_scheduler": {"core_method": core, "step_size": 4, "gamma": 0.5}, "optimizer": hypes["optimizer"]}
             s1 = mine.setup_lr_schedular(h, mine.setup_optimizer(h, net(3)), 9)
-            s2 = theirs.setup_lr_schedular(h, theirs.setup_optimizer(h, net(3)), 9)
-            assert type(s1) is type(s2) and s1.get_last_lr() == s2.get_last_lr()
+
+            def schedule_theirs():
+                s2 = theirs.setup_lr_schedular(h, theirs.setup_optimizer(h, net(3)), 9)
+                return _qualname(s2), s2.get_last_lr()
+            s2_type, s2_lr = tape.call(f"setup_lr_schedular({core})", schedule_theirs)
+            assert _qualname(s1) == s2_type and s1.get_last_lr() == s2_lr
 
 
+@needs_reference
 @pytest.mark.parametrize("shift", [1000, 2000])
 def test_v2xvit_and_baseline_oracles_against_live_reference_with_other_seeds(shift, monkeypatch):
     """oracle/v2xvit_ref.py and oracle/model_ref.heter_model_baseline are pinned by ONE committed sample each (fusion_small,
