@@ -197,7 +197,7 @@ def _baseline_modality(base, strides, inplanes=None):
 
 def lidar_baseline(fusion_method="v2xvit", lidar_range=FULL_RANGE, max_cav=5, modality="m1"):
     """HeterModelBaseline (LiDAROnly/lidar_v2xvit.yaml; BASELINE config 5 with modality='m3'):
-    encoder -> plain BEV backbone -> shrinker -> single-scale fusion (v2xvit | att | max) -> heads."""
+    encoder -> plain BEV backbone -> shrinker -> single-scale fusion (v2xvit | att | max | cobevt) -> heads."""
     h = _common(lidar_range, max_cav)
     h["name"] = f"heal_amd_opv2v_{modality}_{fusion_method}"
     if modality == "m1":
@@ -212,6 +212,9 @@ def lidar_baseline(fusion_method="v2xvit", lidar_range=FULL_RANGE, max_cav=5, mo
         args["v2xvit"] = _v2xvit_args()
     elif fusion_method == "att":
         args["att"] = {"feat_dim": 256}
+    elif fusion_method == "cobevt":     # LiDAROnly/lidar_cobevt.yaml
+        args["cobevt"] = {"input_dim": 256, "mlp_dim": 256, "agent_size": max_cav, "window_size": 4, "dim_head": 32,
+                          "drop_out": 0.1, "depth": 3}
     h["model"] = {"core_method": "heter_model_baseline", "args": args}
     # encoder + backbone + stride-2 shrinker leave the map at 1/4 of the 0.4 m anchor grid (lidar_v2xvit.yaml: feature_stride 4)
     h["postprocess"]["anchor_args"]["feature_stride"] = 4

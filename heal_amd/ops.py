@@ -801,6 +801,59 @@ class WindowAttention(torch.autograd.Function):
         return gq, gb, None, None, None, None
 
 
+_AGENT_WINDOW_MODES = {"window": 0, "grid": 1}
+
+
+def agent_window_attention_supported(n_agents, window, dim_head, H, W):
+    return 1 <= int(n_agents) <= 8 and int(window) == 4 and int(dim_head) == 32 and H % window == 0 and W % window == 0
+
+
+def agent_window_attention(qkv, bias, n_valid, mode, heads, dim_head, window, scale, out=None):
+    """CoBEVT's masked attention over agents x window pixels (heal_agent_window_attention): qkv [L,H,W,3*heads*dim_head] (packed
+    q|k|v, token-major), bias [heads,T,T] (T = L window^2, token order (l w1 w2)) or None, n_valid: agents >= n_valid are masked
+    keys, mode 'window' | 'grid' -> [L,H,W,heads*dim_head] (written into `out` when given)."""
+    qkv = _need(qkv, torch.float32, "qkv")
+    L, H, W, C3 = (int(v) for v in qkv.shape)
+    if mode not in _AGENT_WINDOW_MODES:
+        raise _capi.HealAmdError(f"agent_window_attention: mode must be 'window' or 'grid', got {mode!r}")
+    if C3 != 3 * heads * dim_head or not agent_window_attention_supported(L, window, dim_head, H, W):
+        raise _capi.HealAmdError(f"agent_window_attention: unsupported shape ({L} agents, window {window}, dim_head {dim_head}, "
+                                 f"map {H}x{W})")
+    n_valid = int(n_valid)
+    if not 1 <= n_valid <= L:
+        raise _capi.HealAmdError(f"agent_window_attention: n_valid {n_valid} outside 1..{L}")
+    T = L * window * window
+    if bias is not None:
+        bias = _need(bias, torch.float32, "bias")
+        if tuple(bias.shape) != (heads, T, T):
+            raise _capi.HealAmdError(f"agent_window_attention: bias must be [heads, T, T] = [{heads}, {T}, {T}]")
+    inner = heads * dim_head
+    if out is None:
+        out = torch.empty((L, H, W, inner), dtype=torch.float32, device=qkv.device)
+    elif not (out.is_contiguous() and out.numel() == L * H * W * inner and out.dtype == torch.float32):
+        raise _capi.HealAmdError("agent_window_attention: `out` must be a contiguous f32 [L,H,W,heads*dim_head] buffer")
+    # per query token: q k^T and p v over the n_valid * window^2 unmasked keys = 4 n_valid window^2 inner FLOPs; q | k | v read +
+    # the result written = 16 inner bytes
+    with _Timed(f"agent_window_attention_{mode}", flops=4.0 * L * H * W * n_valid * window * window * inner,
+                nbytes=16.0 * L * H * W * inner):
+        _capi.call("heal_agent_window_attention", _ptr(qkv), _optr(bias), L, n_valid, H, W, int(heads), int(dim_head),
+                   int(window), _AGENT_WINDOW_MODES[mode], float(scale), _ptr(out), _stream())
+    return out
+
+
+def agent_mean(x):
+    """x [L, ...] f32 -> mean over the first dimension [...] (heal_agent_mean; sums in agent order)."""
+    x = _need(x, torch.float32, "x")
+    L = int(x.shape[0])
+    out = torch.empty(tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    n = out.numel()
+    if n % 4:
+        raise _capi.HealAmdError("agent_mean: the per-agent size must be a multiple of 4")
+    with _Timed("agent_mean", nbytes=4.0 * (L + 1) * n):
+        _capi.call("heal_agent_mean", _ptr(x), L, n, _ptr(out), _stream())
+    return out
+
+
 def label_assign(anchor_boxes, gt_boxes, pos_threshold, neg_threshold):
     """Anchor labelling core of generate_label: stand-up boxes [N,4] / [G,4] f32 cuda -> (assigned [N] i32: gt index of a
     positive anchor or -1, neg [N] u8)."""

@@ -24,8 +24,9 @@
 extern "C" {
 #endif
 
-#define HEAL_AMD_ABI_VERSION 7   /* 6 (round 6): + heal_pfn_pillars / heal_pillar_canvas / heal_pillar_stem_block; the measured-negative entry
-                                   points moved to include/heal_amd_experimental.h (HEAL_BUILD_EXPERIMENTAL=1 builds only) */
+#define HEAL_AMD_ABI_VERSION 8   /* 6 (round 6): + heal_pfn_pillars / heal_pillar_canvas / heal_pillar_stem_block; the measured-negative entry
+                                   points moved to include/heal_amd_experimental.h (HEAL_BUILD_EXPERIMENTAL=1 builds only);
+                                   8: + heal_agent_window_attention / heal_agent_mean (CoBEVT fusion) */
 
 int heal_abi_version(void);
 const char* heal_last_error(void);
@@ -681,6 +682,21 @@ size_t heal_window_attention_backward_workspace(int n_agents, int H, int W, int 
 int heal_window_attention_backward(const float* qkv, const float* pos_bias, const float* out, const float* grad_out, int n_agents,
                                    int H, int W, int heads, int dim_head, int window, float scale, float* grad_qkv,
                                    float* grad_bias, void* ws, size_t ws_bytes, void* stream);
+
+/* heal_agent_window_attention: the masked agent-window attention of CoBEVT (opencood/models/fuse_modules/swap_fusion_modules.py:
+ *   11-108 Attention, as SwapFusionBlockMask calls it at :135-152; fusion_in_one.py:374-430).  For every group of T = 16 n_agents tokens
+ *   (l, w1, w2) -- mode 0 (window): pixel (x * window + w1, y * window + w2) of every agent l; mode 1 (grid): pixel
+ *   (w1 * H / window + x, w2 * W / window + y) -- and every head:
+ *     out[token, h*d:(h+1)*d] = softmax(scale * Q K^T + bias[h], keys of agents >= n_valid masked to -inf) V.
+ *   qkv [n_agents,H,W,3*heads*dim_head] f32 = the packed to_qkv projection (q | k | v chunks, each (head, dim)); bias [heads,T,T]
+ *   (relative_position_bias_table[relative_position_index], token order (l w1 w2)) or NULL; out [n_agents,H,W,heads*dim_head].
+ *   Queries of padded agents are not masked: their rows are written too.  window 4, dim_head 32, n_agents 1..8,
+ *   1 <= n_valid <= n_agents, H and W multiples of window.  K / V of agents >= n_valid are never read.
+ * heal_agent_mean: out[i] = mean over l of x[l, i] for x [n_agents, n_elems] (CoBEVT's mlp_head Reduce('b m d h w -> b d h w',
+ *   'mean'), fusion_in_one.py:404-410, padded agents included); n_elems multiple of 4.                                            */
+int heal_agent_window_attention(const float* qkv, const float* bias, int n_agents, int n_valid, int H, int W, int heads,
+                                int dim_head, int window, int mode, float scale, float* out, void* stream);
+int heal_agent_mean(const float* x, int n_agents, long long n_elems, float* out, void* stream);
 
 /* ---- V2X-ViT linear algebra (opencood/models/sub_modules/base_transformer.py:7-40, hmsa.py:38-151, mswin.py:46-122,
  * split_attn.py:6-62, v2xvit_basic.py:158-192): token-major fp32 GEMM on v_mfma_f32_32x32x2_f32 with the LayerNorm of PreNorm
