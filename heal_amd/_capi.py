@@ -248,8 +248,8 @@ def _trace_done(name):
 
 
 # ---- HEAL_GRAPH_GUARD=1: pointer ownership of captured graphs ---------------------------------------------------------
-# A captured HIP graph has every address it was handed baked in; nothing in the runtime notices when one of them is later freed (ops.py
-# keeps scratch and weight layouts alive by policy: "retire, never free").  In guard mode every device address passed through the C ABI
+# A captured HIP graph has every address it was handed baked in; nothing in the runtime notices when one of them is later freed (scratch
+# (ops._workspace) and weight-derived tensors (heal_amd/derived.py) a graph may read are retired, never freed).  In guard mode every device address passed through the C ABI
 # DURING a capture is logged; whoever owns the graph takes the log (guard_take) and has it verified before replays (guard_check): each
 # address must still lie in memory the caching allocator has handed out -- an active block of the ordinary pool, or any block of a
 # graph-private pool that is still mapped (tensors allocated and released inside a capture live there for the life of their graph).

@@ -120,7 +120,6 @@ class CoBEVT(_WarpThenFuse):
                                       _NoParams("Rearrange('b d h w -> b h w d')"),
                                       nn.LayerNorm(input_dim), nn.Linear(input_dim, input_dim),
                                       _NoParams("Rearrange('b h w d -> b d h w')"))
-        self._fh = None
 
     def _check(self, n):
         if n > self.agent_size:
@@ -150,7 +149,8 @@ class CoBEVT(_WarpThenFuse):
     def fuse_warped_pm(self, x):
         """x token-major [n, H, W, C] (one scene's real agents) -> [H, W, C] on the HIP path: padded to L once, token-major through
         every block, agent mean + LayerNorm + Linear at the end."""
-        from heal_amd.opencood.models.sub_modules.v2xvit_basic import _Folded, _fold_ln
+        from heal_amd.derived import derived
+        from heal_amd.opencood.models.sub_modules.v2xvit_basic import _fold_ln
         n, H, W, C = x.shape
         self._check(n)
         if n < self.agent_size:
@@ -163,9 +163,7 @@ class CoBEVT(_WarpThenFuse):
             x = stage.fused(x, n)
         mean = ops.agent_mean(x)                          # [H, W, C]: every agent, padded ones included
         norm, lin = self.mlp_head[2], self.mlp_head[3]
-        if self._fh is None:
-            self._fh = _Folded()
-        w, b = self._fh.get([lin.weight, lin.bias, norm.weight, norm.bias], lambda: _fold_ln(lin.weight, lin.bias, norm))
+        w, b = derived("fold_ln", (lin.weight, lin.bias, norm.weight, norm.bias), lambda: _fold_ln(lin.weight, lin.bias, norm))
         return ops.linear(mean, w, b, stats=ops.ln_stats(mean, norm.eps)).view(H, W, C)
 
     def forward(self, x, record_len, affine_matrix):

@@ -16,7 +16,8 @@ import torch
 import torch.nn as nn
 
 from heal_amd import ops
-from heal_amd.opencood.models.sub_modules.v2xvit_basic import FeedForward, _Folded, _fold_ln
+from heal_amd.derived import derived
+from heal_amd.opencood.models.sub_modules.v2xvit_basic import FeedForward, _fold_ln
 
 
 def _grad_path(x, module):
@@ -70,7 +71,6 @@ class Attention(nn.Module):
         self.relative_position_bias_table = nn.Embedding(
             (2 * agent_size - 1) * (2 * window_size - 1) * (2 * window_size - 1), self.heads)
         self.register_buffer("relative_position_index", _relative_position_index(agent_size, window_size))
-        self._f = _Folded()
 
     def forward(self, x, key_mask=None):
         """x [b, l, X, Y, w1, w2, c], key_mask [b, l] (nonzero = real agent) -> same shape (swap_fusion_modules.py:86-131)."""
@@ -95,8 +95,8 @@ class Attention(nn.Module):
         """[heads, T, T] f32: the table looked up once per weight version (inference; a captured graph keeps its address while
         the table is unchanged)."""
         tab = self.relative_position_bias_table.weight
-        return self._f.get([tab, self.relative_position_index], lambda: tab.detach()[self.relative_position_index]
-                           .permute(2, 0, 1).contiguous().float())
+        return derived("agent_window_position_bias", (tab, self.relative_position_index),
+                       lambda: tab.detach()[self.relative_position_index].permute(2, 0, 1).contiguous().float())
 
     def fused_residual(self, x, norm, n_valid, mode):
         """x token-major [L, H, W, C] -> x + to_out(attention(norm(x))): LayerNorm folded into the 256 -> 768 heal_linear, the
@@ -109,9 +109,7 @@ class Attention(nn.Module):
         return ops.linear(att, self.to_out[0].weight, None, residual=x.reshape(-1, C)).view(L, H, W, C)
 
     def _f_qkv(self, norm):
-        if getattr(self, "_fq", None) is None:
-            self._fq = _Folded()
-        return self._fq.get([self.to_qkv.weight, norm.weight, norm.bias], lambda: _fold_ln(self.to_qkv.weight, None, norm))
+        return derived("fold_ln", (self.to_qkv.weight, None, norm.weight, norm.bias), lambda: _fold_ln(self.to_qkv.weight, None, norm))
 
 
 class SwapFusionBlockMask(nn.Module):

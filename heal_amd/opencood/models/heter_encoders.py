@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 from heal_amd import ops
+from heal_amd.derived import derived
 from heal_amd.opencood.models.sub_modules.bev_blocks import grad_path
 from heal_amd.opencood.models.sub_modules.pillar_vfe import PillarVFE
 from heal_amd.opencood.models.sub_modules.point_pillar_scatter import PointPillarScatter
@@ -34,8 +35,6 @@ class PointPillar(nn.Module):
         self.pillar_vfe = PillarVFE(args["pillar_vfe"], num_point_features=4, voxel_size=args["voxel_size"],
                                     point_cloud_range=args["lidar_range"])
         self.scatter = PointPillarScatter(args["point_pillar_scatter"])
-        self._fold_key = None
-        self._fold = None
 
     # set by the model when this encoder's backbone opens with a block that reads the pillars itself (bev_blocks.BasicBlock.
     # takes_pooled): the inference forward then returns ops.PillarBEV instead of the dense canvas (HEAL_K2_POOLED=0: always dense)
@@ -53,11 +52,7 @@ class PointPillar(nn.Module):
         pfn = self.pillar_vfe.pfn_layers[0]
         tensors = [pfn.linear.weight] + ([pfn.norm.weight, pfn.norm.bias, pfn.norm.running_mean,
                                           pfn.norm.running_var] if pfn.use_norm else [pfn.linear.bias])
-        key = tuple((t.data_ptr(), t._version) for t in tensors)
-        if key != self._fold_key:
-            self._fold = pfn.folded_bn()
-            self._fold_key = key
-        return self._fold
+        return derived("pfn_folded_bn", tensors, pfn.folded_bn)
 
     def encode_points(self, point_list, max_points=None, max_voxels=None):
         """Raw device point clouds -> canvas with NO host round trip: K1 per agent into collated buffers (the running

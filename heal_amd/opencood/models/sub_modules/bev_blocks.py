@@ -8,7 +8,7 @@ naive_compress.py:5-31.
 
 Training / fine-tuning (gradients enabled, see `grad_path`): the blocks run conv -> BatchNorm -> ReLU as torch modules with
 autograd.  Inference design (eval mode): every Conv+BatchNorm pair is folded into one convolution with bias
-(cached, re-folded when a parameter changes), ReLU and the residual add run in place -- one pass
+(heal_amd.derived: re-folded when a parameter changes), ReLU and the residual add run in place -- one pass
 over each BEV map instead of three.  Pointwise, dense 3x3 (padding 1, stride 1 | 2) and 32-group 3x3 convolutions run on
 the hand-written fp32-MFMA / stencil kernels of libheal_amd with that epilogue fused; what is left to the library
 (MIOpen through torch) are the 7x7 stems and kernel != stride transposed convolutions.
@@ -18,33 +18,21 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-
-def _versions(*tensors):
-    return tuple((t.data_ptr(), t._version) for t in tensors if t is not None)
+from heal_amd.derived import derived
 
 
-class _FoldCache:
-    """Folded (weight, bias) of a conv followed by an eval-mode BatchNorm, cached per module pair."""
-
-    def __init__(self):
-        self.key = None
-        self.value = None
-
-    def get(self, conv, bn, transposed=False):
-        tensors = [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        key = _versions(*tensors)
-        if key != self.key:
-            with torch.no_grad():
-                scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-                shift = bn.bias - bn.running_mean * scale
-                if transposed:  # ConvTranspose2d weight is [Cin, Cout/groups, k, k]
-                    w = conv.weight * scale.view(1, -1, 1, 1)
-                else:
-                    w = conv.weight * scale.view(-1, 1, 1, 1)
-                b = shift if conv.bias is None else shift + conv.bias * scale
-                self.value = (w.contiguous(), b.contiguous())
-            self.key = key
-        return self.value
+def fold_bn(conv, bn, transposed=False):
+    """Folded (weight, bias) of a conv followed by an eval-mode BatchNorm."""
+    def build():
+        scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
+        shift = bn.bias - bn.running_mean * scale
+        if transposed:  # ConvTranspose2d weight is [Cin, Cout/groups, k, k]
+            w = conv.weight * scale.view(1, -1, 1, 1)
+        else:
+            w = conv.weight * scale.view(-1, 1, 1, 1)
+        b = shift if conv.bias is None else shift + conv.bias * scale
+        return w.contiguous(), b.contiguous()
+    return derived("fold_bn", (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var), build, (transposed,))
 
 
 import os
@@ -135,21 +123,21 @@ class ConvBN(nn.Module):
     owner; this helper only provides the folded forward."""
 
     @staticmethod
-    def run(x, conv, bn, cache, relu, residual=None, out=None):
+    def run(x, conv, bn, relu, residual=None, out=None):
         if out is not None and not grad_path(x, bn, conv):      # (inference: the agent-chunked / camera-crop stage walks)
-            w, b = cache.get(conv, bn)
+            w, b = fold_bn(conv, bn)
             y = conv_bias_act(x, w, b, conv.stride, conv.padding, conv.dilation, conv.groups, relu, residual, out=out)
             if y.data_ptr() != out.data_ptr():
                 out.copy_(y)
             return out
         if out is not None:      # gradient path with a destination (CPU tests of the stage walks): compute, then copy
-            return out.copy_(ConvBN.run(x, conv, bn, cache, relu, residual))
+            return out.copy_(ConvBN.run(x, conv, bn, relu, residual))
         if grad_path(x, bn, conv):   # training / fine-tuning: conv -> BatchNorm (batch statistics when training) -> + -> ReLU
             y = bn(conv(x))
             if residual is not None:
                 y = y + residual
             return F.relu(y) if relu else y
-        w, b = cache.get(conv, bn)
+        w, b = fold_bn(conv, bn)
         return conv_bias_act(x, w, b, conv.stride, conv.padding, conv.dilation, conv.groups, relu, residual)
 
 
@@ -179,7 +167,6 @@ class BasicBlock(nn.Module):
         self.bn2 = norm_layer(planes)
         self.downsample = downsample
         self.stride = stride
-        self._c1, self._c2, self._cd = _FoldCache(), _FoldCache(), _FoldCache()
 
     def takes_pooled(self):
         """True if this block can read K4's sparse pixel-major map (ops.PooledBEV) directly: conv1 3x3 stride 2 pad 1 and a
@@ -193,14 +180,10 @@ class BasicBlock(nn.Module):
 
     def _stem_params(self, x):
         from heal_amd import ops
-        w1, b1 = self._c1.get(self.conv1, self.bn1)
-        wd, bd = self._cd.get(self.downsample[0], self.downsample[1])
+        w1, b1 = fold_bn(self.conv1, self.bn1)
+        wd, bd = fold_bn(self.downsample[0], self.downsample[1])
         frag = getattr(x, "fragments", ops.stem_fragments)     # the weight layout the sparse input's kernel reads
-        key = (self._c1.key, self._cd.key, getattr(x, "weight_layout", "tiles"))
-        if getattr(self, "_stem_key", None) != key:
-            self._stem = frag(w1, wd) + (b1, bd)
-            self._stem_key = key
-        return self._stem
+        return derived("stem_block", (w1, b1, wd, bd), lambda: frag(w1, wd) + (b1, bd), (getattr(x, "weight_layout", "tiles"),))
 
     def forward(self, x):
         from heal_amd import ops
@@ -209,13 +192,13 @@ class BasicBlock(nn.Module):
                     and x.stem_supported(self.conv1.out_channels, self.downsample[0].out_channels)):
                 wm, wd, b1, bd = self._stem_params(x)
                 out, identity = x.stem_block(wm, b1, wd, bd)
-                return ConvBN.run(out, self.conv2, self.bn2, self._c2, relu=True, residual=identity)
+                return ConvBN.run(out, self.conv2, self.bn2, relu=True, residual=identity)
             x = x.dense()
         identity = x
         if self.downsample is not None:
-            identity = ConvBN.run(x, self.downsample[0], self.downsample[1], self._cd, relu=False)
-        out = ConvBN.run(x, self.conv1, self.bn1, self._c1, relu=True)
-        return ConvBN.run(out, self.conv2, self.bn2, self._c2, relu=True, residual=identity)
+            identity = ConvBN.run(x, self.downsample[0], self.downsample[1], relu=False)
+        out = ConvBN.run(x, self.conv1, self.bn1, relu=True)
+        return ConvBN.run(out, self.conv2, self.bn2, relu=True, residual=identity)
 
 
 class Bottleneck(nn.Module):
@@ -237,22 +220,16 @@ class Bottleneck(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
         self.stride = stride
-        self._c1, self._c2, self._c3, self._cd = _FoldCache(), _FoldCache(), _FoldCache(), _FoldCache()
-        self._fused_key = None
-        self._fused = None
 
     def _fused_params(self):
         """Folded weights of the three convolutions in the layout heal_resnext_bottleneck wants."""
         from heal_amd import ops
-        w1, b1 = self._c1.get(self.conv1, self.bn1)
-        w2, b2 = self._c2.get(self.conv2, self.bn2)
-        w3, b3 = self._c3.get(self.conv3, self.bn3)
-        key = (self._c1.key, self._c2.key, self._c3.key)
-        if key != self._fused_key:
-            self._fused = (ops.mfma_a_fragments(w1.reshape(w1.shape[0], w1.shape[1])), b1, w2, b2,
-                           ops.mfma_a_fragments(w3.reshape(w3.shape[0], w3.shape[1])), b3)
-            self._fused_key = key
-        return self._fused
+        w1, b1 = fold_bn(self.conv1, self.bn1)
+        w2, b2 = fold_bn(self.conv2, self.bn2)
+        w3, b3 = fold_bn(self.conv3, self.bn3)
+        return derived("resnext_bottleneck", (w1, b1, w2, b2, w3, b3), lambda: (
+            ops.mfma_a_fragments(w1.reshape(w1.shape[0], w1.shape[1])), b1, w2, b2,
+            ops.mfma_a_fragments(w3.reshape(w3.shape[0], w3.shape[1])), b3))
 
     def _fusable(self, x):
         # The fused kernel (heal_resnext_bottleneck) is correct but, at one workgroup per CU, still slower
@@ -280,10 +257,10 @@ class Bottleneck(nn.Module):
             return y if out is None else out.copy_(y)
         identity = x
         if self.downsample is not None:
-            identity = ConvBN.run(x, self.downsample[0], self.downsample[1], self._cd, relu=False)
-        y = ConvBN.run(x, self.conv1, self.bn1, self._c1, relu=True)
-        y = ConvBN.run(y, self.conv2, self.bn2, self._c2, relu=True)
-        return ConvBN.run(y, self.conv3, self.bn3, self._c3, relu=True, residual=identity, out=out)
+            identity = ConvBN.run(x, self.downsample[0], self.downsample[1], relu=False)
+        y = ConvBN.run(x, self.conv1, self.bn1, relu=True)
+        y = ConvBN.run(y, self.conv2, self.bn2, relu=True)
+        return ConvBN.run(y, self.conv3, self.bn3, relu=True, residual=identity, out=out)
 
 
 class ResNetModified(nn.Module):
@@ -364,7 +341,6 @@ class _Deblock(nn.Sequential):
 
     def __init__(self, conv, bn):
         super().__init__(conv, bn, nn.ReLU())
-        self._cache = _FoldCache()
 
     def out_shape(self, x):
         """(channels, H, W) of the output for input x (what decode_multiscale_feature sizes the concatenated tensor with)."""
@@ -390,7 +366,7 @@ class _Deblock(nn.Sequential):
         conv, bn = self[0], self[1]
         from heal_amd import ops
         if isinstance(conv, nn.ConvTranspose2d):
-            w, b = self._cache.get(conv, bn, transposed=True)
+            w, b = fold_bn(conv, bn, transposed=True)
             k = conv.kernel_size[0]
             if (_CONV1X1 and x.is_cuda and conv.kernel_size == conv.stride and conv.kernel_size[0] == conv.kernel_size[1]
                     and conv.padding == (0, 0) and conv.output_padding == (0, 0) and conv.groups == 1
@@ -398,20 +374,17 @@ class _Deblock(nn.Sequential):
                 # kernel == stride: the transposed convolution is a pointwise convolution to Cout*k*k channels followed
                 # by a depth-to-space shuffle; bias and ReLU commute with the shuffle, so they ride in the conv1x1
                 # epilogue (the library path is GEMM + col2im + a bias/ReLU pass)
-                key = (w.data_ptr(), w._version, b.data_ptr(), b._version)
-                if getattr(self, "_ps_key", None) != key:
-                    cin, cout = int(w.shape[0]), int(w.shape[1])
-                    self._ps = (w.permute(1, 2, 3, 0).reshape(cout * k * k, cin, 1, 1).contiguous(),
-                                b.repeat_interleave(k * k).contiguous())
-                    self._ps_key = key
+                cin, cout = int(w.shape[0]), int(w.shape[1])
+                wp, bp = derived("deblock_pointwise", (w, b), lambda: (
+                    w.permute(1, 2, 3, 0).reshape(cout * k * k, cin, 1, 1).contiguous(), b.repeat_interleave(k * k).contiguous()))
                 if into is not None and int(x.shape[3]) % 4 == 0 and into[0].is_contiguous():
                     # bias, ReLU, the depth-to-space shuffle AND the concatenation ride in the conv1x1 epilogue
-                    return ops.conv1x1_d2s(x, self._ps[0], self._ps[1], 1, k, into[0], into[1])
-                y = ops.conv1x1(x, self._ps[0], self._ps[1], None, 1)
+                    return ops.conv1x1_d2s(x, wp, bp, 1, k, into[0], into[1])
+                y = ops.conv1x1(x, wp, bp, None, 1)
                 return y if k == 1 else F.pixel_shuffle(y, k)
             y = F.conv_transpose2d(x, w, None, conv.stride, conv.padding, conv.output_padding, conv.groups)
             return ops.bias_act_(y, b, None, True)
-        w, b = self._cache.get(conv, bn)
+        w, b = fold_bn(conv, bn)
         return conv_bias_act(x, w, b, conv.stride, conv.padding, 1, 1, True)
 
 
@@ -566,17 +539,13 @@ class ConvNeXtBlock(nn.Module):
             if layer_scale_init_value > 0 else None
 
     def _folded_pw2(self):
-        """pwconv2 with the layer scale folded in: gamma * (W2 h + b2) = (gamma . W2) h + gamma . b2 (cached)."""
-        t = [self.pwconv2.weight, self.pwconv2.bias] + ([self.gamma] if self.gamma is not None else [])
-        key = _versions(*t)
-        if getattr(self, "_pw2_key", None) != key:
-            with torch.no_grad():
-                w, b = self.pwconv2.weight, self.pwconv2.bias
-                if self.gamma is not None:
-                    w, b = w * self.gamma[:, None], b * self.gamma
-                self._pw2 = (w.contiguous()[:, :, None, None], b.contiguous())
-            self._pw2_key = key
-        return self._pw2
+        """pwconv2 with the layer scale folded in: gamma * (W2 h + b2) = (gamma . W2) h + gamma . b2."""
+        def build():
+            w, b = self.pwconv2.weight, self.pwconv2.bias
+            if self.gamma is not None:
+                w, b = w * self.gamma[:, None], b * self.gamma
+            return w.contiguous()[:, :, None, None], b.contiguous()
+        return derived("convnext_pw2", (self.pwconv2.weight, self.pwconv2.bias, self.gamma), build)
 
     def forward(self, x):
         from heal_amd import ops
@@ -646,16 +615,15 @@ class NaiveCompressor(nn.Module):
                                      nn.BatchNorm2d(input_dim, eps=1e-3, momentum=0.01), nn.ReLU(),
                                      nn.Conv2d(input_dim, input_dim, 3, 1, 1),
                                      nn.BatchNorm2d(input_dim, eps=1e-3, momentum=0.01), nn.ReLU())
-        self._c = [_FoldCache() for _ in range(3)]
 
     def encode(self, x):
         """The half that runs on the SENDING agent: [n, C, H, W] -> [n, C / ratio, H, W] (what travels, naive_compress.py:25)."""
-        return ConvBN.run(x, self.encoder[0], self.encoder[1], self._c[0], relu=True)
+        return ConvBN.run(x, self.encoder[0], self.encoder[1], relu=True)
 
     def decode(self, z):
         """The half that runs on the RECEIVING agent (naive_compress.py:26-29)."""
-        z = ConvBN.run(z, self.decoder[0], self.decoder[1], self._c[1], relu=True)
-        return ConvBN.run(z, self.decoder[3], self.decoder[4], self._c[2], relu=True)
+        z = ConvBN.run(z, self.decoder[0], self.decoder[1], relu=True)
+        return ConvBN.run(z, self.decoder[3], self.decoder[4], relu=True)
 
     def forward(self, x):
         return self.decode(self.encode(x))

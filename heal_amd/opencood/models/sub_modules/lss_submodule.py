@@ -16,7 +16,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from heal_amd.opencood.models.sub_modules.bev_blocks import (BasicBlock, Bottleneck, ConvBN, _FoldCache, conv_bias_act,
+from heal_amd.derived import derived
+from heal_amd.opencood.models.sub_modules.bev_blocks import (BasicBlock, Bottleneck, ConvBN, conv_bias_act, fold_bn,
                                                              grad_path)
 
 
@@ -31,15 +32,14 @@ class Up(nn.Module):
             nn.ReLU(inplace=True),
             nn.Conv2d(out_channels, out_channels, kernel_size=3, padding=1, bias=False), nn.BatchNorm2d(out_channels),
             nn.ReLU(inplace=True))
-        self._c = [_FoldCache(), _FoldCache()]
 
     def forward(self, x1, x2):
         from heal_amd import ops
         fused = x1.is_cuda and self.up.scale_factor == 2 and not grad_path(x1, self)
         up = ops.upsample2x_bilinear(x1) if fused else self.up(x1)
         x = torch.cat([x2, up], dim=1)
-        x = ConvBN.run(x, self.conv[0], self.conv[1], self._c[0], relu=True)
-        return ConvBN.run(x, self.conv[3], self.conv[4], self._c[1], relu=True)
+        x = ConvBN.run(x, self.conv[0], self.conv[1], relu=True)
+        return ConvBN.run(x, self.conv[3], self.conv[4], relu=True)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -66,7 +66,7 @@ class _SamePadConv2d(nn.Conv2d):
         self.static_padding = nn.ZeroPad2d(self.same_pad) if (pad_h > 0 or pad_w > 0) else nn.Identity()
 
 
-def _conv_bn(x, conv, bn, cache, act, in_scale=None, residual=None, channel_sums=False):
+def _conv_bn(x, conv, bn, act, in_scale=None, residual=None, channel_sums=False):
     """conv + folded BatchNorm (+ SiLU).  Pointwise convolutions run on heal_conv1x1 with the squeeze-excite gate
     (in_scale, per image and input channel), the bias, the skip connection and the activation fused."""
     if grad_path(x, bn, conv):   # gradient path: the package's own composition (scale, pad, conv, BatchNorm, swish, skip)
@@ -75,7 +75,7 @@ def _conv_bn(x, conv, bn, cache, act, in_scale=None, residual=None, channel_sums
         y = bn(conv(conv.static_padding(x)))
         y = F.silu(y) if act else y
         return y + residual if residual is not None else y
-    w, b = cache.get(conv, bn)
+    w, b = fold_bn(conv, bn)
     if (x.is_cuda and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.groups == 1
             and not any(conv.same_pad)):
         from heal_amd import ops
@@ -116,23 +116,22 @@ class _MBConv(nn.Module):
         self._se_expand = _SamePadConv2d(sq, mid, 1, bias=True, image_size=1)
         self._project_conv = _SamePadConv2d(mid, oup, 1, image_size=out_size)
         self._bn2 = nn.BatchNorm2d(oup, momentum=0.01, eps=1e-3)
-        self._c = [_FoldCache(), _FoldCache(), _FoldCache()]
 
     def forward(self, x):
         inp = x
         if self.expand != 1:
-            x = _conv_bn(x, self._expand_conv, self._bn0, self._c[0], act=True)
+            x = _conv_bn(x, self._expand_conv, self._bn0, act=True)
         from heal_amd import ops
         dw = self._depthwise_conv
         if (x.is_cuda and not grad_path(x, self) and dw.kernel_size[0] in (3, 5) and dw.stride[0] in (1, 2)
                 and x.shape[0] * dw.in_channels <= 65535):
             # the squeeze (spatial mean) rides in the depthwise launch as per-tile sums; the gate kernel adds them up and scales
-            x, sums = _conv_bn(x, dw, self._bn1, self._c[1], act=True, channel_sums=True)
+            x, sums = _conv_bn(x, dw, self._bn1, act=True, channel_sums=True)
             gate = ops.se_gate(sums, self._se_reduce.weight, self._se_reduce.bias, self._se_expand.weight,
                                self._se_expand.bias, scale=1.0 / float(x.shape[2] * x.shape[3]), tiles=int(sums.shape[2]))
-            return _conv_bn(x, self._project_conv, self._bn2, self._c[2], act=False, in_scale=gate[:, :, None, None],
+            return _conv_bn(x, self._project_conv, self._bn2, act=False, in_scale=gate[:, :, None, None],
                             residual=inp if self.id_skip else None)
-        x = _conv_bn(x, dw, self._bn1, self._c[1], act=True)
+        x = _conv_bn(x, dw, self._bn1, act=True)
         # efficientnet_pytorch MBConvBlock: s = expand(silu(reduce(avgpool(x)))); x = sigmoid(s) * x; project; (+ skip)
         if grad_path(x, self):
             s_ = self._se_expand(F.silu(self._se_reduce(x.mean((2, 3), keepdim=True))))
@@ -140,7 +139,7 @@ class _MBConv(nn.Module):
         else:
             gate = ops.se_gate(x.mean((2, 3)), self._se_reduce.weight, self._se_reduce.bias, self._se_expand.weight,
                                self._se_expand.bias)
-        return _conv_bn(x, self._project_conv, self._bn2, self._c[2], act=False, in_scale=gate[:, :, None, None],
+        return _conv_bn(x, self._project_conv, self._bn2, act=False, in_scale=gate[:, :, None, None],
                         residual=inp if self.id_skip else None)
 
 
@@ -160,12 +159,11 @@ class EfficientNetB0(nn.Module):
         self._conv_head = _SamePadConv2d(320, 1280, 1, image_size=size)  # present for checkpoint parity, unused
         self._bn1 = nn.BatchNorm2d(1280, momentum=0.01, eps=1e-3)
         self._fc = nn.Linear(1280, 1000)
-        self._c0 = _FoldCache()
 
     def endpoints(self, x):
         """lss_submodule.py:87-107: feature maps just before every spatial reduction, plus the last."""
         out = {}
-        x = _conv_bn(x, self._conv_stem, self._bn0, self._c0, act=True)
+        x = _conv_bn(x, self._conv_stem, self._bn0, act=True)
         prev = x
         for block in self._blocks:
             x = block(x)
@@ -220,15 +218,10 @@ class _CamEncodeBase(nn.Module):
         return items, depth_logit, x_img
 
     def _fused_head(self):
-        """image_head | depth_head as ONE [C + D, 512] pointwise weight (cached per parameter version)."""
+        """image_head | depth_head as ONE [C + D, 512] pointwise weight."""
         hs = (self.image_head, self.depth_head)
-        key = tuple((h.weight.data_ptr(), h.weight._version, h.bias.data_ptr(), h.bias._version) for h in hs)
-        hit = self.__dict__.get("_heal_fused_head")
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                hit = (key, torch.cat([h.weight for h in hs], 0).contiguous(), torch.cat([h.bias for h in hs], 0).contiguous())
-            self.__dict__["_heal_fused_head"] = hit  # plain attribute: not a parameter, not in the state_dict
-        return hit[1], hit[2]
+        return derived("lss_fused_head", [t for h in hs for t in (h.weight, h.bias)], lambda: (
+            torch.cat([h.weight for h in hs], 0).contiguous(), torch.cat([h.bias for h in hs], 0).contiguous()))
 
     def heads_pixel_major(self, features, x):
         """The two 1x1 heads (lss_submodule.py:113,127) as one convolution that writes PIXEL-MAJOR [BN, fH*fW, C + D] (a pixel's
@@ -297,7 +290,6 @@ class CamEncode_Resnet101(_CamEncodeBase):
         self.layer3 = nn.Identity()
         self.depth_head = nn.Conv2d(512, self.D, kernel_size=1, padding=0)
         self.image_head = nn.Conv2d(512, self.C, kernel_size=1, padding=0)
-        self._c = _FoldCache()
 
     @staticmethod
     def _make_layer(inplanes, planes, blocks, stride):
@@ -314,9 +306,9 @@ class CamEncode_Resnet101(_CamEncodeBase):
             # in place (heal_stem7x7): no channel-slice copy, no library convolution, the 64-channel half-resolution map never
             # reaches HBM
             from heal_amd import ops
-            w, b = self._c.get(self.conv1, self.bn1)
+            w, b = fold_bn(self.conv1, self.bn1)
             return self.layer2(self.layer1(ops.stem7x7(x, w, b, pool=True)))
-        f = ConvBN.run(x[:, :3, :, :], self.conv1, self.bn1, self._c, relu=True)
+        f = ConvBN.run(x[:, :3, :, :], self.conv1, self.bn1, relu=True)
         return self.layer2(self.layer1(self.maxpool(f)))
 
 
@@ -338,7 +330,6 @@ class BevEncode(nn.Module):
             nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True),
             nn.Conv2d(256, 128, kernel_size=3, padding=1, bias=False), nn.BatchNorm2d(128), nn.ReLU(inplace=True),
             nn.Conv2d(128, outC, kernel_size=1, padding=0))
-        self._c = [_FoldCache(), _FoldCache()]
 
     @staticmethod
     def _make_layer(inplanes, planes, stride):
@@ -349,11 +340,11 @@ class BevEncode(nn.Module):
 
     def forward(self, x):
         from heal_amd import ops
-        x = ConvBN.run(x, self.conv1, self.bn1, self._c[0], relu=True)
+        x = ConvBN.run(x, self.conv1, self.bn1, relu=True)
         x1 = self.layer1(x)
         x = self.layer3(self.layer2(x1))
         x = self.up1(x, x1)
         x = ops.upsample2x_bilinear(x) if (x.is_cuda and not grad_path(x, self)) else self.up2[0](x)
-        x = ConvBN.run(x, self.up2[1], self.up2[2], self._c[1], relu=True)
+        x = ConvBN.run(x, self.up2[1], self.up2[2], relu=True)
         last = self.up2[4]
         return conv_bias_act(x, last.weight, last.bias, last.stride, last.padding, 1, 1, False)

@@ -19,6 +19,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from heal_amd.derived import derived
+
 
 class SparseConvParam(nn.Module):
     """Weight container of one SubMConv3d / SparseConv3d (bias=False)."""
@@ -84,18 +86,14 @@ class _Block(nn.Sequential):
 
     def __init__(self, conv, channels):
         super().__init__(conv, nn.BatchNorm1d(channels, eps=1e-3, momentum=0.01), nn.ReLU())
-        self._key = None
-        self._fold = None
 
     def bn(self):
         bn = self[1]
-        key = tuple((t.data_ptr(), t._version) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
-        if key != self._key:
-            with torch.no_grad():
-                scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-                self._fold = (scale.contiguous(), (bn.bias - bn.running_mean * scale).contiguous())
-            self._key = key
-        return self._fold
+
+        def build():
+            scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
+            return scale.contiguous(), (bn.bias - bn.running_mean * scale).contiguous()
+        return derived("bn_scale_shift", (bn.weight, bn.bias, bn.running_mean, bn.running_var), build)
 
     def run_dense(self, x, mask):
         """Gradient path of one block on dense tensors: x [B,Cin,D,H,W] (zero at inactive cells), mask [B,1,D,H,W] ->

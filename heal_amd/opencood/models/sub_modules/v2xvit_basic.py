@@ -11,7 +11,7 @@ Module / parameter layout mirrors the reference so that checkpoints load.  Execu
     round-2 library path for A/B);
   * HGTCavAttention: HEAL always passes a zero prior encoding (fusion_in_one.py:346-355), so every agent
     has type 0 and only relation 0 is exercised.  The per-head relation matrices are folded into the q / v
-    projections once (cached), and the per-pixel L x L attention runs in the fused kernel K6;
+    projections once (heal_amd.derived), and the per-pixel L x L attention runs in the fused kernel K6;
   * padded agents are not materialised: they are masked keys and never reach the ego row, so the
     transformer runs on the real agents only;
   * STTF / ROI mask: with the identity spatial-correction matrices HEAL passes (fusion_in_one.py:367) the
@@ -26,6 +26,7 @@ import torch.nn.functional as F
 import os
 
 from heal_amd import ops
+from heal_amd.derived import derived
 
 
 def _grad_path(x, module):
@@ -38,21 +39,6 @@ def _fused_ok(x, module):
         return False
     L, H, W, C = x.shape
     return C % 128 == 0 and (H * W) % 128 == 0 and x.dtype == torch.float32
-
-
-class _Folded:
-    """Cache of derived weights, rebuilt when any source tensor changes (data_ptr / version)."""
-
-    def __init__(self):
-        self.key, self.val = None, None
-
-    def get(self, tensors, build):
-        key = tuple((t.data_ptr(), t._version) for t in tensors)
-        if key != self.key:
-            with torch.no_grad():
-                self.val = build()
-            self.key = key
-        return self.val
 
 
 def _fold_ln(weight_nk, bias, norm):
@@ -85,7 +71,6 @@ class FeedForward(nn.Module):
         super().__init__()
         self.net = nn.Sequential(nn.Linear(dim, hidden_dim), nn.GELU(), nn.Dropout(dropout),
                                  nn.Linear(hidden_dim, dim), nn.Dropout(dropout))
-        self._f = _Folded()
 
     def forward(self, x):
         if _grad_path(x, self):
@@ -97,7 +82,7 @@ class FeedForward(nn.Module):
         l1, l2 = self.net[0], self.net[3]
         if not (ops.linear_supported(1, l1.in_features, l1.out_features) and ops.linear_supported(1, l2.in_features, l2.out_features)):
             return self.forward(norm(x)) + x
-        w1, b1 = self._f.get([l1.weight, l1.bias, norm.weight, norm.bias], lambda: _fold_ln(l1.weight, l1.bias, norm))
+        w1, b1 = derived("fold_ln", (l1.weight, l1.bias, norm.weight, norm.bias), lambda: _fold_ln(l1.weight, l1.bias, norm))
         shp = x.shape
         h = ops.linear(x, w1, b1, stats=ops.ln_stats(x, norm.eps), act="gelu")
         return ops.linear(h, l2.weight, l2.bias, residual=x.reshape(-1, shp[-1])).view(shp)
@@ -123,30 +108,25 @@ class HGTCavAttention(nn.Module):
         nn.init.xavier_uniform_(self.relation_att)
         nn.init.xavier_uniform_(self.relation_msg)
         self.drop_out = nn.Dropout(dropout)   # hmsa.py:57,149: applied to the projected output (active in training only)
-        self._key = None
-        self._qkv = None
-        self._f = _Folded()
 
     def _folded_qkv(self):
         """[dim, 3*inner] weight and bias of x -> (q W_att, k, v W_msg) for agent type 0 / relation 0:
         att = (q W_att) . k   (hmsa.py:131-134),  message = v W_msg   (hmsa.py:141-143)."""
         ts = [self.q_linears[0].weight, self.q_linears[0].bias, self.k_linears[0].weight, self.k_linears[0].bias,
               self.v_linears[0].weight, self.v_linears[0].bias, self.relation_att, self.relation_msg]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        if key != self._key:
-            with torch.no_grad():
-                m, d = self.heads, self.dim_head
-                wa = torch.block_diag(*[self.relation_att[0, h] for h in range(m)])   # [inner, inner]
-                wm = torch.block_diag(*[self.relation_msg[0, h] for h in range(m)])
-                wq = self.q_linears[0].weight.t() @ wa            # x @ Wq^T @ blockdiag(W_att)
-                bq = self.q_linears[0].bias @ wa
-                wv = self.v_linears[0].weight.t() @ wm
-                bv = self.v_linears[0].bias @ wm
-                w = torch.cat([wq, self.k_linears[0].weight.t(), wv], dim=1).contiguous()
-                b = torch.cat([bq, self.k_linears[0].bias, bv]).contiguous()
-                self._qkv = (w, b)
-            self._key = key
-        return self._qkv
+
+        def build():
+            m = self.heads
+            wa = torch.block_diag(*[self.relation_att[0, h] for h in range(m)])   # [inner, inner]
+            wm = torch.block_diag(*[self.relation_msg[0, h] for h in range(m)])
+            wq = self.q_linears[0].weight.t() @ wa            # x @ Wq^T @ blockdiag(W_att)
+            bq = self.q_linears[0].bias @ wa
+            wv = self.v_linears[0].weight.t() @ wm
+            bv = self.v_linears[0].bias @ wm
+            w = torch.cat([wq, self.k_linears[0].weight.t(), wv], dim=1).contiguous()
+            b = torch.cat([bq, self.k_linears[0].bias, bv]).contiguous()
+            return w, b
+        return derived("hgt_folded_qkv", ts, build)
 
     def forward(self, x, mask=None, prior_encoding=None):
         """x [L,H,W,C] (one scene, real agents only) -> [L,H,W,C]."""
@@ -187,7 +167,7 @@ class HGTCavAttention(nn.Module):
         if inner != 256 or not ops.linear_supported(1, C, 3 * inner):
             return self.forward(norm(x)) + x
         w, b = self._folded_qkv()                                        # [C, 3 inner], [3 inner]
-        wq, bq = self._f.get([w, b, norm.weight, norm.bias], lambda: _fold_ln(w.t().contiguous(), b, norm))
+        wq, bq = derived("fold_ln_t", (w, b, norm.weight, norm.bias), lambda: _fold_ln(w.t().contiguous(), b, norm))
         qkv = ops.linear(x, wq, bq, stats=ops.ln_stats(x, norm.eps), parts=3).view(3, L, H * W, inner)
         out = ops.agent_attention(qkv[0], qkv[1], qkv[2], self.heads, self.scale, agent_major=True)   # [L, HW, inner]
         a = self.a_linears[0]
@@ -205,11 +185,9 @@ class HGTCavAttention(nn.Module):
         if inner != 256 or not ops.linear_supported(1, C, 3 * inner):
             return None
         w, b = self._folded_qkv()                                        # [C, 3 inner], [3 inner]: (q W_att | k | v W_msg)
-        wq, bq = self._f.get([w, b, norm.weight, norm.bias], lambda: _fold_ln(w.t().contiguous(), b, norm))
-        if getattr(self, "_fe", None) is None:
-            self._fe = _Folded()
-        w_q, b_q, w_kv, b_kv = self._fe.get([wq, bq], lambda: (wq[:inner].contiguous(), bq[:inner].contiguous(),
-                                                                wq[inner:].contiguous(), bq[inner:].contiguous()))
+        wq, bq = derived("fold_ln_t", (w, b, norm.weight, norm.bias), lambda: _fold_ln(w.t().contiguous(), b, norm))
+        w_q, b_q, w_kv, b_kv = derived("hgt_ego_split", (wq, bq), lambda: (wq[:inner].contiguous(), bq[:inner].contiguous(),
+                                                                            wq[inner:].contiguous(), bq[inner:].contiguous()))
         n_pix = H * W
         stats = ops.ln_stats(x, norm.eps)
         kv = ops.linear(x, w_kv, b_kv, stats=stats, parts=2).view(2, L, n_pix, inner)
@@ -282,12 +260,7 @@ class BaseWindowAttention(nn.Module):
             if torch.is_grad_enabled() and pe.requires_grad:
                 return pe[ri[0], ri[1]]
             # inference: the [T, T] table of a parameter version is looked up once, not per forward (3 index kernels per block)
-            key = (pe.data_ptr(), pe._version, str(device))
-            hit = self.__dict__.get("_bias_tab")
-            if hit is None or hit[0] != key:
-                hit = (key, pe.detach()[ri[0], ri[1]].contiguous())
-                self.__dict__["_bias_tab"] = hit
-            return hit[1]
+            return derived("window_position_bias", (pe,), lambda: pe.detach()[ri[0], ri[1]].contiguous(), (str(device),))
         return self.pos_embedding
 
 
@@ -324,7 +297,6 @@ class PyramidWindowAttention(nn.Module):
         self.pwmsa = nn.ModuleList([BaseWindowAttention(dim, h, d, drop_out, w, relative_pos_embedding)
                                     for h, d, w in zip(heads, dim_heads, window_size)])
         self.fuse_mehod = fuse_method
-        self._f, self._fo, self._fc = _Folded(), _Folded(), _Folded()
         # Row stripes (heal_amd/dist.py, ShardedBaselineStriped): x is rows [r Hs, (r + 1) Hs) of every agent's map, Hs a multiple
         # of the largest window.  Windows never cross a stripe, so everything here is local EXCEPT split attention's global
         # average: `_stripe.all_gather(t)` -> [world, *t.shape] is the only exchange (the per-chunk column sums, 12 KB per agent).
@@ -350,16 +322,16 @@ class PyramidWindowAttention(nn.Module):
         if not ok or (self.fuse_mehod != "naive" and self.split_attn.input_dim != C):
             return self.forward(norm(x)) + x
         srcs = [w.to_qkv.weight for w in ws] + [norm.weight, norm.bias]
-        wq, bq = self._f.get(srcs, lambda: _fold_ln(torch.cat([w.to_qkv.weight for w in ws], 0), None, norm))
+        wq, bq = derived("pyramid_window_qkv", srcs, lambda: _fold_ln(torch.cat([w.to_qkv.weight for w in ws], 0), None, norm))
         T = L * H * W
         qkv = ops.linear(x, wq, bq, stats=ops.ln_stats(x, norm.eps), parts=3)        # [3, T, 3 C]
         branches = torch.empty((3, T, C), dtype=torch.float32, device=x.device)
         for i, w in enumerate(ws):
             ops.window_attention(qkv[i].view(L, H, W, 3 * C), w.position_bias(x.device), w.heads, w.dim_head, w.window_size,
                                  w.scale, out=branches[i])
-        wo, bo = self._fo.get([w.to_out[0].weight for w in ws] + [w.to_out[0].bias for w in ws], lambda: (
+        wo, bo = derived("pyramid_window_out", [w.to_out[0].weight for w in ws] + [w.to_out[0].bias for w in ws], lambda: (
             torch.stack([w.to_out[0].weight for w in ws]).contiguous(), torch.stack([w.to_out[0].bias for w in ws]).contiguous()))
-        wo_cat = self._fc.get([wo], lambda: torch.cat([wo[0], wo[1], wo[2]], 1).contiguous())   # [C, 3 C]: K runs over branches
+        wo_cat = derived("pyramid_window_out_cat", (wo,), lambda: torch.cat([wo[0], wo[1], wo[2]], 1).contiguous())   # [C, 3 C]: K runs over branches
         if self.fuse_mehod == "naive":
             scale = torch.full((L, 3, C), 1.0 / 3.0, dtype=torch.float32, device=x.device)
             bias = (bo.sum(0) / 3.0).expand(L, C).contiguous()

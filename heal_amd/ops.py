@@ -10,7 +10,8 @@ import os
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, derived
+from .derived import derived as _derived
 
 _WS = {}
 
@@ -135,30 +136,19 @@ def _need(t, dtype, name):
     return t.contiguous()
 
 
-_WS_RETIRED = []
-
-
-def _retire_cache(cache):
-    """Evict a weight-layout cache WITHOUT freeing its device tensors: a captured HIP graph may have their addresses baked in
-    (same policy as `_workspace`); every tensor found in the cached values moves to the keep-alive list."""
-    for v in cache.values():
-        for t in (v if isinstance(v, (tuple, list)) else (v,)):
-            if isinstance(t, torch.Tensor) and t.is_cuda:
-                _WS_RETIRED.append(t)
-    cache.clear()
-
-
-def _workspace(key, nbytes, device):
+def _workspace(key, nbytes, device, zeroed=False):
     """Grow-only per-(op, device) scratch buffer (256-B aligned by the caching allocator).  A buffer that is outgrown is
-    RETIRED, not freed: a captured HIP graph may have its address baked in, and handing the memory back to the caching
-    allocator would let a later replay scribble over somebody else's tensor."""
+    RETIRED (derived.retire), not freed: a captured HIP graph may have its address baked in, and handing the memory back to the
+    caching allocator would let a later replay scribble over somebody else's tensor.  zeroed=True: scratch with a zero-on-entry /
+    zero-on-exit contract (heal_bev_pool_pm), allocated zero-filled ONCE and then owned by the operator, which leaves it clean
+    after every call."""
     # one scratch per (operator, device, STREAM): modalities encoded on concurrent streams must not share scratch
     k = (key, device.index, torch.cuda.current_stream(device).cuda_stream)
     buf = _WS.get(k)
     if buf is None or buf.numel() < nbytes:
         if buf is not None:
-            _WS_RETIRED.append(buf)
-        buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+            derived.retire(buf)
+        buf = (torch.zeros if zeroed else torch.empty)(max(int(nbytes), 256), dtype=torch.uint8, device=device)
         _WS[k] = buf
     return buf
 
@@ -933,42 +923,19 @@ def nms_quads(quads_sorted, thresh):
     return keep, count
 
 
-_ZWS = {}
-
-
-def _workspace_zeroed(key, nbytes, device):
-    """Scratch with a zero-on-entry / zero-on-exit contract (heal_bev_pool_pm): allocated zero-filled ONCE and then owned by
-    the operator, which leaves it clean after every call.  Outgrown buffers are retired, not freed (captured graphs)."""
-    k = (key, device.index, torch.cuda.current_stream(device).cuda_stream)
-    buf = _ZWS.get(k)
-    if buf is None or buf.numel() < nbytes:
-        if buf is not None:
-            _WS_RETIRED.append(buf)
-        buf = torch.zeros(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-        _ZWS[k] = buf
-    return buf
-
-
-_FRUSTUM_OK = {}
-
-
 def _frustum_separable(frustum):
     """True if frustum[d][v][u] == (xs[u], ys[v], ds[d]) -- what create_frustum builds (heter_encoders.py:110-123) and what
     heal_bev_pool_pm assumes.  Checked once per tensor (a host sync; not during graph capture)."""
-    key = (frustum.data_ptr(), frustum._version, tuple(frustum.shape))
-    hit = _FRUSTUM_OK.get(key)
-    if hit is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise _capi.HealAmdError("bev_pool: first use of a frustum tensor inside a graph capture (run one eager step first)")
+    if derived.capturing() and not derived.ready("frustum_separable", (frustum,)):
+        raise _capi.HealAmdError("bev_pool: first use of a frustum tensor inside a graph capture (run one eager step first)")
+
+    def build():
         D, fH, fW, _ = frustum.shape
         sep = torch.stack((frustum[0, 0, :, 0].view(1, 1, fW).expand(D, fH, fW),
                            frustum[0, :, 0, 1].view(1, fH, 1).expand(D, fH, fW),
                            frustum[:, 0, 0, 2].view(D, 1, 1).expand(D, fH, fW)), -1)
-        if len(_FRUSTUM_OK) > 64:
-            _FRUSTUM_OK.clear()
-        hit = (bool(torch.equal(sep, frustum)), frustum)  # keep the tensor alive: the key is its address
-        _FRUSTUM_OK[key] = hit
-    return hit[0]
+        return bool(torch.equal(sep, frustum))
+    return _derived("frustum_separable", (frustum,), build)
 
 
 def bev_pool_pm_supported(D, fH, C):
@@ -1067,7 +1034,7 @@ def bev_pool_pm(head, C, D, fH, fW, frustum, cam_mats, n_agents, n_cams, dx, bx,
     dev = head.device
     nbytes = _capi.query("heal_bev_pool_pm_workspace", n_agents, C, nxi[0], nxi[1], nxi[2])
     # one scratch per problem shape: the two-half invariant holds for ONE carving of the buffer only
-    ws = _workspace_zeroed(("bev_pool_pm", n_agents, C, nxi[0], nxi[1], nxi[2]), nbytes, dev)
+    ws = _workspace(("bev_pool_pm", n_agents, C, nxi[0], nxi[1], nxi[2]), nbytes, dev, zeroed=True)
     nbytes_alg = 4.0 * (BN * HW * (C + D)) + 4.0 * n_agents * C * nxi[0] * nxi[1] * nxi[2]
     with _Timed("bev_pool", nbytes=nbytes_alg, kernel_events=True):
         _capi.call("heal_bev_pool_scatter", _ptr(head), CT, _ptr(frustum), _ptr(cam_mats), n_agents, n_cams, D, fH, fW, C,
@@ -1100,7 +1067,7 @@ def bev_pool_pm_multi(problems):
         nxi = [int(v) for v in q["nx"]]
         nb = _capi.query("heal_bev_pool_pm_workspace", int(q["n_agents"]), C, nxi[0], nxi[1], nxi[2])
         # one scratch per problem SLOT and shape: two problems of equal shape in one launch must not share rows / flags
-        wss.append(_workspace_zeroed(("bev_pool_pm", i, int(q["n_agents"]), C, nxi[0], nxi[1], nxi[2]), nb, dev))
+        wss.append(_workspace(("bev_pool_pm", i, int(q["n_agents"]), C, nxi[0], nxi[1], nxi[2]), nb, dev, zeroed=True))
         keep.append((head, fr, cm, CT, nxi))
         nbytes_alg += 4.0 * (BN * HW * (C + D)) + 4.0 * q["n_agents"] * C * nxi[0] * nxi[1] * nxi[2]
     n = len(problems)
@@ -1203,25 +1170,18 @@ def mean_vfe(voxels, num_points, n_dev=None):
     return out
 
 
-_SP_FRAGS = {}
-
-
 def sp_weight_fragments(weight):
-    """[K,Cin,Cout] -> the fragment order of the pair-compacted kernel (heal_sp_weight_fragments), cached per weight version
-    (a handful of entries: the 12 layers of the encoder).  None when the channel counts have no fragment form."""
+    """[K,Cin,Cout] -> the fragment order of the pair-compacted kernel (heal_sp_weight_fragments).  None when the channel counts
+    have no fragment form."""
     K, cin, cout = (int(v) for v in weight.shape)
     if cin % 4 or (cin >= 16 and cin % 16) or cout % 16 or cin < 4 or int(weight.shape[0]) > 27:
         return None
-    key = (weight.data_ptr(), weight._version, K, cin, cout, str(weight.device))
-    hit = _SP_FRAGS.get(key)
-    if hit is None:
-        if len(_SP_FRAGS) > 256:
-            _WS_RETIRED.extend(v[0] for v in _SP_FRAGS.values())   # retired, not freed: a captured graph may hold the address
-            _SP_FRAGS.clear()
+
+    def build():
         out = torch.empty_like(weight)
         _capi.call("heal_sp_weight_fragments", _ptr(weight), K, cin, cout, _ptr(out), _stream())
-        hit = _SP_FRAGS[key] = (out, weight)  # keeps the source alive: data_ptr stays unique while cached
-    return hit[0]
+        return out
+    return _derived("sp_weight_fragments", (weight,), build)
 
 
 class PairTiles:
@@ -1642,17 +1602,10 @@ def split_attn_weights_from_colsum(colsum, rows_per_part, w_out, b_out, fc1, ln_
 
 
 # ------------------------------------------------------------------------------------------------ K7
-_FRAGG_CACHE = {}
-
-
 def grouped16_fragments(weight, cg):
     """[C, cg, 3, 3] grouped weight (cg = 16 | 8) -> MFMA A fragments of the 16-channel super-groups
-    [C/16][tap][ks][lane] (block-diagonal zero padding for cg = 8), cached per storage + version."""
-    key = (weight.data_ptr(), weight._version, tuple(weight.shape))
-    hit = _FRAGG_CACHE.get(key)
-    if hit is None:
-        if len(_FRAGG_CACHE) > 512:
-            _retire_cache(_FRAGG_CACHE)
+    [C/16][tap][ks][lane] (block-diagonal zero padding for cg = 8)."""
+    def build():
         C = int(weight.shape[0])
         w = weight.detach().reshape(C // 16, 16, cg, 9)                   # [sg, co, ci_in_group, tap]
         if cg == 16:
@@ -1662,28 +1615,16 @@ def grouped16_fragments(weight, cg):
             full[:, :8, :8] = w[:, :8]
             full[:, 8:, 8:] = w[:, 8:]
         # [sg, co(ln), ks, lk, tap] -> [sg, tap, ks, lk, ln]
-        f = full.reshape(C // 16, 16, 4, 4, 9).permute(0, 4, 2, 3, 1).contiguous()
-        hit = (f, weight)
-        _FRAGG_CACHE[key] = hit
-    return hit[0]
-
-
-_FRAGQ_CACHE = {}
+        return full.reshape(C // 16, 16, 4, 4, 9).permute(0, 4, 2, 3, 1).contiguous()
+    return _derived("grouped16_fragments", (weight,), build)
 
 
 def grouped_small_fragments(weight, cg):
     """[C, cg, 3, 3] grouped weight (cg = 4 | 8 | 16) -> weight operands of heal_grouped_small_conv3x3: [C/16][tap][ci][16 output channels
-    of the super-group], cached per storage + version."""
-    key = (weight.data_ptr(), weight._version, tuple(weight.shape))
-    hit = _FRAGQ_CACHE.get(key)
-    if hit is None:
-        if len(_FRAGQ_CACHE) > 512:
-            _retire_cache(_FRAGQ_CACHE)
-        C = int(weight.shape[0])
-        f = weight.detach().reshape(C // 16, 16, cg, 9).permute(0, 3, 2, 1).contiguous()   # [sg, tap, ci, co]
-        hit = (f, weight)
-        _FRAGQ_CACHE[key] = hit
-    return hit[0]
+    of the super-group]."""
+    C = int(weight.shape[0])
+    return _derived("grouped_small_fragments", (weight,),
+                    lambda: weight.detach().reshape(C // 16, 16, cg, 9).permute(0, 3, 2, 1).contiguous())   # [sg, tap, ci, co]
 
 
 def grouped_conv3x3(x, weight, bias, groups, stride=1, relu=True):
@@ -1732,10 +1673,7 @@ def gconv_conv3(x, w2, b2, groups, w3, b3, residual=None, relu=True):
     cg = width // groups
     cout = int(w3.shape[0])
     frag2 = grouped_small_fragments(_need(w2, torch.float32, "w2"), cg)
-    key = (w3.data_ptr(), w3._version, "gc3")
-    frag3 = _FRAG_CACHE.get(key)
-    if frag3 is None:
-        frag3 = _FRAG_CACHE[key] = mfma_a_fragments(w3.detach().reshape(cout, width))
+    frag3 = _derived("gconv_conv3_fragments", (w3,), lambda: mfma_a_fragments(w3.detach().reshape(cout, width)))
     y = torch.empty((n, cout, H, W), dtype=torch.float32, device=x.device)
     flops = 2.0 * n * H * W * (9 * width * cg + width * cout)
     nbytes = 4.0 * n * H * W * (width + cout * (2 if residual is not None else 1))
@@ -1763,27 +1701,17 @@ def mfma_a_fragments(wm):
     return wm.reshape(M // 16, 16, K // 4, 4).permute(0, 2, 3, 1).reshape(M // 16, K // 4, 64).contiguous()
 
 
-_FRAG_CACHE = {}
-
-
 def conv1x1_fragments(w):
-    """Cached MFMA A-fragment layout of a [Cout,Cin,1,1] (or [Cout,Cin]) weight, zero-padded to [ceil64(Cout),
-    ceil32(Cin)], keyed by storage + version."""
-    key = (w.data_ptr(), w._version, tuple(w.shape))
-    hit = _FRAG_CACHE.get(key)
-    if hit is None:
-        if len(_FRAG_CACHE) > 1024:
-            _retire_cache(_FRAG_CACHE)
+    """MFMA A-fragment layout of a [Cout,Cin,1,1] (or [Cout,Cin]) weight, zero-padded to [ceil64(Cout), ceil32(Cin)]."""
+    def build():
         cout, cin = int(w.shape[0]), int(w.shape[1])
         mpad, kpad = (cout + 63) // 64 * 64, (cin + 31) // 32 * 32
         wm = w.detach().reshape(cout, cin)
         if (mpad, kpad) != (cout, cin):
             wm = torch.nn.functional.pad(wm, (0, kpad - cin, 0, mpad - cout))
         fr = mfma_a_fragments(wm)            # [M/16, K/4, 64] -> four k-steps per lane contiguous: [M/16, K/16, 64, 4]
-        fr = fr.reshape(mpad // 16, kpad // 16, 4, 64).permute(0, 1, 3, 2).contiguous()
-        hit = (fr, w)  # keep w alive: the key is its address
-        _FRAG_CACHE[key] = hit
-    return hit[0]
+        return fr.reshape(mpad // 16, kpad // 16, 4, 64).permute(0, 1, 3, 2).contiguous()
+    return _derived("conv1x1_fragments", (w,), build)
 
 
 def conv1x1_supported(cin, cout, hw, stride=1, out_w=None):
@@ -1808,26 +1736,18 @@ def conv1x1_ksplit(n, cin, cout, hw):
     return -(-chunks // -(-chunks // want))       # ceil(chunks / ceil(chunks / want)): no empty split
 
 
-_STEM_CACHE = {}
-
-
 def stem7x7_fragments(w):
-    """[64, cin, 7, 7] -> MFMA A-fragment order [4][ceil(cin * 49 / 4)][64] of heal_stem7x7 (cached per storage + version)."""
-    key = (w.data_ptr(), w._version, tuple(w.shape))
-    hit = _STEM_CACHE.get(key)
-    if hit is None:
-        if len(_STEM_CACHE) > 64:
-            _WS_RETIRED.extend(v[0] for v in _STEM_CACHE.values())
-            _STEM_CACHE.clear()
-        cout, cin = int(w.shape[0]), int(w.shape[1])
-        if cout != 64 or tuple(w.shape[2:]) != (7, 7) or not 1 <= cin <= 4:
-            raise _capi.HealAmdError(f"stem7x7: weight must be [64, 1..4, 7, 7], got {tuple(w.shape)}")
+    """[64, cin, 7, 7] -> MFMA A-fragment order [4][ceil(cin * 49 / 4)][64] of heal_stem7x7."""
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    if cout != 64 or tuple(w.shape[2:]) != (7, 7) or not 1 <= cin <= 4:
+        raise _capi.HealAmdError(f"stem7x7: weight must be [64, 1..4, 7, 7], got {tuple(w.shape)}")
+
+    def build():
         K = cin * 49
         ks = (K + 3) // 4
         wk = torch.nn.functional.pad(w.detach().to(torch.float32).reshape(64, K), (0, 4 * ks - K))      # [64, 4 ks]
-        frag = wk.reshape(4, 16, ks, 4).permute(0, 2, 3, 1).contiguous()                               # [mt][ks][lk][ln]
-        hit = _STEM_CACHE[key] = (frag, w)
-    return hit[0]
+        return wk.reshape(4, 16, ks, 4).permute(0, 2, 3, 1).contiguous()                                # [mt][ks][lk][ln]
+    return _derived("stem7x7_fragments", (w,), build)
 
 
 def stem7x7(x, w, bias, pool=True):
@@ -1864,9 +1784,6 @@ def conv1x1_tiled_ok(n, cin, cout, hw):
     return blocks >= 256 and cin >= 128
 
 
-_FRAGS_CACHE = {}
-
-
 def arith_products():
     """HEAL_ARITH: "" / "f32" (default: exact-fp32 MFMA everywhere) | "bf16x6" | "bf16x9" -- the OPT-IN split-bf16 evaluation of the
     pointwise convolutions (heal_conv1x1_split; fp32 in / out / accumulate, 6 or 9 bf16 partial products per fp32 product)."""
@@ -1877,12 +1794,8 @@ def arith_products():
 def conv1x1_split_fragments(w):
     """[Cout, Cin(,1,1)] fp32 -> the three bf16 planes (w = h + m + l, round to nearest) in the fragment order of heal_conv1x1_split:
     [Cout/128][Cin/32][k16 step 2][row block 4][plane 3][lane 64][8] with element = W_p[128 ct + 32 rb + lane % 32][32 c + 16 s +
-    8 (lane / 32) + e]; cached per storage + version."""
-    key = (w.data_ptr(), w._version, tuple(w.shape))
-    hit = _FRAGS_CACHE.get(key)
-    if hit is None:
-        if len(_FRAGS_CACHE) > 512:
-            _retire_cache(_FRAGS_CACHE)
+    8 (lane / 32) + e]."""
+    def build():
         cout, cin = int(w.shape[0]), int(w.shape[1])
         wm = w.detach().reshape(cout, cin).to(torch.float32)
         h = wm.to(torch.bfloat16)
@@ -1891,10 +1804,8 @@ def conv1x1_split_fragments(w):
         lo = (r1 - m.float()).to(torch.bfloat16)
         planes = torch.stack([h, m, lo], 0)                                    # [3, cout, cin]
         f = planes.reshape(3, cout // 128, 4, 32, cin // 32, 2, 2, 8)          # [p, ct, rb, li, c, s, kb, e]
-        f = f.permute(1, 4, 5, 2, 0, 6, 3, 7).contiguous()                     # [ct, c, s, rb, p, kb, li, e]
-        hit = (f, w)
-        _FRAGS_CACHE[key] = hit
-    return hit[0]
+        return f.permute(1, 4, 5, 2, 0, 6, 3, 7).contiguous()                  # [ct, c, s, rb, p, kb, li, e]
+    return _derived("conv1x1_split_fragments", (w,), build)
 
 
 def _w_rowmajor(w):
@@ -2010,27 +1921,18 @@ def conv1x1_d2s(x, w, bias, act, k, dst, channel_offset):
     return dst[:, channel_offset:channel_offset + cout // (k * k)]
 
 
-_FRAG3_CACHE = {}
-
-
 def conv3x3_fragments(w):
-    """Cached MFMA A-fragment layout of a [Cout,Cin,3,3] weight for heal_conv3x3: zero-padded to [ceil64(Cout), ceil8(Cin)],
-    ordered [Cout/64][Cin/8][tap][k-step][m-tile][lane] (see include/heal_amd.h); keyed by storage + version."""
-    key = (w.data_ptr(), w._version, tuple(w.shape))
-    hit = _FRAG3_CACHE.get(key)
-    if hit is None:
-        if len(_FRAG3_CACHE) > 512:
-            _retire_cache(_FRAG3_CACHE)
+    """MFMA A-fragment layout of a [Cout,Cin,3,3] weight for heal_conv3x3: zero-padded to [ceil64(Cout), ceil8(Cin)],
+    ordered [Cout/64][Cin/8][tap][k-step][m-tile][lane] (see include/heal_amd.h)."""
+    def build():
         cout, cin = int(w.shape[0]), int(w.shape[1])
         mpad, kpad = (cout + 63) // 64 * 64, (cin + 7) // 8 * 8
         wm = w.detach().reshape(cout, cin, 9)
         if (mpad, kpad) != (cout, cin):
             wm = torch.nn.functional.pad(wm, (0, 0, 0, kpad - cin, 0, mpad - cout))
         # [mb, mt, ln, chunk, ks, lk, tap] -> [mb, chunk, tap, ks, mt, lk, ln]
-        f = wm.reshape(mpad // 64, 4, 16, kpad // 8, 2, 4, 9).permute(0, 3, 6, 4, 1, 5, 2).contiguous()
-        hit = (f, w)  # keep w alive: the key is its address
-        _FRAG3_CACHE[key] = hit
-    return hit[0]
+        return wm.reshape(mpad // 64, 4, 16, kpad // 8, 2, 4, 9).permute(0, 3, 6, 4, 1, 5, 2).contiguous()
+    return _derived("conv3x3_fragments", (w,), build)
 
 
 def conv3x3_same(x, w, bias, stride, pad, act="none"):
@@ -2050,9 +1952,6 @@ def conv3x3_same(x, w, bias, stride, pad, act="none"):
         _capi.call("heal_conv3x3_same", _ptr(x), _ptr(frag), _ptr(_need(bias, torch.float32, "bias")) if bias is not None else None,
                    n, cin, cout, H, W, int(stride), pt, pl, Ho, Wo, {"none": 0, "relu": 1, "silu": 2}[act], _ptr(y), _stream())
     return y
-
-
-_FRAGW_CACHE = {}
 
 
 def conv3x3_winograd_waves(n=1, cout=64, H=256, W=256):
@@ -2087,14 +1986,9 @@ _WG_KC_DEFAULT = "8"
 
 
 def conv3x3_winograd_fragments(w, waves=8, kc=8):
-    """Cached Winograd-domain weights U = G g G^T of a [Cout,Cin,3,3] filter bank in the lane-major fragment order
-    heal_conv3x3_winograd[_kc] reads for `waves` waves per block and `kc` channels per chunk (include/heal_amd.h); keyed by storage +
-    version."""
-    key = (w.data_ptr(), w._version, tuple(w.shape), waves, kc)
-    hit = _FRAGW_CACHE.get(key)
-    if hit is None:
-        if len(_FRAGW_CACHE) > 512:
-            _retire_cache(_FRAGW_CACHE)
+    """Winograd-domain weights U = G g G^T of a [Cout,Cin,3,3] filter bank in the lane-major fragment order
+    heal_conv3x3_winograd[_kc] reads for `waves` waves per block and `kc` channels per chunk (include/heal_amd.h)."""
+    def build():
         cout, cin = int(w.shape[0]), int(w.shape[1])
         mpad, kpad = (cout + 63) // 64 * 64, (cin + kc - 1) // kc * kc
         G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], dtype=torch.float64,
@@ -2103,21 +1997,15 @@ def conv3x3_winograd_fragments(w, waves=8, kc=8):
         if (mpad, kpad) != (cout, cin):
             U = torch.nn.functional.pad(U, (0, 0, 0, kpad - cin, 0, mpad - cout))
         # [mb, mt, ln, chunk, ks, lk, w, xi_i] -> [mb, chunk, w, lk, ln, xi_i, ks, mt]
-        f = U.reshape(mpad // 64, 4, 16, kpad // kc, kc // 4, 4, waves, 16 // waves).permute(0, 3, 6, 5, 2, 7, 4, 1).contiguous()
-        hit = (f, w)
-        _FRAGW_CACHE[key] = hit
-    return hit[0]
+        return U.reshape(mpad // 64, 4, 16, kpad // kc, kc // 4, 4, waves, 16 // waves).permute(0, 3, 6, 5, 2, 7, 4, 1).contiguous()
+    return _derived("conv3x3_winograd_fragments", (w,), build, (waves, kc))
 
 
 def conv3x3_winograd4_fragments(w):
-    """Cached F(4x4,3x3) Winograd-domain weights U = G g G^T (6 x 6 per filter, formed in float64) of a [Cout,Cin,3,3] filter bank
+    """F(4x4,3x3) Winograd-domain weights U = G g G^T (6 x 6 per filter, formed in float64) of a [Cout,Cin,3,3] filter bank
     in the lane-major order heal_conv3x3_winograd4 reads: [Cout/32][Cin/16][wave 8][lane 64][xi_i 9][ks 4], value
     U[xi = 9 (wave & 3) + xi_i][co = 32 mb + 16 (wave >> 2) + (lane & 15)][ci = 16 chunk + 4 ks + (lane >> 4)], zero-padded."""
-    key = (w.data_ptr(), w._version, tuple(w.shape), "f4")
-    hit = _FRAGW_CACHE.get(key)
-    if hit is None:
-        if len(_FRAGW_CACHE) > 512:
-            _retire_cache(_FRAGW_CACHE)
+    def build():
         cout, cin = int(w.shape[0]), int(w.shape[1])
         mpad, kpad = (cout + 31) // 32 * 32, (cin + 15) // 16 * 16
         G = torch.tensor([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6],
@@ -2126,10 +2014,8 @@ def conv3x3_winograd4_fragments(w):
         if (mpad, kpad) != (cout, cin):
             U = torch.nn.functional.pad(U, (0, 0, 0, kpad - cin, 0, mpad - cout))
         # [mb, mt, ln, chunk, ks, lk, g, xi_i] -> [mb, chunk, mt, g, lk, ln, xi_i, ks]   (wave = 4 mt + g, lane = 16 lk + ln)
-        f = U.reshape(mpad // 32, 2, 16, kpad // 16, 4, 4, 4, 9).permute(0, 3, 1, 6, 5, 2, 7, 4).contiguous()
-        hit = (f, w)
-        _FRAGW_CACHE[key] = hit
-    return hit[0]
+        return U.reshape(mpad // 32, 2, 16, kpad // 16, 4, 4, 4, 9).permute(0, 3, 1, 6, 5, 2, 7, 4).contiguous()
+    return _derived("conv3x3_winograd4_fragments", (w,), build)
 
 
 def conv3x3_winograd4_ok(n, cout, H, W):
@@ -2154,9 +2040,6 @@ def conv3x3_algo(stride, n=1, cout=64, H=256, W=256):
     return "winograd" if blocks >= 96 else "direct"
 
 
-_TAPMAJOR_CACHE = {}
-
-
 def conv_gemm_supported(cin, cout, Wo):
     import os
     return cout % 128 == 0 and cin % 32 == 0 and Wo % 4 == 0 and os.environ.get("HEAL_CONV_GEMM", "1") == "1"
@@ -2169,24 +2052,15 @@ def conv_gemm(x, w, bias=None, residual=None, relu=False, stride=1):
     n, cin, H, W = (int(v) for v in x.shape)
     cout, ks = int(w.shape[0]), int(w.shape[2])
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    key = (w.data_ptr(), w._version, tuple(w.shape))
-    hit = _TAPMAJOR_CACHE.get(key)
-    if hit is None:
-        if len(_TAPMAJOR_CACHE) > 256:
-            _WS_RETIRED.extend(v[0] for v in _TAPMAJOR_CACHE.values())   # retired, not freed (captured graphs)
-            _TAPMAJOR_CACHE.clear()
-        hit = _TAPMAJOR_CACHE[key] = (w.detach().permute(0, 2, 3, 1).reshape(cout, ks * ks, cin).contiguous(), w)
+    wt = _derived("conv_gemm_tapmajor", (w,), lambda: w.detach().permute(0, 2, 3, 1).reshape(cout, ks * ks, cin).contiguous())
     y = torch.empty((n, cout, Ho, Wo), dtype=torch.float32, device=x.device)
     if residual is not None:
         residual = _need(residual, torch.float32, "residual")
     name = (f"conv3x3_{cin}_{cout}" if ks == 3 else f"conv{ks}x{ks}_{cin}_{cout}") + ("_s2" if stride == 2 else "")
     with _Timed(name, 2.0 * ks * ks * n * cin * cout * Ho * Wo, 4.0 * n * (cin * H * W + cout * Ho * Wo), kernel_events=True):
-        _capi.call("heal_conv_gemm", _ptr(x), _ptr(hit[0]), _optr(bias), _optr(residual), n, cin, cout, H, W, ks, int(stride),
+        _capi.call("heal_conv_gemm", _ptr(x), _ptr(wt), _optr(bias), _optr(residual), n, cin, cout, H, W, ks, int(stride),
                    int(bool(relu)), _ptr(y), _stream())
     return y
-
-
-_PAD128_CACHE = {}
 
 
 def conv7x7_s2_supported(cin, cout, W):
@@ -2198,19 +2072,16 @@ def conv7x7_s2(x, w, bias=None, relu=False):
     stem of the old-style Lift-Splat model (lss_submodule.py:242).  The kernel wants 128-channel output tiles: the weight (and bias) are
     padded with zero rows once (cached), the first Cout channels of the result are returned."""
     cout = int(w.shape[0])
-    key = (w.data_ptr(), w._version, None if bias is None else (bias.data_ptr(), bias._version))
-    hit = _PAD128_CACHE.get(key)
-    if hit is None:
-        if len(_PAD128_CACHE) > 32:
-            _retire_cache(_PAD128_CACHE)
+    def build():
         wp = torch.zeros((128,) + tuple(w.shape[1:]), dtype=torch.float32, device=w.device)
         wp[:cout] = w.detach()
         bp = None
         if bias is not None:
             bp = torch.zeros((128,), dtype=torch.float32, device=w.device)
             bp[:cout] = bias.detach()
-        hit = _PAD128_CACHE[key] = (wp, bp, w)
-    y = conv_gemm(x, hit[0], hit[1], None, relu, 2)
+        return wp, bp
+    wp, bp = _derived("conv7x7_s2_pad128", (w, bias), build)
+    y = conv_gemm(x, wp, bp, None, relu, 2)
     return y[:, :cout].contiguous() if cout < 128 else y
 
 
@@ -2310,9 +2181,6 @@ def layernorm_nchw(x, gamma, beta, eps):
     return y
 
 
-_SE_T_CACHE = {}
-
-
 def se_gate(mean, w_reduce, b_reduce, w_expand, b_expand, scale=1.0, tiles=1):
     """Squeeze-excite gate: mean [n,C] (any trailing 1-dims), w_reduce [S,C,1,1], w_expand [C,S,1,1] -> gate [n,C].
     tiles = T, scale = 1/(H*W): `mean` holds the per-tile sums [n,C,T] of depthwise_conv(channel_sums=True)."""
@@ -2320,16 +2188,10 @@ def se_gate(mean, w_reduce, b_reduce, w_expand, b_expand, scale=1.0, tiles=1):
     S = int(w_reduce.shape[0])
     mean = _need(mean.reshape(n, C, int(tiles)), torch.float32, "mean")
     w_expand = _need(w_expand, torch.float32, "w_expand")
-    key = (w_expand.data_ptr(), w_expand._version)
-    hit = _SE_T_CACHE.get(key)
-    if hit is None:
-        if len(_SE_T_CACHE) > 256:
-            _SE_T_CACHE.clear()
-        hit = (w_expand.detach().reshape(C, S).t().contiguous(), w_expand)  # [S,C]; keep the source alive (key = address)
-        _SE_T_CACHE[key] = hit
+    w_t = _derived("se_gate_expand_t", (w_expand,), lambda: w_expand.detach().reshape(C, S).t().contiguous())   # [S,C]
     gate = torch.empty((n, C), dtype=torch.float32, device=mean.device)
     _capi.call("heal_se_gate", _ptr(mean), _ptr(_need(w_reduce, torch.float32, "w_reduce")),
-               _ptr(_need(b_reduce, torch.float32, "b_reduce")), _ptr(hit[0]),
+               _ptr(_need(b_reduce, torch.float32, "b_reduce")), _ptr(w_t),
                _ptr(_need(b_expand, torch.float32, "b_expand")), n, C, S, float(scale), int(tiles), _ptr(gate),
                _stream())
     return gate

@@ -22,7 +22,7 @@ reps = 20
 for i in range(reps + 5):
     ops.bev_pool_pm(*args)
     torch.cuda.synchronize()
-    ws = ops._ZWS[(("bev_pool_pm", 1, C, int(nx[0]), int(nx[1]), int(nx[2])), 0, torch.cuda.current_stream().cuda_stream)]
+    ws = ops._WS[(("bev_pool_pm", 1, C, int(nx[0]), int(nx[1]), int(nx[2])), 0, torch.cuda.current_stream().cuda_stream)]
     st = ws.view(torch.int32)[16:48].cpu().numpy().reshape(2, 16)[:, :8]
     if i >= 5:
         acc += st

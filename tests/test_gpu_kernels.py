@@ -1035,7 +1035,7 @@ def _pm_ws_views(ws, n_cells, C):
     return words, flags, rows
 
 
-def test_bev_pool_pm_scratch_is_self_cleaning_and_repeatable():
+def test_bev_pool_pm_zeroed_workspace_is_self_cleaning_and_repeatable():
     """heal_bev_pool_pm never memsets: calls alternate between the two (rows, flags) halves of the workspace, cells are tagged
     by generation, and every scatter zeroes -- as tail work of its own launch -- the rows its predecessor tagged in the other
     half.  Calls on different inputs interleaved (dense scene, empty scene: every point out of range, dense again) must each
@@ -1061,7 +1061,7 @@ def test_bev_pool_pm_scratch_is_self_cleaning_and_repeatable():
         _pool_close(out.cpu().numpy(), ref, max_bad_cells=0, name=f"bev_pool_pm_repeat_{trial}")
         if shift == 1e6:
             assert float(out.abs().max()) == 0.0
-        ws = ops._ZWS[(("bev_pool_pm", 1, C, int(nx[0]), int(nx[1]), int(nx[2])), 0, torch.cuda.current_stream().cuda_stream)]
+        ws = ops._WS[(("bev_pool_pm", 1, C, int(nx[0]), int(nx[1]), int(nx[2])), 0, torch.cuda.current_stream().cuda_stream)]
         words, flags, rows = _pm_ws_views(ws, n_cells, C)
         gen = int(words[0].item())
         gen0 = gen - trial if gen0 is None else gen0

@@ -636,13 +636,14 @@ def test_exact_rational_iou_known_answers():
     assert E.exact_quad_iou(np.zeros((4, 2), np.float32), np.zeros((4, 2), np.float32)) is None
 
 
-def test_camera_crop_walk_is_exact_on_the_torch_path():
+def test_camera_crop_walk_with_derived_zero_response_is_exact_on_the_torch_path():
     """Round 6 (fuse_modules/pyramid_fuse.py): camera agents' zero-padded maps go through the pyramid stages on the crop their content can
     influence, the rest of every stage output is the stack's response to an all-zero map.  The claim is about LOCALITY, not about
     kernels, so it is checked here on the CPU with the modules' torch path (parameters require grad -> conv / BatchNorm as torch operators):
     random weights and BatchNorm statistics, two LiDAR-like agents with dense maps + two camera agents that are zero outside a box,
     both agent orders; every level must equal the plain walk EVERYWHERE (inside and outside the pasted box) to fp32 rounding.  Also the
     interval arithmetic the crop is planned with."""
+    from heal_amd import derived
     from heal_amd.opencood.models.fuse_modules.pyramid_fuse import PyramidFusion, _stage_influence, _stage_needs
     cfg = {"layer_nums": [3, 5, 8], "num_filters": [16, 32, 64], "layer_strides": [1, 2, 2], "upsample_strides": [1, 2, 4],
            "num_upsample_filter": [32, 32, 32], "resnext": True, "inplanes": 16}
@@ -661,8 +662,12 @@ def test_camera_crop_walk_is_exact_on_the_torch_path():
         x[cam[0]:cam[1]] *= keep
         with torch.enable_grad():                       # (the torch path; no autograd graph is needed afterwards)
             # the cached zero-input response, computed here on the torch path (the model computes it under no_grad on the device)
-            pf._bg = [f.detach() for f in pf.resnet(torch.zeros(1, 16, H, W))]
-            pf._bg_key = pf._zero_response_key(x)
+            tag, sources, extra = pf._zero_response_slot(x)
+
+            def torch_path_zero_response():
+                with torch.enable_grad():
+                    return [f.detach() for f in pf.resnet(torch.zeros(1, 16, H, W))]
+            derived.derived(tag, sources, torch_path_zero_response, extra)
             plain = [f.detach() for f in pf.get_multiscale_feature(x)]
             plan = pf._camcrop_plan(x, cam, box)
             crop = [f.detach() for f in pf.get_multiscale_feature_camcrop(x, cam, box)]
