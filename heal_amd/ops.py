@@ -136,6 +136,17 @@ def _need(t, dtype, name):
     return t.contiguous()
 
 
+def _need_bias(bias, cout, who):
+    """An optional per-output-channel bias: None, or a f32 cuda tensor of exactly `cout` elements (made contiguous: the kernels
+    read bias[co] from a bare pointer, so a strided view or a longer buffer would be misread without an error)."""
+    if bias is None:
+        return None
+    bias = _need(bias, torch.float32, "bias")
+    if bias.numel() != cout:
+        raise _capi.HealAmdError(f"{who}: bias has {bias.numel()} elements for {cout} output channels")
+    return bias
+
+
 def _workspace(key, nbytes, device, zeroed=False):
     """Grow-only per-(op, device) scratch buffer (256-B aligned by the caching allocator).  A buffer that is outgrown is
     RETIRED (derived.retire), not freed: a captured HIP graph may have its address baked in, and handing the memory back to the
@@ -1637,6 +1648,7 @@ def grouped_conv3x3(x, weight, bias, groups, stride=1, relu=True):
     x = _need(x, torch.float32, "x")
     weight = _need(weight, torch.float32, "weight")
     n, C, H, W = (int(v) for v in x.shape)
+    bias = _need_bias(bias, C, "grouped_conv3x3")
     Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
     y = torch.empty((n, C, Ho, Wo), dtype=torch.float32, device=x.device)
     cg = C // groups
@@ -1764,7 +1776,7 @@ def stem7x7(x, w, bias, pool=True):
     y = torch.empty((n, 64, Ho, Wo), dtype=torch.float32, device=x.device)
     with _Timed(f"stem7x7_{cin}" + ("_pool" if pool else ""), 2.0 * n * 64 * cin * 49 * Hc * Wc, kernel_events=True):
         _capi.call("heal_stem7x7", _ptr(x), cx * H * W, n, cin, H, W, _ptr(frag),
-                   _ptr(_need(bias, torch.float32, "bias")) if bias is not None else None, int(bool(pool)), _ptr(y), _stream())
+                   _ptr(_need_bias(bias, 64, "stem7x7")), int(bool(pool)), _ptr(y), _stream())
     return y
 
 
@@ -1830,6 +1842,7 @@ def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixe
     x = _need(x, torch.float32, "x")
     n, cin, H, W = (int(v) for v in x.shape)
     cout = int(w.shape[0])
+    bias = _need_bias(bias, cout, "conv1x1")
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     hard_ok = stride in (1, 2) and ((Ho * Wo) % 4 == 0 if stride == 1 else Wo % 4 == 0)
     if int(w.shape[1]) != cin or not hard_ok:
@@ -1868,8 +1881,6 @@ def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixe
         if residual is not None or cout % 4 != 0:
             raise _capi.HealAmdError("conv1x1: pixel-major output needs Cout % 4 == 0 and takes no residual")
         y = torch.empty((n, Ho * Wo, cout), dtype=torch.float32, device=x.device)
-        if bias is not None:
-            bias = _need(bias, torch.float32, "bias")
     else:
         y = _out_or_empty(out, (n, cout, Ho, Wo), x.device, "conv1x1")
     if residual is not None:
@@ -1907,7 +1918,7 @@ def conv1x1_d2s(x, w, bias, act, k, dst, channel_offset):
     if (not dst.is_contiguous() or int(dst.shape[0]) != n or int(dst.shape[2]) != H * k or int(dst.shape[3]) != W * k
             or cout % (k * k) or W % 4):
         raise _capi.HealAmdError(f"conv1x1_d2s: destination {tuple(dst.shape)} does not fit x {tuple(x.shape)} at k={k}")
-    bias = _need(bias, torch.float32, "bias") if bias is not None else None
+    bias = _need_bias(bias, cout, "conv1x1_d2s")
     if conv1x1_tiled_ok(n, cin, cout, H * W) and w.dtype == torch.float32:
         wr = _w_rowmajor(w)
         with _Timed(f"conv1x1_{cin}_{cout}", 2.0 * n * cin * cout * H * W, 4.0 * n * H * W * (cin + cout)):
@@ -1949,7 +1960,7 @@ def conv3x3_same(x, w, bias, stride, pad, act="none"):
     y = torch.empty((n, cout, Ho, Wo), dtype=torch.float32, device=x.device)
     with _Timed(f"conv3x3_{cin}_{cout}_s{stride}same", 2.0 * 9 * n * cin * cout * Ho * Wo, 4.0 * n * (cin * H * W + cout * Ho * Wo),
                 kernel_events=True):
-        _capi.call("heal_conv3x3_same", _ptr(x), _ptr(frag), _ptr(_need(bias, torch.float32, "bias")) if bias is not None else None,
+        _capi.call("heal_conv3x3_same", _ptr(x), _ptr(frag), _ptr(_need_bias(bias, cout, "conv3x3_same")),
                    n, cin, cout, H, W, int(stride), pt, pl, Ho, Wo, {"none": 0, "relu": 1, "silu": 2}[act], _ptr(y), _stream())
     return y
 
@@ -2054,8 +2065,11 @@ def conv_gemm(x, w, bias=None, residual=None, relu=False, stride=1):
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     wt = _derived("conv_gemm_tapmajor", (w,), lambda: w.detach().permute(0, 2, 3, 1).reshape(cout, ks * ks, cin).contiguous())
     y = torch.empty((n, cout, Ho, Wo), dtype=torch.float32, device=x.device)
+    bias = _need_bias(bias, cout, "conv_gemm")
     if residual is not None:
         residual = _need(residual, torch.float32, "residual")
+        if tuple(residual.shape) != tuple(y.shape):
+            raise _capi.HealAmdError("conv_gemm: residual shape mismatch")
     name = (f"conv3x3_{cin}_{cout}" if ks == 3 else f"conv{ks}x{ks}_{cin}_{cout}") + ("_s2" if stride == 2 else "")
     with _Timed(name, 2.0 * ks * ks * n * cin * cout * Ho * Wo, 4.0 * n * (cin * H * W + cout * Ho * Wo), kernel_events=True):
         _capi.call("heal_conv_gemm", _ptr(x), _ptr(wt), _optr(bias), _optr(residual), n, cin, cout, H, W, ks, int(stride),
@@ -2072,6 +2086,8 @@ def conv7x7_s2(x, w, bias=None, relu=False):
     stem of the old-style Lift-Splat model (lss_submodule.py:242).  The kernel wants 128-channel output tiles: the weight (and bias) are
     padded with zero rows once (cached), the first Cout channels of the result are returned."""
     cout = int(w.shape[0])
+    bias = _need_bias(bias, cout, "conv7x7_s2")
+
     def build():
         wp = torch.zeros((128,) + tuple(w.shape[1:]), dtype=torch.float32, device=w.device)
         wp[:cout] = w.detach()
@@ -2115,8 +2131,7 @@ def conv3x3(x, w, bias=None, residual=None, relu=False, stride=1):
         residual = _need(residual, torch.float32, "residual")
         if tuple(residual.shape) != tuple(y.shape):
             raise _capi.HealAmdError("conv3x3: residual shape mismatch")
-    if bias is not None:
-        bias = _need(bias, torch.float32, "bias")
+    bias = _need_bias(bias, cout, "conv3x3")
     if stride == 1 and conv3x3_winograd4_ok(n, cout, H, W):
         frag = conv3x3_winograd4_fragments(w)
         with _Timed(f"conv3x3w_{cin}_{cout}", 2.0 * 9 * n * cin * cout * Ho * Wo, 4.0 * n * (cin * H * W + cout * Ho * Wo)):
@@ -2228,6 +2243,7 @@ def depthwise_conv(x, weight, bias, stride, pad, act="none", channel_sums=None):
     x = _need(x, torch.float32, "x")
     weight = _need(weight, torch.float32, "weight")
     n, C, H, W = (int(v) for v in x.shape)
+    bias = _need_bias(bias, C, "depthwise_conv")
     k = int(weight.shape[-1])
     pl, pr, pt, pb = (int(v) for v in pad)
     Ho = (H + pt + pb - k) // stride + 1
