@@ -164,6 +164,10 @@ _SIGNATURES = {
                                                 c_void_p]),
     "heal_agent_window_attention": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [c_float, c_void_p, c_void_p]),
     "heal_agent_mean": (c_int, [c_void_p, c_int, ctypes.c_longlong, c_void_p, c_void_p]),
+    "heal_v2v_message_workspace": (c_size_t, [c_int] * 5),
+    "heal_v2v_message": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p] + [c_int] * 9
+                         + [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "heal_gru_zero_state": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong] + [c_int] * 4 + [c_void_p, c_void_p]),
     "heal_label_assign_workspace": (c_size_t, [c_int]),
     "heal_label_assign": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                   c_size_t, c_void_p]),

@@ -197,7 +197,7 @@ def _baseline_modality(base, strides, inplanes=None):
 
 def lidar_baseline(fusion_method="v2xvit", lidar_range=FULL_RANGE, max_cav=5, modality="m1"):
     """HeterModelBaseline (LiDAROnly/lidar_v2xvit.yaml; BASELINE config 5 with modality='m3'):
-    encoder -> plain BEV backbone -> shrinker -> single-scale fusion (v2xvit | att | max | cobevt) -> heads."""
+    encoder -> plain BEV backbone -> shrinker -> single-scale fusion (v2xvit | att | max | cobevt | v2vnet) -> heads."""
     h = _common(lidar_range, max_cav)
     h["name"] = f"heal_amd_opv2v_{modality}_{fusion_method}"
     if modality == "m1":
@@ -215,6 +215,11 @@ def lidar_baseline(fusion_method="v2xvit", lidar_range=FULL_RANGE, max_cav=5, mo
     elif fusion_method == "cobevt":     # LiDAROnly/lidar_cobevt.yaml
         args["cobevt"] = {"input_dim": 256, "mlp_dim": 256, "agent_size": max_cav, "window_size": 4, "dim_head": 32,
                           "drop_out": 0.1, "depth": 3}
+    elif fusion_method == "v2vnet":     # LiDAROnly/lidar_v2vnet.yaml; conv_gru.H / W: the fusion map (128 x 128 on the full range)
+        H = int(round((lidar_range[4] - lidar_range[1]) / (0.4 * 4)))
+        W = int(round((lidar_range[3] - lidar_range[0]) / (0.4 * 4)))
+        args["v2vnet"] = {"num_iteration": 2, "in_channels": 256, "gru_flag": True, "agg_operator": "avg",
+                          "conv_gru": {"H": H, "W": W, "num_layers": 1, "kernel_size": [[3, 3]]}}
     h["model"] = {"core_method": "heter_model_baseline", "args": args}
     # encoder + backbone + stride-2 shrinker leave the map at 1/4 of the 0.4 m anchor grid (lidar_v2xvit.yaml: feature_stride 4)
     h["postprocess"]["anchor_args"]["feature_stride"] = 4

@@ -1,7 +1,7 @@
 """Single-scale fusion operators used by HeterModelBaseline (reference: opencood/models/fuse_modules/
-fusion_in_one.py): MaxFusion (:87-124), AttFusion (:126-151, :14-45), V2XViTFusion (:320-372), CoBEVT (:374-430).
-Warping to the ego frame is K5's heal_warp_agent; the per-pixel attention is K6; CoBEVT's agent-window attention is
-heal_agent_window_attention (swap_fusion_modules.py)."""
+fusion_in_one.py): MaxFusion (:87-124), AttFusion (:126-151, :14-45), V2VNetFusion (:203-318), V2XViTFusion (:320-372),
+CoBEVT (:374-430).  Warping to the ego frame is K5's heal_warp_agent; the per-pixel attention is K6; CoBEVT's agent-window
+attention is heal_agent_window_attention (swap_fusion_modules.py); V2VNet's masked message aggregation is heal_v2v_message."""
 import os
 
 import numpy as np
@@ -194,8 +194,191 @@ class CoBEVT(_WarpThenFuse):
         return torch.stack(out)
 
 
+def _warp_affine_simple(src, M, dsize):
+    """torch_transformation_utils.py:323-332: affine_grid (in M's dtype, then cast) + bilinear grid_sample, zero padding."""
+    import torch.nn.functional as F
+    grid = F.affine_grid(M, [src.shape[0], src.shape[1], dsize[0], dsize[1]], align_corners=False).to(src)
+    return F.grid_sample(src, grid, align_corners=False)
+
+
+class V2VNetFusion(nn.Module):
+    """fusion_in_one.py:203-318 (with sub_modules/convgru.py).  num_iteration Jacobi rounds of message passing: every node i
+    warps every node j into its frame, msg_ij = msg_cnn(cat(nbr_ij, x_i)) * roi_mask_ij, agg_i = mean_j | max_j msg_ij, then
+    x_i' = ConvGRU(cat(x_i, agg_i)) (zero hidden state, one step) or x_i + agg_i; the output is mlp(node 0) per scene.
+
+    On the CPU, under autograd and for shapes the kernels do not take, the reference's torch arithmetic runs.  Inference on
+    the device uses these identities:
+      1. only node 0 of the last round reaches the output: the last round computes ego 0 only;
+      2. msg_cnn(cat(nbr, x_i)) = W_n * nbr + (W_e * x_i + b): the ego term E_i once per ego, and
+         mean: agg_i = (sum_j m_ij (W_n * nbr_ij) + (sum_j m_ij) E_i) / N;  max: agg_i = max_j m_ij (W_n * nbr_ij + E_i);
+      3. with h = 0, reset * h = 0 and every hidden-channel slice multiplies zeros: h' = sigmoid(beta) * tanh(can), from the beta
+         half of conv_gates and the input half of conv_can;
+      4. the x_i parts of msg_cnn, beta and can are one stacked 3x3 convolution C -> 3C; the agg_i parts one C -> 2C.
+    The one divergence: where a gate is NaN or Inf, the reference's (1 - u) * h = (1 - u) * 0 propagates a NaN that (3) does
+    not form (and the reset gate, which the reference computes but multiplies by zero, is never evaluated).
+    HEAL_V2VNET_FUSED=0 runs the torch arithmetic on the device too (the A/B switch of scripts/v2vnet_bench.py)."""
+
+    def __init__(self, args):
+        super().__init__()
+        from heal_amd.opencood.models.sub_modules.convgru import ConvGRU
+        in_channels = args["in_channels"]
+        H, W = args["conv_gru"]["H"], args["conv_gru"]["W"]
+        kernel_size = args["conv_gru"]["kernel_size"]
+        num_gru_layers = args["conv_gru"]["num_layers"]
+        self.num_iteration = args["num_iteration"]
+        self.gru_flag = args["gru_flag"]
+        self.agg_operator = args["agg_operator"]
+        self.msg_cnn = nn.Conv2d(in_channels * 2, in_channels, kernel_size=3, stride=1, padding=1)
+        self.conv_gru = ConvGRU(input_size=(H, W), input_dim=in_channels * 2, hidden_dim=[in_channels] * num_gru_layers,
+                                kernel_size=kernel_size, num_layers=num_gru_layers, batch_first=True, bias=True,
+                                return_all_layers=False)
+        self.mlp = nn.Linear(in_channels, in_channels)
+
+    def _check(self, H, W):
+        if self.agg_operator not in ("avg", "max"):
+            raise ValueError("agg_operator has wrong value")
+        if self.gru_flag and (H, W) != (self.conv_gru.height, self.conv_gru.width):
+            raise ValueError(f"V2VNetFusion: the fusion map is {H}x{W} but conv_gru was built for {self.conv_gru.height}x"
+                             f"{self.conv_gru.width} (conv_gru.H / W in the YAML must equal the map size)")
+
+    # ---- the reference's arithmetic ----------------------------------------------------------------------------------------
+    def forward_torch(self, x, record_len, affine_matrix):
+        """fusion_in_one.py:238-318 as written (the CPU, gradient and unsupported-shape path)."""
+        _, C, H, W = x.shape
+        lens = record_len_to_list(record_len)
+        aff = affine_matrix if isinstance(affine_matrix, torch.Tensor) else torch.from_numpy(np.asarray(affine_matrix))
+        aff = aff.to(x.device)
+        B, L = aff.shape[:2]
+        split_x = regroup(x, lens)
+        roi_mask = torch.zeros((B, L, L, 1, H, W)).to(x)
+        for b in range(B):
+            for i in range(lens[b]):
+                roi_mask[b, i] = _warp_affine_simple(torch.ones((L, 1, H, W)).to(x), aff[b][i], (H, W))
+        batch_node_features = split_x
+        for _ in range(self.num_iteration):
+            batch_updated = []
+            for b in range(B):
+                N = lens[b]
+                t_matrix = aff[b][:N, :N, :, :]
+                updated = []
+                for i in range(N):
+                    mask = roi_mask[b, i, :N, ...]
+                    neighbor = _warp_affine_simple(batch_node_features[b], t_matrix[i], (H, W))
+                    ego = batch_node_features[b][i].unsqueeze(0).repeat(N, 1, 1, 1)
+                    message = self.msg_cnn(torch.cat([neighbor, ego], dim=1)) * mask
+                    agg = torch.mean(message, dim=0) if self.agg_operator == "avg" else torch.max(message, dim=0)[0]
+                    if self.gru_flag:
+                        cat_feature = torch.cat([batch_node_features[b][i, ...], agg], dim=0)
+                        gru_out = self.conv_gru(cat_feature.unsqueeze(0).unsqueeze(0))[0][0].squeeze(0).squeeze(0)
+                    else:
+                        gru_out = batch_node_features[b][i, ...] + agg
+                    updated.append(gru_out.unsqueeze(0))
+                batch_updated.append(torch.cat(updated, dim=0))
+            batch_node_features = batch_updated
+        out = torch.cat([itm[0, ...].unsqueeze(0) for itm in batch_node_features], dim=0)
+        return self.mlp(out.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
+
+    # ---- inference on the device -------------------------------------------------------------------------------------------
+    def fused_ok(self, x, lens):
+        C, H, W = (int(v) for v in x.shape[1:])
+        ks_ok = all(tuple(k) == (3, 3) for k in (c.conv_gates.kernel_size for c in self.conv_gru.cell_list))
+        mlp_ok = (H * W) % 4 == 0 or ops.linear_supported(H * W, C, C)
+        return (x.is_cuda and x.dtype == torch.float32 and not (torch.is_grad_enabled() and x.requires_grad) and ks_ok and mlp_ok
+                and max(lens) <= 8 and os.environ.get("HEAL_V2VNET_FUSED", "1") != "0")
+
+    def _weights(self):
+        """(W_n, stacked x_i weight, stacked bias, agg weight | None, [(layer weight, layer bias)] for GRU layers >= 1), from the
+        parameters by slicing (derived store: rebuilt when a parameter changes)."""
+        from heal_amd.derived import derived
+        C = self.mlp.in_features
+        cells = list(self.conv_gru.cell_list) if self.gru_flag else []
+        srcs = (self.msg_cnn.weight, self.msg_cnn.bias) + tuple(t for c in cells[:1] for t in (c.conv_gates.weight, c.conv_gates.bias,
+                                                                                               c.conv_can.weight, c.conv_can.bias))
+
+        def build():
+            wm, bm = self.msg_cnn.weight, self.msg_cnn.bias
+            w_n = wm[:, :C].contiguous()
+            if not cells:
+                return w_n, wm[:, C:].contiguous(), bm.contiguous(), None
+            g, c0 = cells[0].conv_gates, cells[0].conv_can
+            w_x = torch.cat([wm[:, C:], g.weight[C:2 * C, :C], c0.weight[:, :C]]).contiguous()
+            b_x = torch.cat([bm, g.bias[C:2 * C], c0.bias]).contiguous()
+            w_a = torch.cat([g.weight[C:2 * C, C:2 * C], c0.weight[:, C:2 * C]]).contiguous()
+            return w_n, w_x, b_x, w_a
+        w_n, w_x, b_x, w_a = derived("v2vnet_stack", srcs, build, (C, bool(cells)))
+        layers = []
+        for c in cells[1:]:
+            g, cc = c.conv_gates, c.conv_can
+            layers.append(derived("v2vnet_gru_layer", (g.weight, g.bias, cc.weight, cc.bias), lambda g=g, cc=cc: (
+                torch.cat([g.weight[C:2 * C, :C], cc.weight[:, :C]]).contiguous(), torch.cat([g.bias[C:2 * C], cc.bias]).contiguous()),
+                (C,)))
+        return w_n, w_x, b_x, w_a, layers
+
+    def _masks(self, n, n_ego, rows, H, W, dev, f64):
+        """roi_mask[i, j] = warp_affine_simple(ones, t[i, j]) for egos i < n_ego, j < n -> [n_ego, n, H, W] (heal_warp_agent)."""
+        ones = torch.ones((1, H, W), dtype=torch.float32, device=dev)
+        zeros = torch.zeros((1, H, W), dtype=torch.float32, device=dev)
+        score = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+        masks = torch.empty((n_ego, n, H, W), dtype=torch.float32, device=dev)
+        for i in range(n_ego):
+            for j in range(n):
+                ops.warp_agent(ones, zeros, rows[i][j], f64, out=(masks[i, j], score))
+        return masks
+
+    def fuse_scene(self, feats, rows, f64):
+        """feats [n, C, H, W] (one scene), rows[i][j] the (2, 3) affine of t[i, j] -> node 0 after num_iteration rounds [1, C, H, W]."""
+        n, C, H, W = (int(v) for v in feats.shape)
+        dev = feats.device
+        w_n, w_x, b_x, w_a, layers = self._weights()
+        mode = "mean" if self.agg_operator == "avg" else "max"
+        T = self.num_iteration
+        masks = self._masks(n, n if T > 1 else 1, rows, H, W, dev, f64)
+        zeros = torch.zeros((1, H, W), dtype=torch.float32, device=dev)
+        score = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+        x = feats.contiguous()
+        for it in range(T):
+            n_ego = n if it < T - 1 else 1                    # (1) the last round: ego 0 only
+            xs = torch.empty((n_ego, n, C, H, W), dtype=torch.float32, device=dev)
+            for i in range(n_ego):
+                for j in range(n):
+                    ops.warp_agent(x[j], zeros, rows[i][j], f64, out=(xs[i, j], score))
+            ego = x[:n_ego]
+            stacked = ops.conv3x3(ego, w_x, b_x)              # (4) [E | beta_x | can_x] or E alone
+            agg = ops.v2v_message(xs, masks[:n_ego], stacked, w_n, None if self.gru_flag else ego, mode)   # (2)
+            if self.gru_flag:                                 # (3)
+                h = ops.gru_zero_state(ops.conv3x3(agg, w_a), stacked[:, C:])
+                for w_l, b_l in layers:
+                    h = ops.gru_zero_state(ops.conv3x3(h, w_l, b_l))
+                x = h
+            else:
+                x = agg
+        return x[:1]
+
+    def _mlp(self, out):
+        """mlp over channels of out [B, C, H, W]: heal_conv1x1 on NCHW (heal_linear on the token-major copy when H*W % 4)."""
+        B, C, H, W = (int(v) for v in out.shape)
+        if (H * W) % 4 == 0:
+            return ops.conv1x1(out, self.mlp.weight.view(C, C, 1, 1), self.mlp.bias)
+        y = ops.linear(out.permute(0, 2, 3, 1).contiguous(), self.mlp.weight, self.mlp.bias)
+        return y.view(B, H, W, C).permute(0, 3, 1, 2).contiguous()
+
+    def forward(self, x, record_len, affine_matrix):
+        C, H, W = (int(v) for v in x.shape[1:])
+        self._check(H, W)
+        lens = record_len_to_list(record_len)
+        if not self.fused_ok(x, lens):
+            return self.forward_torch(x, record_len, affine_matrix)
+        aff, f64 = _host_affine(affine_matrix)
+        nodes = []
+        for b, feats in enumerate(regroup(x, lens)):
+            n = feats.shape[0]
+            rows = [aff[b][i, :n] for i in range(n)]
+            nodes.append(self.fuse_scene(feats, rows, f64))
+        return self._mlp(torch.cat(nodes))
+
+
 def build_fusion(args):
-    """The single-scale fusion operator a model YAML names (`fusion_method`: max | att | v2xvit | cobevt; the other methods of
+    """The single-scale fusion operator a model YAML names (`fusion_method`: max | att | v2xvit | cobevt | v2vnet; the other methods of
     fusion_in_one.py belong to papers outside the hot-path scope)."""
     method = args["fusion_method"]
     if method == "max":
@@ -206,4 +389,6 @@ def build_fusion(args):
         return V2XViTFusion(args["v2xvit"])
     if method == "cobevt":
         return CoBEVT(args["cobevt"])
+    if method == "v2vnet":
+        return V2VNetFusion(args["v2vnet"])
     raise NotImplementedError(f"fusion_method '{method}' is outside the hot-path scope (SURVEY 2, row 2)")

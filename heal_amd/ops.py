@@ -855,6 +855,87 @@ def agent_mean(x):
     return out
 
 
+def v2v_message_tile_h(n_ego, cout, H, W, mode):
+    """Output rows per heal_v2v_message block: 8 for the mean (2 waves per SIMD at 138 VGPRs), 4 for the max (its fold keeps E
+    and a running maximum: 8 rows would leave one wave per SIMD); HEAL_V2V_TH overrides (4 | 8 | 16)."""
+    e = os.environ.get("HEAL_V2V_TH", "")
+    if e in ("4", "8", "16"):
+        return int(e)
+    return 4 if mode == 1 else 8
+
+
+def v2v_message_nsplit(n_ego, n_agents, cout, H, W, tile_h):
+    """Agent-loop splits: 1 unless one launch has fewer blocks than two per CU (256 CUs): then enough splits for ~512 blocks, at
+    most one per agent, none empty.  HEAL_V2V_SPLIT forces a value (clamped to [1, n_agents])."""
+    blocks = n_ego * -(-cout // 64) * -(-W // 16) * -(-H // tile_h)
+    env = os.environ.get("HEAL_V2V_SPLIT")
+    want = int(env) if env is not None else (-(-512 // blocks) if blocks < 512 else 1)
+    want = max(1, min(want, n_agents))
+    return -(-n_agents // -(-n_agents // want))       # no empty split
+
+
+def v2v_message(xs, mask, e, w, residual=None, mode="mean", nsplit=None):
+    """V2VNet's masked message aggregation (heal_v2v_message; fusion_in_one.py:266-294).  xs [n_ego, N, Cin, H, W] warped
+    neighbour maps, mask [n_ego, N, H, W], e [n_ego, >= Cout, H, W] the ego term W_e * x + b (its first Cout channels are read:
+    a slice of the stacked convolution), w [Cout, Cin, 3, 3] the neighbour half of msg_cnn's weight, residual [n_ego, Cout, H, W]
+    or None; mode 'mean' | 'max' -> [n_ego, Cout, H, W]."""
+    xs = _need(xs, torch.float32, "xs")
+    mask = _need(mask, torch.float32, "mask")
+    n_ego, N, cin, H, W = (int(v) for v in xs.shape)
+    cout = int(w.shape[0])
+    if tuple(w.shape) != (cout, cin, 3, 3) or mode not in ("mean", "max") or not 1 <= N <= 8:
+        raise _capi.HealAmdError(f"v2v_message: unsupported weight {tuple(w.shape)} / mode {mode} / {N} agents for xs "
+                                 f"{tuple(xs.shape)} (3x3 weights, mean | max, 1..8 agents)")
+    if tuple(mask.shape) != (n_ego, N, H, W):
+        raise _capi.HealAmdError(f"v2v_message: mask {tuple(mask.shape)} for xs {tuple(xs.shape)}")
+    if not (isinstance(e, torch.Tensor) and e.is_cuda and e.dtype == torch.float32 and e.dim() == 4
+            and int(e.shape[0]) == n_ego and int(e.shape[1]) >= cout and tuple(e.shape[2:]) == (H, W)
+            and e.stride(3) == 1 and e.stride(2) == W and e.stride(1) == H * W):
+        raise _capi.HealAmdError(f"v2v_message: e must be an f32 cuda [n_ego, >= {cout}, {H}, {W}] with contiguous channel planes")
+    _need(e, torch.float32, "e")        # the autograd check (e is read in place: a channel slice is allowed)
+    if residual is not None:
+        residual = _need(residual, torch.float32, "residual")
+        if tuple(residual.shape) != (n_ego, cout, H, W):
+            raise _capi.HealAmdError("v2v_message: residual shape mismatch")
+    m = 1 if mode == "max" else 0
+    th = v2v_message_tile_h(n_ego, cout, H, W, m)
+    ns = v2v_message_nsplit(n_ego, N, cout, H, W, th) if nsplit is None else int(nsplit)
+    frag = conv3x3_fragments(w)
+    out = torch.empty((n_ego, cout, H, W), dtype=torch.float32, device=xs.device)
+    nbytes = _capi.query("heal_v2v_message_workspace", n_ego, cout, H, W, ns)
+    ws = _workspace("v2v_message", nbytes, xs.device) if nbytes else None
+    with _Timed(f"v2v_message_{cin}_{cout}", 2.0 * 9 * n_ego * N * cin * cout * H * W,
+                4.0 * n_ego * (N * (cin + 1) * H * W + 2 * cout * H * W), kernel_events=True):
+        _capi.call("heal_v2v_message", _ptr(xs), _ptr(mask), _ptr(e), int(e.stride(0)), _ptr(frag), _optr(residual), n_ego, N,
+                   cin, cout, H, W, m, ns, th, _ptr(out), _optr(ws), 0 if ws is None else ws.numel(), _stream())
+    return out
+
+
+def gru_zero_state(gates, add=None):
+    """ConvGRU cell with a zero hidden state (heal_gru_zero_state; convgru.py:52-72): gates [n, >= 2C, H, W] (u | c channel
+    blocks, images gates.stride(0) apart), add None or the same layout (added to both blocks) -> h = sigmoid(u) tanh(c) [n, C, H, W].
+    C = gates.shape[1] // 2 unless add is given, then both hold exactly 2C channels."""
+    def check(t, name):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4
+                and t.stride(3) == 1 and t.stride(2) == t.shape[3] and t.stride(1) == t.shape[2] * t.shape[3]):
+            raise _capi.HealAmdError(f"gru_zero_state: {name} must be an f32 cuda [n, 2C, H, W] with contiguous channel planes")
+        _need(t, torch.float32, name)
+    check(gates, "gates")
+    n, c2, H, W = (int(v) for v in gates.shape)
+    if c2 % 2:
+        raise _capi.HealAmdError(f"gru_zero_state: gates has {c2} channels (u | c: an even count)")
+    C = c2 // 2
+    if add is not None:
+        check(add, "add")
+        if int(add.shape[0]) != n or int(add.shape[1]) < c2 or tuple(add.shape[2:]) != (H, W):
+            raise _capi.HealAmdError(f"gru_zero_state: add {tuple(add.shape)} for gates {tuple(gates.shape)}")
+    h = torch.empty((n, C, H, W), dtype=torch.float32, device=gates.device)
+    with _Timed("gru_zero_state", nbytes=4.0 * n * C * H * W * (3 + (2 if add is not None else 0))):
+        _capi.call("heal_gru_zero_state", _ptr(gates), int(gates.stride(0)), _optr(add), 0 if add is None else int(add.stride(0)),
+                   n, C, H, W, _ptr(h), _stream())
+    return h
+
+
 def label_assign(anchor_boxes, gt_boxes, pos_threshold, neg_threshold):
     """Anchor labelling core of generate_label: stand-up boxes [N,4] / [G,4] f32 cuda -> (assigned [N] i32: gt index of a
     positive anchor or -1, neg [N] u8)."""

@@ -24,9 +24,10 @@
 extern "C" {
 #endif
 
-#define HEAL_AMD_ABI_VERSION 8   /* 6 (round 6): + heal_pfn_pillars / heal_pillar_canvas / heal_pillar_stem_block; the measured-negative entry
+#define HEAL_AMD_ABI_VERSION 9   /* 6 (round 6): + heal_pfn_pillars / heal_pillar_canvas / heal_pillar_stem_block; the measured-negative entry
                                    points moved to include/heal_amd_experimental.h (HEAL_BUILD_EXPERIMENTAL=1 builds only);
-                                   8: + heal_agent_window_attention / heal_agent_mean (CoBEVT fusion) */
+                                   8: + heal_agent_window_attention / heal_agent_mean (CoBEVT fusion);
+                                   9: + heal_v2v_message[_workspace] / heal_gru_zero_state (V2VNet fusion) */
 
 int heal_abi_version(void);
 const char* heal_last_error(void);
@@ -697,6 +698,26 @@ int heal_window_attention_backward(const float* qkv, const float* pos_bias, cons
 int heal_agent_window_attention(const float* qkv, const float* bias, int n_agents, int n_valid, int H, int W, int heads,
                                 int dim_head, int window, int mode, float scale, float* out, void* stream);
 int heal_agent_mean(const float* x, int n_agents, long long n_elems, float* out, void* stream);
+
+/* heal_v2v_message: V2VNet's masked message aggregation (opencood/models/fuse_modules/fusion_in_one.py:266-287: msg_cnn over
+ *   cat(warped neighbour, ego), times the warped ROI mask, mean | max over the neighbours; :293-294 the gru_flag: false update).
+ *   For every ego e < n_ego of a scene with n_agents = N agents:
+ *     mode 0 (mean): out[e] = (sum_j mask[e,j] (W_n * xs[e,j]) + (sum_j mask[e,j]) E[e]) / N   (+ residual[e])
+ *     mode 1 (max):  out[e] = max_j mask[e,j] (W_n * xs[e,j] + E[e])                          (+ residual[e])
+ *   W_n * : 3x3 convolution, padding 1, of the warped neighbour maps xs [n_ego, N, cin, H, W]; w_frag = W_n [cout, cin, 3, 3] in
+ *   heal_conv3x3's fragment order (ops.conv3x3_fragments, 16-B aligned); mask [n_ego, N, H, W]; E = the ego term W_e * x_e + bias,
+ *   [cout, H, W] per ego, egos e_stride floats apart (a slice of a wider stacked convolution); residual [n_ego, cout, H, W] or
+ *   NULL; out [n_ego, cout, H, W].  N in [1, 8].  nsplit in [1, N] splits the agent loop over blocks (partials in ws,
+ *   heal_v2v_message_workspace bytes, 16-B aligned; combined in split order); tile_h 4 | 8 | 16 output rows per block.
+ * heal_gru_zero_state: the ConvGRU cell with a zero hidden state (sub_modules/convgru.py:52-72, h_cur = 0):
+ *   h = sigmoid(u) * tanh(c),  u = gates[:, :C] (+ add[:, :C]),  c = gates[:, C:2C] (+ add[:, C:2C]);
+ *   gates / add: n images of [2C, H, W] gates_stride / add_stride floats apart (add may be NULL); h [n, C, H, W].          */
+size_t heal_v2v_message_workspace(int n_ego, int cout, int H, int W, int nsplit);
+int heal_v2v_message(const float* xs, const float* mask, const float* e, long long e_stride, const float* w_frag,
+                     const float* residual, int n_ego, int n_agents, int cin, int cout, int H, int W, int mode, int nsplit,
+                     int tile_h, float* out, void* ws, size_t ws_bytes, void* stream);
+int heal_gru_zero_state(const float* gates, long long gates_stride, const float* add, long long add_stride, int n, int channels,
+                        int H, int W, float* h, void* stream);
 
 /* ---- V2X-ViT linear algebra (opencood/models/sub_modules/base_transformer.py:7-40, hmsa.py:38-151, mswin.py:46-122,
  * split_attn.py:6-62, v2xvit_basic.py:158-192): token-major fp32 GEMM on v_mfma_f32_32x32x2_f32 with the LayerNorm of PreNorm
