@@ -147,6 +147,38 @@ def _need_bias(bias, cout, who):
     return bias
 
 
+def _need_rows(t, width, name, who):
+    """A f32 cuda row matrix [n, width] (made contiguous).  No autograd check: the sparse encoder hands its activations over
+    detached, and SparseTensor.features is never part of a recorded graph."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _capi.HealAmdError(f"{who}: {name} must be a CUDA/HIP tensor (heal_amd has no CPU path)")
+    if t.dtype != torch.float32:
+        raise _capi.HealAmdError(f"{who}: {name} must have dtype torch.float32, got {t.dtype}")
+    if t.dim() != 2 or int(t.shape[1]) != width:
+        raise _capi.HealAmdError(f"{who}: {name} has shape {tuple(t.shape)}, want [n, {width}]")
+    return t.contiguous()
+
+
+def _need_nbr(nbr, K, who):
+    """A neighbour table [n_out, K] int32 on the device (made contiguous): the kernels read it as n_out * K int32 words from a
+    bare pointer, so an int64 table or one with another tap count would be misread without an error."""
+    if not isinstance(nbr, torch.Tensor) or not nbr.is_cuda:
+        raise _capi.HealAmdError(f"{who}: nbr must be a CUDA/HIP tensor (heal_amd has no CPU path)")
+    if nbr.dtype != torch.int32:
+        raise _capi.HealAmdError(f"{who}: nbr must have dtype torch.int32, got {nbr.dtype}")
+    if nbr.dim() != 2 or int(nbr.shape[1]) != K:
+        raise _capi.HealAmdError(f"{who}: nbr has shape {tuple(nbr.shape)}, want [n_out, {K}] for a {K}-tap weight")
+    return nbr.contiguous()
+
+
+def _need_channels(t, cout, name, who):
+    """A per-output-channel f32 vector of exactly `cout` elements (BatchNorm scale / shift of the sparse layers)."""
+    t = _need(t, torch.float32, name)
+    if t.numel() != cout:
+        raise _capi.HealAmdError(f"{who}: {name} has {t.numel()} elements for {cout} output channels")
+    return t
+
+
 def _workspace(key, nbytes, device, zeroed=False):
     """Grow-only per-(op, device) scratch buffer (256-B aligned by the caching allocator).  A buffer that is outgrown is
     RETIRED (derived.retire), not freed: a captured HIP graph may have its address baked in, and handing the memory back to the
@@ -1458,6 +1490,11 @@ class SparseTensor:
         """Gather-GEMM: weight [K,Cin,Cout]; returns features [n_out,Cout]."""
         weight = _need(weight, torch.float32, "weight")
         K, cin, cout = (int(v) for v in weight.shape)
+        features = _need_rows(self.features, cin, "features", "SparseTensor.conv")
+        if not isinstance(nbr, PairTiles):       # pair tiles: a word buffer, checked against K and the channels below
+            nbr = _need_nbr(nbr, K, "SparseTensor.conv")
+        bn_scale = _need_channels(bn_scale, cout, "bn_scale", "SparseTensor.conv")
+        bn_shift = _need_channels(bn_shift, cout, "bn_shift", "SparseTensor.conv")
         frag = sp_weight_fragments(weight)
         n_out = int(nbr.shape[0])
         out = torch.empty((n_out, cout), dtype=torch.float32, device=nbr.device)
@@ -1468,13 +1505,11 @@ class SparseTensor:
                 if K != 27 or not _capi.query("heal_sp_conv_tiles_supported", cin, cout):
                     raise ValueError(f"SparseTensor.conv: pair tiles do not serve a {K}-tap {cin} -> {cout} layer "
                                      "(SparseTensor.rulebook decides per layer)")
-                _capi.call("heal_sp_conv_tiles", _ptr(self.features), _ptr(nbr.buf), n_out, nbr.slot_sites, cin, cout, _ptr(frag),
-                           _ptr(_need(bn_scale, torch.float32, "bn_scale")), _ptr(_need(bn_shift, torch.float32, "bn_shift")),
-                           int(bool(relu)), _ptr(out), _optr(n_out_dev), _stream())
+                _capi.call("heal_sp_conv_tiles", _ptr(features), _ptr(nbr.buf), n_out, nbr.slot_sites, cin, cout, _ptr(frag),
+                           _ptr(bn_scale), _ptr(bn_shift), int(bool(relu)), _ptr(out), _optr(n_out_dev), _stream())
             else:
-                _capi.call("heal_sp_conv", _ptr(self.features), _ptr(nbr), n_out, K, cin, cout, _ptr(weight), _optr(frag),
-                           _ptr(_need(bn_scale, torch.float32, "bn_scale")), _ptr(_need(bn_shift, torch.float32, "bn_shift")),
-                           int(bool(relu)), _ptr(out), _optr(n_out_dev), _stream())
+                _capi.call("heal_sp_conv", _ptr(features), _ptr(nbr), n_out, K, cin, cout, _ptr(weight), _optr(frag),
+                           _ptr(bn_scale), _ptr(bn_shift), int(bool(relu)), _ptr(out), _optr(n_out_dev), _stream())
         if SP_TRACE is not None and TIMING is not None:
             SP_TRACE.append({"cin": cin, "cout": cout, "K": K, "n_in": self.n_dev if self.n_dev is not None else self.n,
                              "n_out": n_out_dev if n_out_dev is not None else n_out, "nbr": nbr, "events": (tm.e0, tm.e1)})
@@ -1503,6 +1538,8 @@ def sp_conv_raw(features, nbr, weight):
     features = _need(features, torch.float32, "features")
     weight = _need(weight, torch.float32, "weight")
     K, cin, cout = (int(v) for v in weight.shape)
+    features = _need_rows(features, cin, "features", "sp_conv_raw")
+    nbr = _need_nbr(nbr, K, "sp_conv_raw")
     key = (cout, str(features.device))
     ident = _SP_IDENT.get(key)
     if ident is None:
@@ -1524,8 +1561,13 @@ def sp_wgrad(features, grad_out, nbr):
     features = _need(features, torch.float32, "features")
     grad_out = _need(grad_out, torch.float32, "grad_out")
     nbr = _need(nbr, torch.int32, "nbr")
+    if nbr.dim() != 2 or features.dim() != 2 or grad_out.dim() != 2:
+        raise _capi.HealAmdError(f"sp_wgrad: features {tuple(features.shape)}, grad_out {tuple(grad_out.shape)} and nbr "
+                                 f"{tuple(nbr.shape)} must be matrices")
     n_out, K = (int(v) for v in nbr.shape)
     cin, cout = int(features.shape[1]), int(grad_out.shape[1])
+    if int(grad_out.shape[0]) != n_out:
+        raise _capi.HealAmdError(f"sp_wgrad: grad_out has {int(grad_out.shape[0])} rows for the {n_out} output rows of nbr")
     if n_out == 0:
         return torch.zeros((K, cin, cout), dtype=torch.float32, device=features.device)
     chunks = _capi.query("heal_sp_wgrad_chunks", n_out)
