@@ -226,6 +226,25 @@ def lidar_baseline(fusion_method="v2xvit", lidar_range=FULL_RANGE, max_cav=5, mo
     return load_general_params(h)
 
 
+def lidar_coalign(fusion_method="att", lidar_range=FULL_RANGE, max_cav=5):
+    """HeterModelBaselineMs, the multiscale CoAlign baseline (LiDAROnly/lidar_coalign.yaml with its `att` block repaired,
+    INTEGRATION.md): PointPillars -> one-level ResNet backbone -> identity aligner, then three fusion levels (64 / 128 / 256
+    channels at 1, 1/2, 1/4 of the 0.8 m map), each fused over the agents (att | max), decoded and shrunk to 256 channels."""
+    h = _common(lidar_range, max_cav)
+    h["name"] = f"heal_amd_opv2v_lidar_coalign_{fusion_method}"
+    args = {"ego_modality": "m1", "lidar_range": list(lidar_range), "supervise_single": False,
+            "m1": _pointpillar_modality(lidar_range, "identity"), "fusion_method": fusion_method,
+            "fusion_backbone": {"layer_nums": [3, 5, 8], "layer_strides": [1, 2, 2], "num_filters": [64, 128, 256],
+                                "upsample_strides": [1, 2, 4], "num_upsample_filter": [128, 128, 128]},
+            "shrink_header": _shrink_header(), "in_head": 256, "anchor_number": 2, "dir_args": copy.deepcopy(DIR_ARGS)}
+    if fusion_method == "att":
+        args["att"] = {"feat_dim": [64, 128, 256]}
+    elif fusion_method != "max":
+        raise NotImplementedError(f"lidar_coalign: fusion_method '{fusion_method}' (max | att)")
+    h["model"] = {"core_method": "heter_model_baseline_ms", "args": args}
+    return load_general_params(h)      # feature_stride 2 (the _common default): the fused map is the backbone's stride-2 grid
+
+
 def oldstyle_pointpillar(fusion_method=None, lidar_range=FULL_RANGE, max_cav=5, compression=0):
     """Old-style YAML (v2xsim2/visualization.yaml `model` block): core_method point_pillar, or
     point_pillar_baseline when a fusion_method (max | att | v2xvit) is given.  Uses the `processed_lidar` key."""

@@ -594,6 +594,152 @@ __global__ __launch_bounds__(256) void k_warp_fuse_backward(const float* __restr
     }
 }
 
+// ---- CoAlign: warp + per-pixel agent attention (or max), every level of a scene in ONE launch ---------------------------------
+// Reference arithmetic (heter_model_baseline_ms.py:199-207 calls one AttFusion / MaxFusion per level with the same affine matrix):
+//   fusion_in_one.py:126-151  x_j = warp_affine_simple(feats[j], t[0, j]);  per pixel X = [n, C]
+//   fusion_in_one.py:14-45    softmax(X X^T / sqrt_dim) X, of which only row 0 (the ego) is kept:
+//                             p = softmax_j(x_0 . x_j / sqrt_dim),  out = sum_j p_j x_j
+//   fusion_in_one.py:87-124   max: out = max_j x_j
+// The scores need every channel of a pixel before the first output channel can be written, so the channel axis cannot be sliced
+// over blocks as in K5.  A block of 256 threads is a tile of `pix` ego pixels x 256 / pix channel slices (thread = pixel + slice): 16 x 4
+// pixels x 4 slices on a large level, 16 x 1 pixels x 16 slices on a small one, so that the 64 x 64 x 256 level of the full-size scene is
+// 256 blocks of 16 channels per thread instead of 64 blocks of 64 (measured: that level alone 236 us before, the tail of the launch):
+//   1. every thread computes, once, its taps per agent (make_taps: the sampling arithmetic of K5, the ego included -- agent 0 goes
+//      through the same sampler with row t[0, 0]);
+//   2. sweep 1: each thread accumulates the n dot products x_0 . x_j over ITS channels; the slices' partial sums meet in LDS and are
+//      added in slice order by every thread (no atomics: two launches are bit-equal);
+//   3. softmax over ALL n agents: an agent whose footprint misses the pixel has x_j = 0, logit 0, and keeps its exp(0 - max) share.
+//      The wave-uniform "no lane of this wave reaches agent j" test skips that agent's loads, never its term of the softmax;
+//   4. sweep 2: out[c] = sum_j p_j x_j[c] (or max_j) over the thread's channels; the second read of the taps comes from L2 / Infinity
+//      Cache (the tile's source footprint was read a few microseconds earlier by the same block).
+// The taps are gathered directly from global memory, as k_warp_fuse does; the LDS staging of k_warp_fuse_lds is not applied here.
+constexpr int WA_TW = 16;              // ego pixel tile: 16 x (pix / 16)
+constexpr int WA_THREADS = 256;        // = pix * channel slices
+constexpr int WA_SMALL_TILES = 1024;   // a level with fewer 16 x 4 tiles than this runs 16 x 1 tiles x 16 slices
+
+struct WaLevel {
+    const float* feats;     // [n_agents, C, H, W]
+    float* out;             // [C, H, W]
+    int C, H, W;
+    int tiles_x, block0;    // tiles per row, first block of this level
+    int pix;                // ego pixels per block: 64 (16 x 4, 4 channel slices) or 16 (16 x 1, 16 slices)
+    float sqrt_dim;         // the logits are divided by this (fusion_in_one.py:39-42)
+};
+struct WaLevels {
+    WaLevel lv[WL_MAXL];
+    int n_levels, n_agents, grid_f64, mode;   // mode 0: attention, 1: max
+    const double* mdev;
+    double m[WF_MAXA][6];
+};
+
+template <int NA>
+__global__ __launch_bounds__(WA_THREADS) void k_warp_att_fuse(const WaLevels P) {
+    __shared__ float s_dot[NA * WA_THREADS];     // [slice][agent][pixel]
+    int lvl = 0;
+#pragma unroll
+    for (int i = 1; i < WL_MAXL; ++i)
+        if (i < P.n_levels && (int)blockIdx.x >= P.lv[i].block0) lvl = i;
+    const WaLevel& L = P.lv[lvl];
+    const int tile = blockIdx.x - L.block0;
+    const int pix_n = L.pix, n_cs = WA_THREADS / pix_n;
+    const int lane = threadIdx.x & (pix_n - 1), cs = threadIdx.x / pix_n;      // pixel of the tile, channel slice
+    const int w = (tile % L.tiles_x) * WA_TW + (lane & (WA_TW - 1));
+    const int h = (tile / L.tiles_x) * (pix_n / WA_TW) + (lane / WA_TW);
+    const bool live = w < L.W && h < L.H;     // no early return: the block meets at a barrier
+    const int HW = L.H * L.W;
+    int off[NA][4];
+    float wt[NA][4];
+    unsigned reach = 0;      // bit a: some lane of this wave samples agent a inside its map
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { off[a][k] = 0; wt[a][k] = 0.f; }
+        if (live) {
+            float gx, gy;
+            double m[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) m[k] = P.mdev ? P.mdev[a * 6 + k] : P.m[a][k];   // wave-uniform
+            if (P.grid_f64) grid_point<double>(m, h, w, L.H, L.W, gx, gy);
+            else grid_point<float>(m, h, w, L.H, L.W, gx, gy);
+            const Taps t = make_taps(gx, gy, L.H, L.W);
+            const int o4[4] = {t.off, t.off + 1, t.off + L.W, t.off + L.W + 1};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const bool ok = (t.ok >> k) & 1u;    // a tap outside the image: weight 0 on a valid address
+                off[a][k] = ok ? o4[k] : 0;
+                wt[a][k] = ok ? t.w[k] : 0.f;
+            }
+        }
+        const bool any = (wt[a][0] != 0.f) | (wt[a][1] != 0.f) | (wt[a][2] != 0.f) | (wt[a][3] != 0.f);
+        reach |= __ballot(any) ? (1u << a) : 0u;
+    }
+    const int cper = (L.C + n_cs - 1) / n_cs;
+    const int c_lo = cs * cper, c_hi = min(c_lo + cper, L.C);
+
+    auto tap4 = [&](int a, int c) -> float {      // sample(): nw, ne, sw, se accumulated in that order
+        const float* src = L.feats + ((size_t)a * L.C + c) * HW;
+        float v = src[off[a][0]] * wt[a][0];
+        v += src[off[a][1]] * wt[a][1];
+        v += src[off[a][2]] * wt[a][2];
+        v += src[off[a][3]] * wt[a][3];
+        return v;
+    };
+
+    float prob[NA];
+    if (P.mode == 0) {
+        float dot[NA];
+#pragma unroll
+        for (int a = 0; a < NA; ++a) dot[a] = 0.f;
+        if (reach & 1u) {          // an ego that reaches no lane: every logit of the wave is 0
+#pragma unroll 2
+            for (int c = c_lo; c < c_hi; ++c) {
+                const float x0 = tap4(0, c);
+                dot[0] += x0 * x0;
+#pragma unroll
+                for (int a = 1; a < NA; ++a)
+                    if ((reach >> a) & 1u) dot[a] += x0 * tap4(a, c);
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < NA; ++a) s_dot[(cs * NA + a) * pix_n + lane] = dot[a];
+        __syncthreads();
+        float mx = -INFINITY;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            float d = s_dot[a * pix_n + lane];
+            for (int s = 1; s < n_cs; ++s) d += s_dot[(s * NA + a) * pix_n + lane];
+            prob[a] = d / L.sqrt_dim;
+            mx = fmaxf(mx, prob[a]);
+        }
+        float den = 0.f;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) { prob[a] = expf(prob[a] - mx); den += prob[a]; }
+#pragma unroll
+        for (int a = 0; a < NA; ++a) prob[a] = prob[a] / den;
+    } else {
+#pragma unroll
+        for (int a = 0; a < NA; ++a) prob[a] = 0.f;
+    }
+
+    const int pix = h * L.W + w;
+#pragma unroll 2
+    for (int c = c_lo; c < c_hi; ++c) {
+        float acc = 0.f;
+        if (P.mode == 0) {
+#pragma unroll
+            for (int a = 0; a < NA; ++a)
+                if ((reach >> a) & 1u) acc += prob[a] * tap4(a, c);
+        } else {
+#pragma unroll
+            for (int a = 0; a < NA; ++a) {
+                const float v = ((reach >> a) & 1u) ? tap4(a, c) : 0.f;     // an agent out of reach is a zero map, and takes part
+                acc = a == 0 ? v : fmaxf(acc, v);
+            }
+        }
+        if (live) L.out[(size_t)c * HW + pix] = acc;
+    }
+}
+
 static int fill_params(WarpParams& p, int n_agents, int C, int H, int W, const double* affine_host,
                        const double* affine_dev, int grid_f64, const int32_t* crop_host) {
     HEAL_REQUIRE(n_agents >= 1 && n_agents <= WF_MAXA, "warp_fuse: n_agents must be in [1,%d] (got %d)",
@@ -682,6 +828,47 @@ extern "C" int heal_warp_fuse_levels(int n_levels, const float* const* feats_hos
 #define HEAL_WFL(N) case N: HEAL_LAUNCH_EV(k_warp_fuse_lds<N>, dim3((unsigned)blocks), dim3(256), 0, st, P); break;
         HEAL_WFL(1) HEAL_WFL(2) HEAL_WFL(3) HEAL_WFL(4) HEAL_WFL(5) HEAL_WFL(6) HEAL_WFL(7) HEAL_WFL(8)
 #undef HEAL_WFL
+    }
+    HEAL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int heal_warp_att_fuse_levels(int n_levels, const float* const* feats_host, int n_agents, const int32_t* channels_host,
+                                         const int32_t* h_host, const int32_t* w_host, const float* sqrt_dim_host,
+                                         const double* affine_host, const double* affine_dev, int grid_f64, int mode,
+                                         float* const* out_host, void* stream) {
+    HEAL_REQUIRE(n_levels >= 1 && n_levels <= WL_MAXL, "warp_att_fuse_levels: 1..%d levels per launch (got %d)", WL_MAXL, n_levels);
+    HEAL_REQUIRE(n_agents >= 1 && n_agents <= WF_MAXA, "warp_att_fuse_levels: n_agents must be in [1,%d] (got %d)", WF_MAXA, n_agents);
+    HEAL_REQUIRE(mode == 0 || mode == 1, "warp_att_fuse_levels: mode must be 0 (attention) or 1 (max), got %d", mode);
+    HEAL_REQUIRE(feats_host && out_host && channels_host && h_host && w_host, "warp_att_fuse_levels: null argument");
+    HEAL_REQUIRE(affine_host != nullptr || affine_dev != nullptr, "warp_att_fuse_levels: affine is NULL (host and device)");
+    WaLevels P;
+    P.n_levels = n_levels; P.n_agents = n_agents; P.grid_f64 = grid_f64; P.mode = mode; P.mdev = affine_dev;
+    for (int a = 0; a < WF_MAXA; ++a)
+        for (int k = 0; k < 6; ++k) P.m[a][k] = (a < n_agents && affine_host) ? affine_host[a * 6 + k] : 0.0;
+    long long blocks = 0;
+    for (int l = 0; l < WL_MAXL; ++l) {
+        WaLevel& L = P.lv[l];
+        if (l >= n_levels) { L = P.lv[0]; L.block0 = 1 << 30; continue; }
+        HEAL_REQUIRE(feats_host[l] && out_host[l] && channels_host[l] >= 1 && h_host[l] >= 1 && w_host[l] >= 1,
+                     "warp_att_fuse_levels: bad level %d", l);
+        HEAL_REQUIRE((long long)n_agents * channels_host[l] * h_host[l] * w_host[l] < (1ll << 31),
+                     "warp_att_fuse_levels: level %d has more than 2^31 elements", l);
+        L.feats = feats_host[l]; L.out = out_host[l];
+        L.C = channels_host[l]; L.H = h_host[l]; L.W = w_host[l];
+        L.sqrt_dim = sqrt_dim_host ? sqrt_dim_host[l] : (float)sqrt((double)L.C);
+        HEAL_REQUIRE(mode == 1 || L.sqrt_dim > 0.f, "warp_att_fuse_levels: sqrt_dim of level %d must be positive", l);
+        L.tiles_x = ceil_div(L.W, WA_TW);
+        L.pix = (long long)L.tiles_x * ceil_div(L.H, 4) < WA_SMALL_TILES ? 16 : 64;
+        L.block0 = (int)blocks;
+        blocks += (long long)L.tiles_x * ceil_div(L.H, L.pix / WA_TW);
+    }
+    HEAL_REQUIRE(blocks < (1ll << 30), "warp_att_fuse_levels: grid too large");
+    hipStream_t st = (hipStream_t)stream;
+    switch (n_agents) {
+#define HEAL_WAF(N) case N: HEAL_LAUNCH_EV(k_warp_att_fuse<N>, dim3((unsigned)blocks), dim3(WA_THREADS), 0, st, P); break;
+        HEAL_WAF(1) HEAL_WAF(2) HEAL_WAF(3) HEAL_WAF(4) HEAL_WAF(5) HEAL_WAF(6) HEAL_WAF(7) HEAL_WAF(8)
+#undef HEAL_WAF
     }
     HEAL_LAUNCH_CHECK();
     return 0;

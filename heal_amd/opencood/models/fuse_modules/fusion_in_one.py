@@ -377,6 +377,71 @@ class V2VNetFusion(nn.Module):
         return self._mlp(torch.cat(nodes))
 
 
+# ---- multiscale fusion of HeterModelBaselineMs (CoAlign) ------------------------------------------------------------------------
+MS_MAX_AGENTS = ops.WARP_ATT_MAX_AGENTS
+
+
+def _ms_mode(fusion_net):
+    kinds = {type(m) for m in fusion_net}
+    if kinds == {AttFusion}:
+        return "att"
+    if kinds == {MaxFusion}:
+        return "max"
+    raise NotImplementedError(f"multiscale fusion takes AttFusion or MaxFusion at every level, got {sorted(k.__name__ for k in kinds)}")
+
+
+def ms_fused_ok(fusion_net, feature_list, lens):
+    """True when `fuse_levels` runs heal_warp_att_fuse_levels: inference on the device in fp32, at most 8 agents per scene and 4
+    levels.  HEAL_MSATT_FUSED=0 keeps the torch arithmetic on the device too (the A/B switch of scripts/coalign_bench.py)."""
+    return (all(f.is_cuda and f.dtype == torch.float32 for f in feature_list)
+            and not (torch.is_grad_enabled() and any(f.requires_grad for f in feature_list))
+            and max(lens) <= MS_MAX_AGENTS and 1 <= len(feature_list) <= ops.WARP_ATT_MAX_LEVELS
+            and os.environ.get("HEAL_MSATT_FUSED", "1") != "0")
+
+
+def fuse_level_torch(module, x, lens, aff):
+    """One level as the reference computes it (fusion_in_one.py:87-151): warp_affine_simple with row t[0, :n] of every scene, then
+    the maximum over agents, or row 0 of softmax(X X^T / sqrt_dim) X per pixel.  The CPU and gradient path."""
+    C, H, W = x.shape[1:]
+    out = []
+    for b, feats in enumerate(regroup(x, lens)):
+        n = feats.shape[0]
+        ego = _warp_affine_simple(feats, aff[b][0, :n], (H, W))
+        if isinstance(module, MaxFusion):
+            out.append(torch.max(ego, dim=0)[0])
+            continue
+        t = ego.view(n, C, -1).permute(2, 0, 1)                                  # [HW, n, C]
+        attn = torch.softmax(torch.bmm(t, t.transpose(1, 2)) / module.sqrt_dim, -1)
+        out.append(torch.bmm(attn, t).permute(1, 2, 0).view(n, C, H, W)[0])
+    return torch.stack(out)
+
+
+def fuse_levels(fusion_net, feature_list, record_len, affine_matrix):
+    """HeterModelBaselineMs' fusion loop (heter_model_baseline_ms.py:204-206): fusion_net[i](feature_list[i], record_len,
+    affine_matrix) for every level, all levels with the same normalised affine matrix -> list of [B, C_i, H_i, W_i].
+    Inference on the device: ONE heal_warp_att_fuse_levels launch per scene (`ms_fused_ok`); otherwise the reference's torch
+    arithmetic.  A scene with more than 8 agents is refused on every path (the reference's configurations stop at max_cav 5)."""
+    if len(fusion_net) != len(feature_list):
+        raise ValueError(f"{len(fusion_net)} fusion modules for {len(feature_list)} feature levels")
+    mode = _ms_mode(fusion_net)
+    lens = record_len_to_list(record_len)
+    if max(lens) > MS_MAX_AGENTS:
+        raise ValueError(f"multiscale fusion: a scene has {max(lens)} agents, more than the {MS_MAX_AGENTS} it is built for")
+    if not ms_fused_ok(fusion_net, feature_list, lens):
+        aff = affine_matrix if isinstance(affine_matrix, torch.Tensor) else torch.from_numpy(np.asarray(affine_matrix))
+        aff = aff.to(feature_list[0].device)
+        return [fuse_level_torch(m, x, lens, aff) for m, x in zip(fusion_net, feature_list)]
+    aff, f64 = _host_affine(affine_matrix)
+    sqrt_dims = [m.sqrt_dim for m in fusion_net] if mode == "att" else None
+    scenes, start = [], 0
+    for b, n in enumerate(lens):
+        scenes.append(ops.warp_att_fuse_levels([f[start:start + n] for f in feature_list], aff[b][0, :n], f64, mode, sqrt_dims))
+        start += n
+    if len(scenes) == 1:
+        return [y.unsqueeze(0) for y in scenes[0]]
+    return [torch.stack([s[i] for s in scenes]) for i in range(len(feature_list))]
+
+
 def build_fusion(args):
     """The single-scale fusion operator a model YAML names (`fusion_method`: max | att | v2xvit | cobevt | v2vnet; the other methods of
     fusion_in_one.py belong to papers outside the hot-path scope)."""

@@ -644,6 +644,47 @@ def warp_fuse_levels(feats_list, occ_list, affine_rows, grid_f64=True, crops=Non
     return outs
 
 
+WARP_ATT_MAX_AGENTS, WARP_ATT_MAX_LEVELS = 8, 4
+
+
+def warp_att_fuse_levels(feats_list, affine_rows, grid_f64=True, mode="att", sqrt_dims=None):
+    """CoAlign's multiscale fusion for every level of one scene in ONE launch (heal_warp_att_fuse_levels): per ego pixel the
+    agents' maps are warped into the ego frame (agent 0 included) and reduced with the ego row of the per-pixel agent attention
+    (mode "att": softmax_j(x_0 . x_j / sqrt_dim) weights) or the maximum over agents (mode "max").
+    feats_list[l] [n,C_l,H_l,W_l] fp32, affine_rows [n,2,3] (host array or CUDA tensor read at run time, shared by the levels),
+    sqrt_dims[l]: the divisor of the logits (None: sqrt(C_l)) -> list of [C_l,H_l,W_l]."""
+    if mode not in ("att", "max"):
+        raise _capi.HealAmdError(f"warp_att_fuse_levels: mode must be 'att' or 'max', got {mode!r}")
+    L = len(feats_list)
+    if not 1 <= L <= WARP_ATT_MAX_LEVELS:
+        raise _capi.HealAmdError(f"warp_att_fuse_levels: 1..{WARP_ATT_MAX_LEVELS} levels per launch (got {L})")
+    feats_list = [_need(f, torch.float32, "feats") for f in feats_list]
+    if any(f.dim() != 4 for f in feats_list):
+        raise _capi.HealAmdError("warp_att_fuse_levels: every level must be [n, C, H, W]")
+    n = int(feats_list[0].shape[0])
+    if any(int(f.shape[0]) != n for f in feats_list):
+        raise _capi.HealAmdError(f"warp_att_fuse_levels: levels with different agent counts {[int(f.shape[0]) for f in feats_list]}")
+    if not 1 <= n <= WARP_ATT_MAX_AGENTS:
+        raise _capi.HealAmdError(f"warp_att_fuse_levels: 1..{WARP_ATT_MAX_AGENTS} agents per scene (got {n})")
+    if sqrt_dims is not None and len(sqrt_dims) != L:
+        raise _capi.HealAmdError(f"warp_att_fuse_levels: {len(sqrt_dims)} sqrt_dims for {L} levels")
+    outs, nbytes = [], 0.0
+    for f in feats_list:
+        C, H, W = (int(v) for v in f.shape[1:])
+        outs.append(torch.empty((C, H, W), dtype=torch.float32, device=f.device))
+        nbytes += 4.0 * H * W * (n * C + C)                 # compulsory traffic: every agent's map once, the fused map once
+    a, ap, adev = _affine_args(affine_rows, n)
+    sd = [float(np.float32(np.sqrt(int(f.shape[1])) if sqrt_dims is None else sqrt_dims[l])) for l, f in enumerate(feats_list)]
+    fp = _host_array([f.data_ptr() for f in feats_list], ctypes.c_void_p)
+    yp = _host_array([y.data_ptr() for y in outs], ctypes.c_void_p)
+    with _Timed("warp_att_fuse_levels", 0.0, nbytes, kernel_events=True):
+        _capi.call("heal_warp_att_fuse_levels", L, fp, n, _host_array([int(f.shape[1]) for f in feats_list], ctypes.c_int32),
+                   _host_array([int(f.shape[2]) for f in feats_list], ctypes.c_int32),
+                   _host_array([int(f.shape[3]) for f in feats_list], ctypes.c_int32), _host_array(sd, ctypes.c_float),
+                   ap, adev, int(bool(grid_f64)), 0 if mode == "att" else 1, yp, _stream())
+    return outs
+
+
 def warp_fuse_backward(feats, occ, affine_rows, grad_out, grid_f64=True, crop=None):
     """Gradient of warp_fuse with respect to (feats, occ): grad_out [C,H,W] -> ([n,C,H,W], [n,1,H,W])."""
     feats = _need(feats, torch.float32, "feats")

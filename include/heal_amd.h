@@ -24,10 +24,11 @@
 extern "C" {
 #endif
 
-#define HEAL_AMD_ABI_VERSION 9   /* 6 (round 6): + heal_pfn_pillars / heal_pillar_canvas / heal_pillar_stem_block; the measured-negative entry
+#define HEAL_AMD_ABI_VERSION 10  /* 6 (round 6): + heal_pfn_pillars / heal_pillar_canvas / heal_pillar_stem_block; the measured-negative entry
                                    points moved to include/heal_amd_experimental.h (HEAL_BUILD_EXPERIMENTAL=1 builds only);
                                    8: + heal_agent_window_attention / heal_agent_mean (CoBEVT fusion);
-                                   9: + heal_v2v_message[_workspace] / heal_gru_zero_state (V2VNet fusion) */
+                                   9: + heal_v2v_message[_workspace] / heal_gru_zero_state (V2VNet fusion);
+                                   10: + heal_warp_att_fuse_levels (CoAlign multiscale fusion) */
 
 int heal_abi_version(void);
 const char* heal_last_error(void);
@@ -174,6 +175,20 @@ int heal_warp_fuse_levels(int n_levels, const float* const* feats_host, const fl
                           const int32_t* channels_host, const int32_t* h_host, const int32_t* w_host,
                           const double* affine_host, const double* affine_dev, int grid_f64, const int32_t* crop_host,
                           float* const* out_host, void* stream);
+
+/* heal_warp_att_fuse_levels: the multiscale fusion of HeterModelBaselineMs (heter_model_baseline_ms.py:199-207: one AttFusion or
+ *   MaxFusion per level, all with the same normalised affine matrix) for every level of one scene in ONE launch.  Per ego pixel:
+ *   x_j = warp_affine_simple(feats[j], row j) for j = 0 .. n_agents-1 (the ego, agent 0, goes through the sampler too), then
+ *     mode 0 (fusion_in_one.py:14-45,126-151): p = softmax_j(x_0 . x_j / sqrt_dim), out = sum_j p_j x_j -- the ego row of the
+ *            n x n attention; an agent whose footprint misses the pixel is a zero vector with logit 0 and keeps its softmax share;
+ *     mode 1 (fusion_in_one.py:87-124): out = max_j x_j.
+ *   Level l: feats_host[l] [n_agents, C_l, H_l, W_l], out_host[l] [C_l, H_l, W_l] (HOST arrays of device pointers); sqrt_dim_host[l]
+ *   divides the logits (NULL: sqrt(C_l)); affine rows as heal_warp_fuse (host, or device memory read at run time).  Any C, H, W;
+ *   1..4 levels, 1..8 agents.  No atomics: repeated launches are bit-equal.  Sampling arithmetic as heal_warp_fuse.              */
+int heal_warp_att_fuse_levels(int n_levels, const float* const* feats_host, int n_agents, const int32_t* channels_host,
+                              const int32_t* h_host, const int32_t* w_host, const float* sqrt_dim_host,
+                              const double* affine_host, const double* affine_dev, int grid_f64, int mode,
+                              float* const* out_host, void* stream);
 
 /* heal_warp_fuse_backward: gradient of heal_warp_fuse with respect to the agents' maps and occupancy logits (training; the
  *   autograd of warp_affine_simple x 2 + masked softmax + weighted sum, pyramid_fuse.py:17-63,145-162).  Arguments as
