@@ -46,6 +46,7 @@ _SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p]),
     "heal_warp_att_fuse_levels": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                           c_int, c_void_p, c_void_p]),
+    "heal_disco_fuse": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 11),
     "heal_warp_fuse_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "heal_warp_agent": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,

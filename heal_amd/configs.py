@@ -197,7 +197,7 @@ def _baseline_modality(base, strides, inplanes=None):
 
 def lidar_baseline(fusion_method="v2xvit", lidar_range=FULL_RANGE, max_cav=5, modality="m1"):
     """HeterModelBaseline (LiDAROnly/lidar_v2xvit.yaml; BASELINE config 5 with modality='m3'):
-    encoder -> plain BEV backbone -> shrinker -> single-scale fusion (v2xvit | att | max | cobevt | v2vnet) -> heads."""
+    encoder -> plain BEV backbone -> shrinker -> single-scale fusion (v2xvit | att | max | cobevt | v2vnet | disconet) -> heads."""
     h = _common(lidar_range, max_cav)
     h["name"] = f"heal_amd_opv2v_{modality}_{fusion_method}"
     if modality == "m1":
@@ -220,6 +220,8 @@ def lidar_baseline(fusion_method="v2xvit", lidar_range=FULL_RANGE, max_cav=5, mo
         W = int(round((lidar_range[3] - lidar_range[0]) / (0.4 * 4)))
         args["v2vnet"] = {"num_iteration": 2, "in_channels": 256, "gru_flag": True, "agg_operator": "avg",
                           "conv_gru": {"H": H, "W": W, "num_layers": 1, "kernel_size": [[3, 3]]}}
+    elif fusion_method == "disconet":   # LiDAROnly/lidar_disco.yaml
+        args["disconet"] = {"feat_dim": 256}
     h["model"] = {"core_method": "heter_model_baseline", "args": args}
     # encoder + backbone + stride-2 shrinker leave the map at 1/4 of the 0.4 m anchor grid (lidar_v2xvit.yaml: feature_stride 4)
     h["postprocess"]["anchor_args"]["feature_stride"] = 4

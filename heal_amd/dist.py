@@ -884,6 +884,9 @@ def make_sharded(model, rank, world, wire_dtype=None, collective=None, split=Non
         if type(model.fusion_net).__name__ == "V2VNetFusion":
             raise NotImplementedError("no agent-sharded split for V2VNet fusion: its nodes exchange features in every message-passing "
                                       "round (fusion_in_one.py:255-310), not once after the warp")
+        if type(model.fusion_net).__name__ == "DiscoFusion":
+            raise NotImplementedError("no agent-sharded split for DiscoFusion: its pixel weights need the ego's unwarped map next to "
+                                      "every gathered agent (fusion_in_one.py:188-192), which the warp-then-gather exchange does not carry")
         if (world > 1 and type(model.fusion_net).__name__ == "V2XViTFusion"
                 and os.environ.get("HEAL_V2XVIT_STRIPES", "1") != "0"):
             return ShardedBaselineStriped(model, rank, world, wire_dtype, collective)

@@ -1,7 +1,8 @@
 """Single-scale fusion operators used by HeterModelBaseline (reference: opencood/models/fuse_modules/
-fusion_in_one.py): MaxFusion (:87-124), AttFusion (:126-151, :14-45), V2VNetFusion (:203-318), V2XViTFusion (:320-372),
-CoBEVT (:374-430).  Warping to the ego frame is K5's heal_warp_agent; the per-pixel attention is K6; CoBEVT's agent-window
-attention is heal_agent_window_attention (swap_fusion_modules.py); V2VNet's masked message aggregation is heal_v2v_message."""
+fusion_in_one.py): MaxFusion (:87-124), AttFusion (:126-151, :14-45), DiscoFusion (:153-201), V2VNetFusion (:203-318),
+V2XViTFusion (:320-372), CoBEVT (:374-430).  Warping to the ego frame is K5's heal_warp_agent; the per-pixel attention is K6; CoBEVT's
+agent-window attention is heal_agent_window_attention (swap_fusion_modules.py); V2VNet's masked message aggregation is
+heal_v2v_message; DiscoNet's warp + pixel-weight MLP + softmax is heal_disco_fuse."""
 import os
 
 import numpy as np
@@ -199,6 +200,101 @@ def _warp_affine_simple(src, M, dsize):
     import torch.nn.functional as F
     grid = F.affine_grid(M, [src.shape[0], src.shape[1], dsize[0], dsize[1]], align_corners=False).to(src)
     return F.grid_sample(src, grid, align_corners=False)
+
+
+class DiscoFusion(nn.Module):
+    """fusion_in_one.py:153-201 (with fuse_modules/disco_fuse.py).  Per scene: every agent warped into the ego frame, one logit per
+    (agent, pixel) from PixelWeightLayer(cat(warped neighbour, unwarped ego)), softmax over agents, weighted sum of the warped maps.
+
+    On the CPU, under autograd, in training mode (BatchNorm batch statistics) and for shapes the kernel does not take, the
+    reference's torch arithmetic runs (`forward_torch`).  Inference on the device is one heal_conv1x1 + one heal_disco_fuse launch
+    per scene, with these identities (DiscoNet):
+      1. inference BatchNorm folds into the convolution before it;
+      2. conv1_1(cat(nbr_j, x_0)) = W1n nbr_j + (W1e x_0 + b1): the ego term E0 is computed once per scene;
+      3. the softmax of one logit is 1: a single agent's output is its warped map, the MLP is skipped.
+    HEAL_DISCO_FUSED=0 runs the torch arithmetic on the device too (the A/B switch of scripts/disconet_bench.py)."""
+
+    def __init__(self, feature_dims):
+        super().__init__()
+        from heal_amd.opencood.models.fuse_modules.disco_fuse import PixelWeightLayer
+        self.pixel_weight_layer = PixelWeightLayer(feature_dims)
+
+    # ---- the reference's arithmetic ----------------------------------------------------------------------------------------
+    def forward_torch(self, x, record_len, affine_matrix):
+        """fusion_in_one.py:175-201 as written (the CPU, gradient, training and unsupported-shape path)."""
+        _, C, H, W = x.shape
+        lens = record_len_to_list(record_len)
+        aff = affine_matrix if isinstance(affine_matrix, torch.Tensor) else torch.from_numpy(np.asarray(affine_matrix))
+        aff = aff.to(x.device)
+        out = []
+        for b, feats in enumerate(regroup(x, lens)):
+            N = lens[b]
+            t_matrix = aff[b][:N, :N, :, :]
+            neighbor = _warp_affine_simple(feats, t_matrix[0, :, :, :], (H, W))
+            ego = feats[0].view(1, C, H, W).expand(N, -1, -1, -1)
+            weight = self.pixel_weight_layer(torch.cat((neighbor, ego), dim=1))        # [N, 1, H, W]
+            weight = torch.softmax(weight, dim=0).expand(-1, C, -1, -1)
+            out.append(torch.sum(weight * neighbor, dim=0))
+        return torch.stack(out)
+
+    # ---- inference on the device -------------------------------------------------------------------------------------------
+    def fused_ok(self, x, lens):
+        C, H, W = (int(v) for v in x.shape[1:])
+        ego_ok = (H * W) % 4 == 0 or ops.linear_supported(H * W, C, ops.DISCO_WIDTHS[0])     # how E0 is computed
+        return (x.is_cuda and x.dtype == torch.float32 and not self.training
+                and not (torch.is_grad_enabled() and x.requires_grad) and max(lens) <= ops.DISCO_MAX_AGENTS
+                and C % 4 == 0 and C == self.pixel_weight_layer.conv1_1.in_channels // 2 and ego_ok
+                and os.environ.get("HEAL_DISCO_FUSED", "1") != "0")
+
+    def _weights(self):
+        """(W1n in A-fragment order, W1e [128, C, 1, 1], b1, W2, b2, W3, b3, w4, b4) with the BatchNorms folded, from the parameters
+        and running statistics (derived store: rebuilt when one of them changes, capture-safe)."""
+        from heal_amd.derived import derived
+        pw = self.pixel_weight_layer
+        pairs = ((pw.conv1_1, pw.bn1_1), (pw.conv1_2, pw.bn1_2), (pw.conv1_3, pw.bn1_3))
+        srcs = tuple(t for conv, bn in pairs for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+        srcs += (pw.conv1_4.weight, pw.conv1_4.bias)
+
+        def build():
+            folded = []
+            for conv, bn in pairs:
+                scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
+                w = conv.weight.reshape(conv.out_channels, conv.in_channels) * scale[:, None]
+                folded.append((w, (conv.bias - bn.running_mean) * scale + bn.bias))
+            (w1, b1), (w2, b2), (w3, b3) = folded
+            C = w1.shape[1] // 2
+            return (ops.mfma_a_fragments(w1[:, :C].contiguous()), w1[:, C:].reshape(-1, C, 1, 1).contiguous(), b1.contiguous(),
+                    w2.contiguous(), b2.contiguous(), w3.contiguous(), b3.contiguous(),
+                    pw.conv1_4.weight.reshape(-1).contiguous(), pw.conv1_4.bias.reshape(-1).contiguous())
+        return derived("disco_fold", srcs, build, tuple(float(bn.eps) for _, bn in pairs))
+
+    def _ego_term(self, x0, w1e, b1):
+        """E0 = W1e x_0 + b1 [128, H, W]: heal_conv1x1 on NCHW (heal_linear on the token-major copy when H * W % 4)."""
+        C, H, W = (int(v) for v in x0.shape)
+        if (H * W) % 4 == 0:
+            return ops.conv1x1(x0.unsqueeze(0), w1e, b1)[0]
+        y = ops.linear(x0.reshape(C, H * W).t().contiguous(), w1e.view(-1, C), b1)
+        return y.t().contiguous().view(-1, H, W)
+
+    def fuse_scene(self, feats, rows, f64, return_scores=False):
+        """feats [n, C, H, W] (one scene), rows [n, 2, 3] the affine rows t[0, :n] -> [C, H, W] (and the logits [n, H, W])."""
+        feats = feats.contiguous()
+        if feats.shape[0] == 1 and not return_scores:       # (3)
+            return ops.disco_fuse(feats, rows, f64, None, None, None, None, None, None, None, None)
+        w1n, w1e, b1, w2, b2, w3, b3, w4, b4 = self._weights()
+        e0 = self._ego_term(feats[0], w1e, b1)               # (2)
+        return ops.disco_fuse(feats, rows, f64, e0, w1n, w2, b2, w3, b3, w4, b4, return_scores=return_scores)
+
+    def forward(self, x, record_len, affine_matrix):
+        lens = record_len_to_list(record_len)
+        if not self.fused_ok(x, lens):
+            return self.forward_torch(x, record_len, affine_matrix)
+        aff, f64 = _host_affine(affine_matrix)
+        out = []
+        for b, feats in enumerate(regroup(x, lens)):
+            n = feats.shape[0]
+            out.append(self.fuse_scene(feats, aff[b][0, :n], f64))
+        return torch.stack(out)
 
 
 class V2VNetFusion(nn.Module):
@@ -443,8 +539,8 @@ def fuse_levels(fusion_net, feature_list, record_len, affine_matrix):
 
 
 def build_fusion(args):
-    """The single-scale fusion operator a model YAML names (`fusion_method`: max | att | v2xvit | cobevt | v2vnet; the other methods of
-    fusion_in_one.py belong to papers outside the hot-path scope)."""
+    """The single-scale fusion operator a model YAML names (`fusion_method`: max | att | v2xvit | cobevt | v2vnet | disconet; where2comm and
+    who2com, which no YAML file selects, are outside the hot-path scope)."""
     method = args["fusion_method"]
     if method == "max":
         return MaxFusion()
@@ -456,4 +552,7 @@ def build_fusion(args):
         return CoBEVT(args["cobevt"])
     if method == "v2vnet":
         return V2VNetFusion(args["v2vnet"])
-    raise NotImplementedError(f"fusion_method '{method}' is outside the hot-path scope (SURVEY 2, row 2)")
+    if method == "disconet":
+        return DiscoFusion(args["disconet"]["feat_dim"])
+    raise NotImplementedError(f"fusion_method '{method}' is outside the hot-path scope (SURVEY 2, row 2): max, att, v2xvit, cobevt, "
+                              "v2vnet and disconet are built")

@@ -1,6 +1,6 @@
 """Old-style intermediate-fusion PointPillars: host mirror of
 opencood/models/point_pillar_baseline.py:16-135.  fusion_method max / att / v2xvit (the fusion modules on the hot
-path); disconet / v2vnet are outside the scope and raise."""
+path); the other methods `build_fusion` knows (cobevt / v2vnet / disconet) construct here too."""
 from heal_amd.opencood.models.fuse_modules.fusion_in_one import build_fusion
 from heal_amd.opencood.models.point_pillar import _PillarDetector
 from heal_amd.opencood.models.sub_modules.naive_compress import NaiveCompressor

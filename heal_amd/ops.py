@@ -685,6 +685,63 @@ def warp_att_fuse_levels(feats_list, affine_rows, grid_f64=True, mode="att", sqr
     return outs
 
 
+DISCO_MAX_AGENTS = 8
+DISCO_WIDTHS = (128, 32, 8)        # PixelWeightLayer: 2C -> 128 -> 32 -> 8 -> 1
+
+
+def disco_fuse(feats, affine_rows, grid_f64, e0, w1n_frag, w2, b2, w3, b3, w4, b4, return_scores=False):
+    """DiscoNet's fusion of one scene in ONE launch (heal_disco_fuse; fusion_in_one.py:153-201): every agent warped into the ego
+    frame, one logit per (agent, pixel) from the PixelWeightLayer over cat(warped neighbour, unwarped ego), softmax over agents,
+    weighted sum.  BatchNorm folded by the caller, layer 1 split by input half:
+    feats [n,C,H,W] fp32 (1..8 agents, C % 4 == 0), affine_rows [n,2,3] (host array or CUDA tensor read at run time),
+    e0 [128,H,W] = W1e x_0 + b1, w1n_frag = mfma_a_fragments(W1n [128,C]) [8,C/4,64], w2 [32,128], b2 [32], w3 [8,32], b3 [8],
+    w4 [8], b4 [1] -> out [C,H,W], or (out, scores [n,H,W] post-ReLU logits) with return_scores."""
+    who = "disco_fuse"
+    feats = _need(feats, torch.float32, "feats")
+    if feats.dim() != 4:
+        raise _capi.HealAmdError(f"{who}: feats must be [n, C, H, W], got {tuple(feats.shape)}")
+    n, C, H, W = (int(v) for v in feats.shape)
+    if not 1 <= n <= DISCO_MAX_AGENTS:
+        raise _capi.HealAmdError(f"{who}: 1..{DISCO_MAX_AGENTS} agents per scene (got {n})")
+    if C % 4 or C < 4:
+        raise _capi.HealAmdError(f"{who}: C must be a positive multiple of the MFMA k-step 4 (got {C})")
+    m1, m2, m3 = DISCO_WIDTHS
+    if n == 1 and not return_scores and all(t is None for t in (e0, w1n_frag, w2, b2, w3, b3, w4, b4)):
+        # the softmax of one logit is exactly 1: the warped map, no PixelWeightLayer operands
+        out = torch.empty((C, H, W), dtype=torch.float32, device=feats.device)
+        a, ap, adev = _affine_args(affine_rows, n)
+        with _Timed(f"disco_fuse_c{C}", 2.0 * C * H * W, 8.0 * C * H * W, kernel_events=True):
+            _capi.call("heal_disco_fuse", _ptr(feats), n, C, H, W, ap, adev, int(bool(grid_f64)), *([None] * 8), _ptr(out), None,
+                       _stream())
+        return out
+    e0 = _need(e0, torch.float32, "e0")
+    if tuple(e0.shape) != (m1, H, W):
+        raise _capi.HealAmdError(f"{who}: e0 has shape {tuple(e0.shape)}, want {(m1, H, W)}")
+    w1n_frag = _need(w1n_frag, torch.float32, "w1n_frag")
+    if tuple(w1n_frag.shape) != (m1 // 16, C // 4, 64):
+        raise _capi.HealAmdError(f"{who}: w1n_frag has shape {tuple(w1n_frag.shape)}, want {(m1 // 16, C // 4, 64)} for C = {C} "
+                                 "(ops.mfma_a_fragments of the [128, C] neighbour half)")
+    w2 = _need(w2, torch.float32, "w2")
+    w3 = _need(w3, torch.float32, "w3")
+    if tuple(w2.shape) != (m2, m1) or tuple(w3.shape) != (m3, m2):
+        raise _capi.HealAmdError(f"{who}: w2 {tuple(w2.shape)} / w3 {tuple(w3.shape)}, want {(m2, m1)} / {(m3, m2)}")
+    b2 = _need_channels(b2, m2, "b2", who)
+    b3 = _need_channels(b3, m3, "b3", who)
+    w4 = _need_channels(w4, m3, "w4", who)
+    b4 = _need_channels(b4, 1, "b4", who)
+    w2_frag = _derived("disco_w2_fragments", (w2,), lambda: mfma_a_fragments(w2))
+    out = torch.empty((C, H, W), dtype=torch.float32, device=feats.device)
+    scores = torch.empty((n, H, W), dtype=torch.float32, device=feats.device) if return_scores else None
+    a, ap, adev = _affine_args(affine_rows, n)
+    flops = 2.0 * n * H * W * (m1 * C + m2 * m1 + m3 * m2 + m3) + 2.0 * n * C * H * W
+    # compulsory traffic: every agent's map once, the ego term, the fused map (and the logits when asked for)
+    nbytes = 4.0 * H * W * (n * C + m1 + C + (n if return_scores else 0))
+    with _Timed(f"disco_fuse_c{C}", flops, nbytes, kernel_events=True):
+        _capi.call("heal_disco_fuse", _ptr(feats), n, C, H, W, ap, adev, int(bool(grid_f64)), _ptr(e0), _ptr(w1n_frag),
+                   _ptr(w2_frag), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(w4), _ptr(b4), _ptr(out), _optr(scores), _stream())
+    return (out, scores) if return_scores else out
+
+
 def warp_fuse_backward(feats, occ, affine_rows, grad_out, grid_f64=True, crop=None):
     """Gradient of warp_fuse with respect to (feats, occ): grad_out [C,H,W] -> ([n,C,H,W], [n,1,H,W])."""
     feats = _need(feats, torch.float32, "feats")

@@ -24,11 +24,12 @@
 extern "C" {
 #endif
 
-#define HEAL_AMD_ABI_VERSION 10  /* 6 (round 6): + heal_pfn_pillars / heal_pillar_canvas / heal_pillar_stem_block; the measured-negative entry
+#define HEAL_AMD_ABI_VERSION 11  /* 6 (round 6): + heal_pfn_pillars / heal_pillar_canvas / heal_pillar_stem_block; the measured-negative entry
                                    points moved to include/heal_amd_experimental.h (HEAL_BUILD_EXPERIMENTAL=1 builds only);
                                    8: + heal_agent_window_attention / heal_agent_mean (CoBEVT fusion);
                                    9: + heal_v2v_message[_workspace] / heal_gru_zero_state (V2VNet fusion);
-                                   10: + heal_warp_att_fuse_levels (CoAlign multiscale fusion) */
+                                   10: + heal_warp_att_fuse_levels (CoAlign multiscale fusion);
+                                   11: + heal_disco_fuse (DiscoNet fusion) */
 
 int heal_abi_version(void);
 const char* heal_last_error(void);
@@ -189,6 +190,22 @@ int heal_warp_att_fuse_levels(int n_levels, const float* const* feats_host, int 
                               const int32_t* h_host, const int32_t* w_host, const float* sqrt_dim_host,
                               const double* affine_host, const double* affine_dev, int grid_f64, int mode,
                               float* const* out_host, void* stream);
+
+/* heal_disco_fuse: DiscoNet's fusion of one scene (fusion_in_one.py:153-201, DiscoFusion.forward, with the PixelWeightLayer of
+ *   fuse_modules/disco_fuse.py) in ONE launch.  Per ego pixel: x_j = warp_affine_simple(feats[j], row j) for j = 0 .. n_agents-1,
+ *   l_j = PixelWeightLayer(cat(x_j, feats[0])) (ReLU(bn(conv1x1)) 2C -> 128 -> 32 -> 8, ReLU(conv1x1 8 -> 1)), p = softmax_j(l_j),
+ *   out = sum_j p_j x_j.  Inference BatchNorm is folded into the convolutions by the caller; layer 1 is split by input half:
+ *   e0 [128, H, W] = W1e feats[0] + b1 (the unwarped ego term, one heal_conv1x1), w1n_frag [8, C/4, 64] the neighbour half W1n
+ *   [128, C] in MFMA 16x16x4 A-fragment order (frag[mt][ks][lane] = W[mt*16 + (lane & 15)][ks*4 + (lane >> 4)]), w2_frag [2, 32, 64]
+ *   the folded conv1_2 [32, 128] in the same order, b2 [32], w3 [8, 32], b3 [8], w4 [8], b4 [1].  feats [n_agents, C, H, W],
+ *   out [C, H, W]; scores [n_agents, H, W] receives the post-ReLU logits when not NULL.  Samples outside a map are zeros and take
+ *   part in the softmax.  With one agent and scores NULL the layer is skipped (weight exactly 1) and its operands may be NULL.
+ *   C % 4 == 0, any H, W, 1..8 agents; affine rows as heal_warp_fuse (host, or device memory read at run time); sampling
+ *   arithmetic as heal_warp_fuse.  fp32 on v_mfma_f32_16x16x4_f32; no atomics: repeated launches are bit-equal.                  */
+int heal_disco_fuse(const float* feats, int n_agents, int channels, int H, int W, const double* affine_host,
+                    const double* affine_dev, int grid_f64, const float* e0, const float* w1n_frag, const float* w2_frag,
+                    const float* b2, const float* w3, const float* b3, const float* w4, const float* b4, float* out,
+                    float* scores, void* stream);
 
 /* heal_warp_fuse_backward: gradient of heal_warp_fuse with respect to the agents' maps and occupancy logits (training; the
  *   autograd of warp_affine_simple x 2 + masked softmax + weighted sum, pyramid_fuse.py:17-63,145-162).  Arguments as
