@@ -58,6 +58,9 @@ _SIGNATURES = {
     "heal_decode_nms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                 c_float, c_float, c_float, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "heal_decode_nms_agents_workspace": (c_size_t, [c_int, c_int]),
+    "heal_decode_nms_agents": (c_int, [c_int] + [c_void_p] * 6 + [c_int, c_int, c_float, c_float, c_float, c_int] +
+                               [c_void_p] * 7 + [c_int, c_void_p, c_size_t, c_void_p]),
     "heal_quad_iou": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "heal_bev_pool_workspace": (c_size_t, [c_int] * 9),
     "heal_bev_pool": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -328,6 +331,15 @@ def guard_check(entries, what="captured graph"):
         if not private and state != "active_allocated":
             raise HealAmdError(f"{what}: {name} was captured with device address {addr:#x}, whose block is now '{state}' "
                                "(its tensor was freed: a replay would read or overwrite somebody else's memory)")
+
+
+def guard_note(name, addresses):
+    """Log device addresses that reach an entry point inside a HOST array of pointers (the *_levels / *_agents entries), which
+    call() cannot see among its arguments."""
+    if _GUARD:
+        import torch
+        if torch.cuda.is_current_stream_capturing():
+            _guard_log.extend((name, int(a)) for a in addresses if a)
 
 
 def call(name, *args):

@@ -17,6 +17,9 @@
 //   k_nms_mask      64x64 tiles of the upper-triangular suppression bit matrix; fp64 convex clip with the polygons in LDS
 //   k_nms_reduce    the matrix copied to LDS; one wave resolves each 64-row diagonal tile with a scalar bit chain and ORs the
 //                   surviving rows into the removed set; ordered compaction of the output by the whole block
+// Late fusion (heal_decode_nms_agents; voxel_postprocessor.py:277-405 with several cavs) puts a multi-agent front end before the
+// same tail: k_decode_key_agents decodes the concatenated anchor range of all cavs, each with its own cav -> ego matrix, into ONE
+// candidate list (composite = score key | POOLED index), and k_rank_prepare re-decodes the top-k through the agent table.
 #include <string.h>
 #include "prims.h"
 #include "../../include/heal_amd.h"
@@ -111,6 +114,16 @@ __device__ __forceinline__ void decode_anchor(const float* __restrict__ cls, con
 // (score key << 32 | anchor index; one wave-aggregated atomic per wave): all composites are distinct, and descending
 // composite order = the reference's order (descending score, ties: larger anchor index first == stable argsort reversed), so
 // the order in which the atomics hand out slots does not matter.
+__device__ __forceinline__ void push_candidate(bool cand, unsigned long long comp, unsigned long long* __restrict__ cand_list,
+                                               int* __restrict__ n_cand) {
+    const unsigned long long m = __ballot(cand);
+    if (!m) return;
+    int base = 0;
+    if ((threadIdx.x & 63) == 0) base = atomicAdd(n_cand, __popcll(m));
+    base = __shfl(base, 0, 64);
+    if (cand) cand_list[base + __popcll(m & lanemask_lt())] = comp;
+}
+
 __global__ __launch_bounds__(256) void k_decode_key(const float* __restrict__ cls,
                                                    const float* __restrict__ reg,
                                                    const float* __restrict__ dir,
@@ -126,12 +139,81 @@ __global__ __launch_bounds__(256) void k_decode_key(const float* __restrict__ cl
         cand = b.pass;
         comp = ((unsigned long long)(__float_as_uint(b.score) - p.key_base) << 32) | (unsigned)j;
     }
-    const unsigned long long m = __ballot(cand);
-    if (!m) return;
-    int base = 0;
-    if ((threadIdx.x & 63) == 0) base = atomicAdd(n_cand, __popcll(m));
-    base = __shfl(base, 0, 64);
-    if (cand) cand_list[base + __popcll(m & lanemask_lt())] = comp;
+    push_candidate(cand, comp, cand_list, n_cand);
+}
+
+// ---- late fusion: the agents of one scene ---------------------------------------------------------------------------
+// Agent k's maps, anchor table and place in the pooled anchor range; the table travels by value in the launch arguments.
+constexpr int DEC_MAX_AGENTS = 8;
+struct AgentDesc {
+    const float *cls, *reg, *dir, *anchors;
+    int H, W;
+    int off;   // pooled index of this agent's anchor 0 (sum of the earlier agents' H * W * A)
+    int blk;   // first block of this agent in k_decode_key_agents (every agent starts a block)
+};
+struct AgentTable {
+    AgentDesc a[DEC_MAX_AGENTS];
+    float tfm[DEC_MAX_AGENTS][12];   // rows 0..2 of the cav -> ego matrices given on the host ...
+    const float* tfm_dev;            // ... or [n_agents,4,4] in device memory, read at run time (NULL: the table above)
+    int n_agents;
+
+    // agent k's descriptor and the decode parameters with ITS map size and matrix; the entry is selected by comparison (a
+    // dynamically indexed by-value table would be copied to scratch memory)
+    __device__ __forceinline__ void agent(int k, const DecodeParams& shared, AgentDesc& d, DecodeParams& q) const {
+        q = shared;
+        d = a[0];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) q.tfm[i] = tfm[0][i];
+#pragma unroll
+        for (int u = 1; u < DEC_MAX_AGENTS; ++u) {
+            if (u == k) {
+                d = a[u];
+#pragma unroll
+                for (int i = 0; i < 12; ++i) q.tfm[i] = tfm[u][i];
+            }
+        }
+        if (tfm_dev != nullptr) {
+#pragma unroll
+            for (int i = 0; i < 12; ++i) q.tfm[i] = tfm_dev[(size_t)k * 16 + i];
+        }
+        q.H = d.H; q.W = d.W;
+    }
+};
+// The same table in device memory, matrices resolved: the first block of every agent writes its row, and k_rank_prepare -- where
+// the agent differs from lane to lane -- indexes it there.
+struct AgentRow {
+    AgentDesc d;
+    float tfm[12];
+};
+
+// k_decode_key over the concatenated anchor range of all agents in one launch.  Every agent starts a block, so the agent is
+// uniform per block (found from the block offsets of the table).  Composite = score key << 32 | pooled index: descending
+// composite order is the pooled order of the reference (all cavs' candidates stacked in cav order, descending score), exact ties
+// larger pooled index first -- later cav, larger anchor -- as box_utils.nms_rotated orders them.
+__global__ __launch_bounds__(256) void k_decode_key_agents(AgentTable t, DecodeParams p, AgentRow* __restrict__ rows,
+                                                          unsigned long long* __restrict__ cand_list,
+                                                          int* __restrict__ n_cand) {
+    int k = 0;
+#pragma unroll
+    for (int u = 1; u < DEC_MAX_AGENTS; ++u) k += (u < t.n_agents && (int)blockIdx.x >= t.a[u].blk) ? 1 : 0;
+    AgentDesc d;
+    DecodeParams q;
+    t.agent(k, p, d, q);
+    if ((int)blockIdx.x == d.blk && threadIdx.x == 0) {
+        rows[k].d = d;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) rows[k].tfm[i] = q.tfm[i];
+    }
+    const int j = ((int)blockIdx.x - d.blk) * 256 + threadIdx.x;
+    bool cand = false;
+    unsigned long long comp = 0ull;
+    if (j < d.H * d.W * q.A) {
+        Box3D b;
+        decode_anchor(d.cls, d.reg, d.dir, d.anchors, q, j, false, b);
+        cand = b.pass;
+        comp = ((unsigned long long)(__float_as_uint(b.score) - q.key_base) << 32) | (unsigned)(d.off + j);
+    }
+    push_candidate(cand, comp, cand_list, n_cand);
 }
 
 // Fallback for more than TOPK_CAP candidates (every anchor above the threshold: not a frame a detector produces): ONE block finds
@@ -322,11 +404,34 @@ __device__ __forceinline__ void decode_slot(const float* __restrict__ cls, const
 // a few hundred in practice) into LDS, four threads count a quarter of it each for one candidate, and the candidate is decoded
 // straight into slot `rank` of the top-k buffers -- no sort, no `sel` list, no single-block kernel on the critical path
 // (k_topk_sort 12 us + k_nms_prepare 5 us before).  More than TOPK_CAP candidates: block 0 alone runs topk_select_sort and decodes.
+// Src says where the candidate with index j (the low word of its composite) comes from: OneAgent -- j is an anchor of the one
+// score map (heal_decode_nms); PooledAgents -- j is a pooled index, resolved through the agent table (heal_decode_nms_agents).
+struct OneAgent {
+    const float *cls, *reg, *dir, *anchors;
+    DecodeParams p;
+    __device__ __forceinline__ void slot(int j, int r, const NmsBufs& nb) const { decode_slot(cls, reg, dir, anchors, p, j, r, nb); }
+};
+struct PooledAgents {
+    const AgentRow* rows;   // [n_agents], written by k_decode_key_agents
+    int n_agents;
+    int* slot_agent;        // [top] source agent of the box in slot r of the top-k buffers, or NULL
+    DecodeParams p;
+    __device__ __forceinline__ void slot(int j, int r, const NmsBufs& nb) const {
+        int k = 0;
+        for (int u = 1; u < n_agents; ++u) k += j >= rows[u].d.off ? 1 : 0;
+        const AgentDesc d = rows[k].d;
+        DecodeParams q = p;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) q.tfm[i] = rows[k].tfm[i];
+        q.H = d.H; q.W = d.W;
+        decode_slot(d.cls, d.reg, d.dir, d.anchors, q, j - d.off, r, nb);
+        if (slot_agent != nullptr) slot_agent[r] = k;
+    }
+};
+
 constexpr int RANK_PER_BLOCK = TOPK_THREADS / 4;
-__global__ __launch_bounds__(TOPK_THREADS) void k_rank_prepare(const float* __restrict__ cls, const float* __restrict__ reg,
-                                                              const float* __restrict__ dir,
-                                                              const float* __restrict__ anchors, DecodeParams p, int n,
-                                                              const unsigned long long* __restrict__ cand_list, int top,
+template <class Src>
+__global__ __launch_bounds__(TOPK_THREADS) void k_rank_prepare(Src src, const unsigned long long* __restrict__ cand_list, int top,
                                                               NmsBufs nb) {
     __shared__ unsigned long long sc[TOPK_CAP];
     __shared__ int hist[256];
@@ -350,10 +455,10 @@ __global__ __launch_bounds__(TOPK_THREADS) void k_rank_prepare(const float* __re
         if (blockIdx.x != 0) return;
         topk_select_sort(cand_list, N, top, sc, hist, &s_prefix, &s_need, &s_count);
         for (int rr = threadIdx.x; rr < min(N, top); rr += TOPK_THREADS)
-            decode_slot(cls, reg, dir, anchors, p, (int)(unsigned)(sc[rr] & 0xFFFFFFFFull), rr, nb);
+            src.slot((int)(unsigned)(sc[rr] & 0xFFFFFFFFull), rr, nb);
         return;
     }
-    if (r >= 0) decode_slot(cls, reg, dir, anchors, p, j, r, nb);
+    if (r >= 0) src.slot(j, r, nb);
 }
 
 // One 64x64 tile of the upper-triangular suppression bit matrix per block (8 waves).  Phase 1: all 4096 bounding-box tests
@@ -435,11 +540,14 @@ __global__ __launch_bounds__(64 * NMS_SPLIT) void k_nms_mask(NmsBufs nb, int top
 //     has been looked at -- the tile is strictly upper triangular -- so alive = valid & ~set afterwards);
 // (one wave doing a dependent vector chain per candidate + 64 predicated LDS reads per block and lane: 20-27 us for 600
 // candidates).  The survivors inside gt_range are then compacted in pick order by the whole block.
+// AGENTS (late fusion): out_agent[pos] = slot_agent[row] of the kept boxes as well; the single-agent instantiation carries none of it.
 constexpr int NMS_RED_THREADS = 1024, NMS_RED_MAXK = 1088;
+template <bool AGENTS>
 __global__ __launch_bounds__(NMS_RED_THREADS) void k_nms_reduce(NmsBufs nb, const unsigned long long* __restrict__ diag,
                                                                int top, int words, float* __restrict__ out_corners,
                                                                float* __restrict__ out_scores, int* __restrict__ out_count,
-                                                               int max_out) {
+                                                               int max_out, const int* __restrict__ slot_agent,
+                                                               int* __restrict__ out_agent) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long smask[];  // [K][W], upper-triangular tiles only
     __shared__ unsigned long long keep_bits[NMS_RED_MAXK / 64];
     __shared__ short s_row[NMS_RED_MAXK];   // pick-order list of the surviving rows inside gt_range
@@ -533,6 +641,10 @@ __global__ __launch_bounds__(NMS_RED_THREADS) void k_nms_reduce(NmsBufs nb, cons
             }
         }
     }
+    if constexpr (AGENTS) {
+        if (out_agent != nullptr)
+            for (int pos = threadIdx.x; pos < s_kept; pos += NMS_RED_THREADS) out_agent[pos] = slot_agent[s_row[pos]];
+    }
 }
 
 __global__ __launch_bounds__(256) void k_quad_iou(const float* __restrict__ a, int n,
@@ -551,7 +663,8 @@ static uint32_t f2u(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 
 struct DecWs {
     unsigned long long* cand;   // [n] candidate composites (score key << 32 | anchor index)
-    uint32_t* sel;              // [top] anchor indices of the top candidates, descending
+    uint32_t* sel;              // [top] agents entry: the source agent of each top-k slot, as int (PooledAgents::slot_agent);
+                                //       the single-agent entry leaves it unused (its workspace layout stays as it was)
     NmsBufs nb;
 };
 
@@ -580,6 +693,46 @@ extern "C" size_t heal_decode_nms_workspace(int anchors_total, int nms_top) {
     return a.off + 256;
 }
 
+namespace heal {
+// keys are bits(score) - key_base: candidates have a sigmoid score in (thr, 1], so bits(score) > bits(thr) for thr > 0; for
+// thr <= 0 a zero score (logit -inf) would collide with the "not a candidate" key 0 -- shift by one in that case
+static void fill_shared_params(DecodeParams& p, int anchor_num, int num_bins, float score_thr, float dir_offset,
+                               const float* gt_range_host) {
+    p.H = 0; p.W = 0; p.A = anchor_num; p.num_bins = num_bins;
+    p.score_thr = score_thr; p.dir_offset = dir_offset;
+    p.period = (float)(2.0 * 3.141592653589793 / (double)(num_bins > 0 ? num_bins : 1));
+    p.two_pi = (float)(2.0 * 3.141592653589793);
+    for (int k = 0; k < 16; ++k) p.tfm[k] = 0.f;
+    for (int k = 0; k < 6; ++k) p.gt_range[k] = gt_range_host[k];
+    p.key_base = score_thr > 0.f ? f2u(score_thr) : 0xFFFFFFFFu;   // bits - (-1) = bits + 1
+}
+
+// k_nms_mask + k_nms_reduce over the top-k buffers that k_rank_prepare filled
+static int launch_nms_tail(const DecWs& w, int nms_top, float nms_thr, float* out_corners, float* out_scores, int32_t* out_count,
+                           int max_out, int32_t* out_agent, bool agents, hipStream_t s) {
+    const int words = ceil_div(nms_top, 64);
+    const size_t reduce_lds = (size_t)words * 64 * words * sizeof(unsigned long long);
+    HEAL_REQUIRE(reduce_lds <= 148 * 1024 && nms_top <= NMS_RED_MAXK,
+                 "decode_nms: nms_top=%d needs %zu B of LDS (limit 148 KB; use <= 1088)", nms_top, reduce_lds);
+    static bool attr_set = false;
+    if (!attr_set) {
+        HEAL_HIP(hipFuncSetAttribute((const void*)k_nms_reduce<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 148 * 1024));
+        HEAL_HIP(hipFuncSetAttribute((const void*)k_nms_reduce<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 148 * 1024));
+        HEAL_HIP(hipFuncSetAttribute((const void*)k_nms_mask, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NMS_POLY_LDS));
+        attr_set = true;
+    }
+    k_nms_mask<<<dim3(words, words), 64 * NMS_SPLIT, NMS_POLY_LDS, s>>>(w.nb, nms_top, words, nms_thr);
+    if (agents)
+        k_nms_reduce<true><<<1, NMS_RED_THREADS, reduce_lds, s>>>(w.nb, w.nb.diag, nms_top, words, out_corners, out_scores,
+                                                                  out_count, max_out, (const int*)w.sel, out_agent);
+    else
+        k_nms_reduce<false><<<1, NMS_RED_THREADS, reduce_lds, s>>>(w.nb, w.nb.diag, nms_top, words, out_corners, out_scores,
+                                                                   out_count, max_out, nullptr, nullptr);
+    HEAL_LAUNCH_CHECK();
+    return 0;
+}
+}  // namespace heal
+
 extern "C" int heal_decode_nms(const float* cls, const float* reg, const float* dir, const float* anchors,
                                int H, int W, int anchor_num, int num_bins, float score_thr,
                                float dir_offset, float nms_thr, int nms_top, const float* tfm_host,
@@ -597,40 +750,74 @@ extern "C" int heal_decode_nms(const float* cls, const float* reg, const float* 
     HEAL_REQUIRE(carve(a, n, nms_top, w), "decode_nms: workspace too small (%zu < %zu)", ws_bytes, a.off);
 
     DecodeParams p;
-    p.H = H; p.W = W; p.A = anchor_num; p.num_bins = num_bins;
-    p.score_thr = score_thr; p.dir_offset = dir_offset;
-    p.period = (float)(2.0 * 3.141592653589793 / (double)(num_bins > 0 ? num_bins : 1));
-    p.two_pi = (float)(2.0 * 3.141592653589793);
+    fill_shared_params(p, anchor_num, num_bins, score_thr, dir_offset, gt_range_host);
+    p.H = H; p.W = W;
     for (int k = 0; k < 16; ++k) p.tfm[k] = tfm_host[k];
-    for (int k = 0; k < 6; ++k) p.gt_range[k] = gt_range_host[k];
-    // candidates have sigmoid score in (thr, 1]; key = bits(score) - key_base >= 1
-    uint32_t key_base = 0, max_key;
-    if (score_thr > 0.f) { key_base = f2u(score_thr); max_key = f2u(1.0f) - key_base; }
-    else { key_base = 0; max_key = f2u(1.0f); }
-    // scores are > thr so bits(score) > key_base for thr > 0; for thr <= 0 a zero score (logit -inf)
-    // would collide with the "not a candidate" key 0 -- shift by one in that case
-    if (score_thr <= 0.f) { key_base = 0xFFFFFFFFu; max_key += 1; }  // bits - (-1) = bits + 1
-    p.key_base = key_base;
-    (void)max_key;
     HEAL_REQUIRE(nms_top <= TOPK_CAP, "decode_nms: nms_top exceeds the top-k capacity");
 
     HEAL_FILL(w.nb.n_cand, 0, sizeof(int), s);
     k_decode_key<<<ceil_div(n, 256), 256, 0, s>>>(cls, reg, dir, anchors, p, n, w.cand, w.nb.n_cand);
-    const int words = ceil_div(nms_top, 64);
-    k_rank_prepare<<<TOPK_CAP / RANK_PER_BLOCK, TOPK_THREADS, 0, s>>>(cls, reg, dir, anchors, p, n, w.cand, nms_top, w.nb);
-    const size_t reduce_lds = (size_t)words * 64 * words * sizeof(unsigned long long);
-    HEAL_REQUIRE(reduce_lds <= 148 * 1024 && nms_top <= NMS_RED_MAXK,
-                 "decode_nms: nms_top=%d needs %zu B of LDS (limit 148 KB; use <= 1088)", nms_top, reduce_lds);
-    static bool attr_set = false;
-    if (!attr_set) {
-        HEAL_HIP(hipFuncSetAttribute((const void*)k_nms_reduce, hipFuncAttributeMaxDynamicSharedMemorySize, 148 * 1024));
-        HEAL_HIP(hipFuncSetAttribute((const void*)k_nms_mask, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NMS_POLY_LDS));
-        attr_set = true;
+    const OneAgent src{cls, reg, dir, anchors, p};
+    k_rank_prepare<OneAgent><<<TOPK_CAP / RANK_PER_BLOCK, TOPK_THREADS, 0, s>>>(src, w.cand, nms_top, w.nb);
+    return launch_nms_tail(w, nms_top, nms_thr, out_corners, out_scores, out_count, max_out, nullptr, false, s);
+}
+
+extern "C" size_t heal_decode_nms_agents_workspace(int anchors_total, int nms_top) {
+    return heal_decode_nms_workspace(anchors_total, nms_top) + align_up(DEC_MAX_AGENTS * sizeof(AgentRow));
+}
+
+extern "C" int heal_decode_nms_agents(int n_agents, const float* const* cls_host, const float* const* reg_host,
+                                      const float* const* dir_host, const float* const* anchors_host, const int32_t* h_host,
+                                      const int32_t* w_host, int anchor_num, int num_bins, float score_thr, float dir_offset,
+                                      float nms_thr, int nms_top, const float* tfm_host, const float* tfm_dev,
+                                      const float* gt_range_host, float* out_corners, float* out_scores, int32_t* out_agent,
+                                      int32_t* out_count, int max_out, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    HEAL_REQUIRE(n_agents >= 1 && n_agents <= DEC_MAX_AGENTS, "decode_nms_agents: n_agents must be in [1,%d] (got %d)",
+                 DEC_MAX_AGENTS, n_agents);
+    HEAL_REQUIRE(cls_host && reg_host && anchors_host && h_host && w_host && gt_range_host && out_corners && out_scores &&
+                 out_count && ws, "decode_nms_agents: null pointer");
+    HEAL_REQUIRE((tfm_host != nullptr) != (tfm_dev != nullptr),
+                 "decode_nms_agents: exactly one of tfm_host / tfm_dev must be given");
+    HEAL_REQUIRE(anchor_num >= 1, "decode_nms_agents: bad shape");
+    HEAL_REQUIRE(nms_top >= 1 && nms_top <= 1088, "decode_nms_agents: nms_top must be in [1,1088]");
+    HEAL_REQUIRE(dir_host == nullptr || num_bins >= 1, "decode_nms_agents: num_bins must be >= 1");
+    HEAL_REQUIRE(max_out >= 1, "decode_nms_agents: max_out must be >= 1");
+    HEAL_REQUIRE(((uintptr_t)ws & 255) == 0, "decode_nms_agents: workspace must be 256-B aligned");
+    AgentTable t;
+    memset(&t, 0, sizeof(t));
+    long long total = 0;
+    int blocks = 0;
+    for (int k = 0; k < n_agents; ++k) {
+        HEAL_REQUIRE(cls_host[k] && reg_host[k] && anchors_host[k] && (dir_host == nullptr || dir_host[k]),
+                     "decode_nms_agents: null map or anchor pointer for agent %d", k);
+        HEAL_REQUIRE(h_host[k] >= 1 && w_host[k] >= 1, "decode_nms_agents: bad map size for agent %d", k);
+        const long long n_k = (long long)h_host[k] * w_host[k] * anchor_num;
+        HEAL_REQUIRE(total + n_k < (1ll << 31) - 256ll * DEC_MAX_AGENTS, "decode_nms_agents: anchors_total must be below 2^31");
+        AgentDesc& d = t.a[k];
+        d.cls = cls_host[k]; d.reg = reg_host[k]; d.dir = dir_host ? dir_host[k] : nullptr; d.anchors = anchors_host[k];
+        d.H = h_host[k]; d.W = w_host[k]; d.off = (int)total; d.blk = blocks;
+        if (tfm_host)
+            for (int i = 0; i < 12; ++i) t.tfm[k][i] = tfm_host[k * 16 + i];
+        total += n_k;
+        blocks += (int)((n_k + 255) / 256);
     }
-    k_nms_mask<<<dim3(words, words), 64 * NMS_SPLIT, NMS_POLY_LDS, s>>>(w.nb, nms_top, words, nms_thr);
-    k_nms_reduce<<<1, NMS_RED_THREADS, reduce_lds, s>>>(w.nb, w.nb.diag, nms_top, words, out_corners, out_scores, out_count, max_out);
-    HEAL_LAUNCH_CHECK();
-    return 0;
+    t.tfm_dev = tfm_dev;
+    t.n_agents = n_agents;
+    Arena a(ws, ws_bytes);
+    DecWs w;
+    const bool fits = carve(a, (int)total, nms_top, w);
+    AgentRow* rows = a.take<AgentRow>(DEC_MAX_AGENTS);
+    HEAL_REQUIRE(fits && a.ok(), "decode_nms_agents: workspace too small (%zu < %zu)", ws_bytes, a.off);
+
+    DecodeParams p;
+    fill_shared_params(p, anchor_num, num_bins, score_thr, dir_offset, gt_range_host);
+
+    HEAL_FILL(w.nb.n_cand, 0, sizeof(int), s);
+    k_decode_key_agents<<<blocks, 256, 0, s>>>(t, p, rows, w.cand, w.nb.n_cand);
+    const PooledAgents src{rows, n_agents, out_agent ? (int*)w.sel : nullptr, p};
+    k_rank_prepare<PooledAgents><<<TOPK_CAP / RANK_PER_BLOCK, TOPK_THREADS, 0, s>>>(src, w.cand, nms_top, w.nb);
+    return launch_nms_tail(w, nms_top, nms_thr, out_corners, out_scores, out_count, max_out, out_agent, true, s);
 }
 
 extern "C" int heal_quad_iou(const float* a, int n, const float* b, int m, float* iou, void* stream) {

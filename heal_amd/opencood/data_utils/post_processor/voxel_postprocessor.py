@@ -238,23 +238,78 @@ class VoxelPostprocessor:
                                                               return_mask=True)
         return torch.from_numpy(kept).to(pred.device), scores[torch.from_numpy(mask).to(pred.device)]
 
-    def _anchors_f32(self, anchor_box, device):
-        """anchors as contiguous fp32 on the device (delta_to_boxes3d does `.float()`), cached."""
+    def _anchors_f32(self, anchor_box, device, keep=1):
+        """anchors as contiguous fp32 on the device (delta_to_boxes3d does `.float()`), cached: at most `keep` tables (one for
+        the single-cav form; late fusion asks for room for every cav's own table)."""
         key = (anchor_box.data_ptr() if isinstance(anchor_box, torch.Tensor) else id(anchor_box), str(device))
         hit = self._anchor_cache.get(key)
         if hit is None:
             t = anchor_box if isinstance(anchor_box, torch.Tensor) else torch.from_numpy(np.asarray(anchor_box))
             hit = (t.to(device=device, dtype=torch.float32).contiguous(), anchor_box)  # keep the source alive: key = address
-            self._anchor_cache = {k: v for k, v in self._anchor_cache.items() if isinstance(k, tuple) and k and k[0] == "label"}
+            is_label = lambda k: isinstance(k, tuple) and k and k[0] == "label"
+            if sum(1 for k in self._anchor_cache if not is_label(k)) >= keep:
+                self._anchor_cache = {k: v for k, v in self._anchor_cache.items() if is_label(k)}
             self._anchor_cache[key] = hit
         return hit[0]
 
+    @staticmethod
+    def _heads(out):
+        return (out['cls_preds'] if 'cls_preds' in out else out['psm'], out['reg_preds'] if 'reg_preds' in out else out['rm'],
+                out.get('dir_preds', out.get('dm')))
+
+    def _late_fused_ok(self, output_dict):
+        """Several cavs go to the pooled decode + NMS kernel (ops.decode_nms_agents) when every cav's maps are CUDA fp32 with
+        batch size 1 on ONE device, there is no iou_preds head and at most 8 cavs; HEAL_LATE_FUSED=0 keeps the per-cav tensor path."""
+        if os.environ.get("HEAL_LATE_FUSED", "1") == "0" or len(output_dict) > ops.DECODE_MAX_AGENTS:
+            return False
+        with_dir = device = None
+        for out in output_dict.values():
+            if 'iou_preds' in out:
+                return False
+            heads = self._heads(out)
+            if with_dir is None:
+                with_dir = heads[2] is not None
+            if (heads[2] is not None) != with_dir:
+                return False
+            for t in heads:
+                if t is None:
+                    continue
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[0] == 1):
+                    return False
+                device = t.device if device is None else device
+                if t.device != device:
+                    return False
+        return True
+
+    def _post_process_agents(self, data_dict, output_dict):
+        """Late fusion on the fused kernel: the cavs of output_dict, in order, through ONE heal_decode_nms_agents call."""
+        cls, reg, dirs, anchors, tfms = [], [], [], [], []
+        for cav_id, out in output_dict.items():
+            assert cav_id in data_dict
+            cav = data_dict[cav_id]
+            c, r, d = self._heads(out)
+            cls.append(c); reg.append(r); dirs.append(d)
+            anchors.append(self._anchors_f32(cav['anchor_box'], c.device, keep=ops.DECODE_MAX_AGENTS))
+            tfms.append(cav['transformation_matrix'])
+        on_dev = [isinstance(t, torch.Tensor) and t.is_cuda for t in tfms]
+        if all(on_dev):
+            tfms = torch.stack([t.to(torch.float32) for t in tfms])      # stays on the device: no host round trip
+        elif any(on_dev):                                                # some on each side: all to the host (this call reads the
+            tfms = [t.cpu() if d else t for t, d in zip(tfms, on_dev)]   # box count from the device at its end in any case)
+        dir_args = self.params.get('dir_args', {'dir_offset': 0.7853, 'num_bins': 2})
+        return ops.decode_nms_agents(cls, reg, None if dirs[0] is None else dirs, anchors, tfms,
+                                     self.params['target_args']['score_threshold'], dir_args['dir_offset'],
+                                     dir_args['num_bins'], self.params['nms_thresh'], self.params['gt_range'])
+
     def post_process(self, data_dict, output_dict):
-        """-> (pred_box3d [K,8,3], scores [K]) or (None, None).  Intermediate / single-agent form:
-        one entry (the ego) in output_dict; batch size 1 (voxel_postprocessor.py:314)."""
+        """-> (pred_box3d [K,8,3], scores [K]) or (None, None).  Intermediate / single-agent form: one entry (the ego) in
+        output_dict; batch size 1 (voxel_postprocessor.py:314).  Late fusion: several cavs, pooled before ONE rotated NMS
+        (_post_process_agents on the fused kernel, _post_process_multi as the fallback and with HEAL_LATE_FUSED=0)."""
         if self.params['order'] != 'hwl':
             raise NotImplementedError("the decode kernel implements order 'hwl' (PointPillars / HEAL configs)")
         if len(output_dict) != 1:
+            if self._late_fused_ok(output_dict):
+                return self._post_process_agents(data_dict, output_dict)
             return self._post_process_multi(data_dict, output_dict)
         cav_id = next(iter(output_dict.keys()))
         out = output_dict[cav_id]

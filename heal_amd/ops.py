@@ -853,6 +853,115 @@ def decode_nms(cls, reg, dirp, anchors, score_thr, dir_offset, num_bins, nms_thr
     return out_c[:k], out_s[:k]
 
 
+DECODE_MAX_AGENTS = 8
+
+
+def decode_nms_agents(cls_list, reg_list, dir_list, anchors_list, tfms, score_thr, dir_offset, num_bins, nms_thr, gt_range,
+                      nms_top=1000, sync=True, want_agent=False):
+    """K8 for late fusion (heal_decode_nms_agents; voxel_postprocessor.py:277-405 with several cavs): the candidates of every
+    agent decoded with its own cav -> ego matrix, pooled in agent order, one rotated NMS over the top `nms_top` of the pool.
+    Per agent k: cls [1,A,H_k,W_k] or [A,H_k,W_k], reg [.,7A,H_k,W_k], dir [.,bins*A,H_k,W_k] (dir_list None: no direction
+    head), anchors [H_k,W_k,A,7], all f32 cuda; contiguous views into a batched head output are read in place.
+    tfms: an [n,4,4] CUDA tensor (read on the device at run time: a captured graph follows the loaded frame's poses; f64 is
+    cast on the device), a list of n CUDA 4x4 tensors (stacked on the device), or a host array / list of n 4x4 matrices; a list
+    that mixes the two is refused.
+    -> sync=True: (corners [K,8,3], scores [K]) or (None, None); sync=False: the full-capacity buffers and the device count,
+    no host synchronisation.  want_agent appends the source agent of every kept box (int32)."""
+    who = "decode_nms_agents"
+    n = len(cls_list)
+    if not 1 <= n <= DECODE_MAX_AGENTS:
+        raise _capi.HealAmdError(f"{who}: 1..{DECODE_MAX_AGENTS} agents per scene (got {n})")
+    if len(reg_list) != n or len(anchors_list) != n or (dir_list is not None and len(dir_list) != n):
+        raise _capi.HealAmdError(f"{who}: {n} score maps, {len(reg_list)} regression maps, "
+                                 f"{'no' if dir_list is None else len(dir_list)} direction maps, {len(anchors_list)} anchor tables")
+    if tfms is None:
+        raise _capi.HealAmdError(f"{who}: tfms is required (an [n,4,4] CUDA tensor or {n} host matrices)")
+
+    def maps(t, name, k):
+        t = _need(t, torch.float32, f"{name}[{k}]")
+        if t.dim() == 4:
+            if t.shape[0] != 1:
+                raise _capi.HealAmdError(f"{who}: batch size must be 1 per agent (voxel_postprocessor.py:314)")
+            t = t[0]
+        if t.dim() != 3:
+            raise _capi.HealAmdError(f"{who}: {name}[{k}] must be [1,C,H,W] or [C,H,W], got {tuple(t.shape)}")
+        return t
+
+    cls_list = [maps(t, "cls_preds", k) for k, t in enumerate(cls_list)]
+    reg_list = [maps(t, "reg_preds", k) for k, t in enumerate(reg_list)]
+    if dir_list is not None:
+        dir_list = [maps(t, "dir_preds", k) for k, t in enumerate(dir_list)]
+    anchors_list = [_need(a, torch.float32, f"anchors[{k}]") for k, a in enumerate(anchors_list)]
+    A = int(cls_list[0].shape[0])
+    hs, ws_, total = [], [], 0
+    for k in range(n):
+        Ak, H, W = (int(v) for v in cls_list[k].shape)
+        if Ak != A:
+            raise _capi.HealAmdError(f"{who}: agent {k} has {Ak} anchors per cell, agent 0 has {A}")
+        if tuple(reg_list[k].shape) != (7 * A, H, W) or (dir_list is not None
+                                                          and tuple(dir_list[k].shape) != (int(num_bins) * A, H, W)):
+            raise _capi.HealAmdError(f"{who}: agent {k}: regression / direction maps do not match the {A} x {H} x {W} score map")
+        if anchors_list[k].numel() != H * W * A * 7:
+            raise _capi.HealAmdError(f"{who}: anchors {tuple(anchors_list[k].shape)} of agent {k} do not match the {A} x {H} x {W} "
+                                     "score map (anchor_args.feature_stride of the YAML vs. the model's output stride)")
+        hs.append(H)
+        ws_.append(W)
+        total += A * H * W
+    if total >= 2 ** 31 - 256 * DECODE_MAX_AGENTS:
+        raise _capi.HealAmdError(f"{who}: {total} pooled anchors (must be below 2^31)")
+    dev = cls_list[0].device
+    null = ctypes.c_void_p(0)
+    if isinstance(tfms, (list, tuple)):
+        on_dev = [isinstance(m, torch.Tensor) and m.is_cuda for m in tfms]
+        if tfms and all(on_dev):
+            tfms = torch.stack([m.detach() for m in tfms])
+        elif any(on_dev):      # copying some of them to the host would synchronise, which sync=False promises not to do
+            raise _capi.HealAmdError(f"{who}: tfms mixes CUDA tensors and host matrices; give all {n} on one side")
+    if isinstance(tfms, torch.Tensor) and tfms.is_cuda:
+        t = tfms.detach()
+        if tuple(t.shape) != (n, 4, 4):
+            raise _capi.HealAmdError(f"{who}: tfms must be [{n},4,4], got {tuple(tfms.shape)}")
+        t = t.to(torch.float32).contiguous()
+        t_host, t_dev = null, _ptr(t)
+    else:
+        if isinstance(tfms, (list, tuple)):
+            tfms = [m.detach().numpy() if isinstance(m, torch.Tensor) else np.asarray(m) for m in tfms]
+        elif isinstance(tfms, torch.Tensor):
+            tfms = tfms.detach().numpy()
+        t = np.ascontiguousarray(np.asarray(tfms, dtype=np.float32))
+        if t.shape != (n, 4, 4):
+            raise _capi.HealAmdError(f"{who}: tfms must be {n} 4x4 matrices, got {t.shape}")
+        t_host, t_dev = t.ctypes.data_as(ctypes.c_void_p), null
+    out_c = torch.empty((nms_top, 8, 3), dtype=torch.float32, device=dev)
+    out_s = torch.empty((nms_top,), dtype=torch.float32, device=dev)
+    out_a = torch.empty((nms_top,), dtype=torch.int32, device=dev) if want_agent else None
+    out_n = torch.zeros((1,), dtype=torch.int32, device=dev)
+    nbytes = _capi.query("heal_decode_nms_agents_workspace", total, int(nms_top))
+    ws = _workspace("decode_nms_agents", nbytes, dev)
+    g = _host_array([float(v) for v in gt_range], ctypes.c_float)
+
+    def ptrs(ts):
+        return _host_array([x.data_ptr() for x in ts], ctypes.c_void_p)
+
+    _capi.guard_note("heal_decode_nms_agents", [x.data_ptr() for ts in (cls_list, reg_list, dir_list or [], anchors_list) for x in ts])
+    with _Timed("decode_nms_agents"):
+        _capi.call("heal_decode_nms_agents", n, ptrs(cls_list), ptrs(reg_list), ptrs(dir_list) if dir_list is not None else null,
+                   ptrs(anchors_list), _host_array(hs, ctypes.c_int32), _host_array(ws_, ctypes.c_int32), A, int(num_bins),
+                   float(score_thr), float(dir_offset), float(nms_thr), int(nms_top), t_host, t_dev, g,
+                   _ptr(out_c), _ptr(out_s), _ptr(out_a), _ptr(out_n), int(nms_top), _ptr(ws), ws.numel(), _stream())
+    _remember("decode_nms_agents", lambda: decode_nms_agents(cls_list, reg_list, dir_list, anchors_list, tfms, score_thr, dir_offset,
+                                                             num_bins, nms_thr, gt_range, nms_top, sync=False,
+                                                             want_agent=want_agent))
+    if not sync:
+        return (out_c, out_s, out_n, out_a) if want_agent else (out_c, out_s, out_n)
+    k = int(out_n.item())
+    if _SPARSE_CHECKS and not torch.cuda.is_current_stream_capturing():
+        verify_sparse_capacity()   # as decode_nms: the first host sync after a no-sync SECOND encoder
+    if k == 0:
+        return (None, None, None) if want_agent else (None, None)
+    return (out_c[:k], out_s[:k], out_a[:k]) if want_agent else (out_c[:k], out_s[:k])
+
+
 def quad_iou(a, b):
     """Pairwise rotated IoU of quads a [n,4,2], b [m,4,2] (f32 cuda) -> [n,m]."""
     a = _need(a, torch.float32, "a")

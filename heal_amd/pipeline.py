@@ -239,6 +239,18 @@ class ScenePipeline:
         batch = {"ego": {"transformation_matrix": self.tfm, "anchor_box": self.anchor_box}}
         return self.post.post_process(batch, {"ego": out})
 
+    def _device_step(self, inputs):
+        """The whole step on `inputs` (a Scene or StaticInputs) without a host synchronisation -> the full-capacity output
+        buffers and the device box count: what capture_slot() records."""
+        from heal_amd import ops
+        dir_args = self.post.params.get("dir_args", {"dir_offset": 0.7853, "num_bins": 2})
+        anchors = self.post._anchors_f32(self.anchor_box, self.device)
+        out = self.model(inputs.model_input())
+        return ops.decode_nms(out["cls_preds"], out["reg_preds"], out.get("dir_preds"), anchors,
+                              self.post.params["target_args"]["score_threshold"], dir_args["dir_offset"],
+                              dir_args["num_bins"], self.post.params["nms_thresh"],
+                              np.eye(4, dtype=np.float32), self.post.params["gt_range"], sync=False)
+
     # ---- hipGraph replay ---------------------------------------------------------------------------
     # A scene is ~400 launches, most of them a few microseconds long: launch-bound on the host.  With
     # static shapes (inputs resident in fixed buffers; variable-size clouds can be padded with NaN
@@ -251,16 +263,10 @@ class ScenePipeline:
         stream -> a `_Slot` (buffers, graph, output buffers, stream).  Several slots of one pipeline share the model's
         parameters and nothing else: scratch buffers are per stream (ops._workspace) and so are the modality side streams."""
         from heal_amd import ops
-        dir_args = self.post.params.get("dir_args", {"dir_offset": 0.7853, "num_bins": 2})
-        anchors = self.post._anchors_f32(self.anchor_box, self.device)
         static = StaticInputs(scene, slack)
 
         def body():
-            out = self.model(static.model_input())
-            return ops.decode_nms(out["cls_preds"], out["reg_preds"], out.get("dir_preds"), anchors,
-                                  self.post.params["target_args"]["score_threshold"], dir_args["dir_offset"],
-                                  dir_args["num_bins"], self.post.params["nms_thresh"],
-                                  np.eye(4, dtype=np.float32), self.post.params["gt_range"], sync=False)
+            return self._device_step(static)
 
         # Capture on the stream the caller already runs on (it must be a non-default stream): MIOpen keeps
         # its solver choices per stream, and the first convolutions on a fresh stream trigger a search that
@@ -315,6 +321,67 @@ class ScenePipeline:
         if k == 0:
             return None, None
         return corners[:k], scores[:k]
+
+
+class LateScenePipeline(ScenePipeline):
+    """Late fusion of one scene (opencood/tools/inference_utils.py:18-47 inference_late_fusion + VoxelPostprocessor.post_process
+    with every cav in output_dict) for a `heter_model_late` model: the scene's agents grouped by modality, ONE batched forward
+    of the single-agent detector per modality, the head outputs sliced per agent (views), the cav -> ego matrices
+    `pairwise_t_matrix[0, :n, 0]`, and one pooled decode + NMS (ops.decode_nms_agents).  step / capture / capture_slot / replay
+    keep ScenePipeline's contracts; with StaticInputs the matrices stay on the device, so a replayed graph follows the poses of
+    the frame that was loaded.  Every agent is decoded on the pipeline's one anchor table."""
+
+    def __init__(self, hypes, device, seed=0):
+        if hypes["model"]["core_method"] != "heter_model_late":
+            raise ValueError(f"LateScenePipeline runs heter_model_late models, got {hypes['model']['core_method']}")
+        super().__init__(hypes, device, seed)
+
+    @staticmethod
+    def _groups(inputs):
+        mods = list(inputs.modalities)
+        return [(m, [a for a in range(inputs.n_agents) if mods[a] == m]) for m in sorted(set(mods))]
+
+    @torch.no_grad()
+    def forward(self, scene):
+        """Per-agent head outputs [1,C,H,W] in agent order (views into the batched outputs, one forward per modality)."""
+        per = [None] * scene.n_agents
+        for _, mine in self._groups(scene):
+            out = self.model(scene.inputs_for(mine))
+            for i, a in enumerate(mine):
+                per[a] = {k: out[k][i:i + 1] for k in ("cls_preds", "reg_preds", "dir_preds") if out.get(k) is not None}
+        return per
+
+    @torch.no_grad()
+    def calibrate_cls_bias(self, scene, target_candidates=600):
+        """About `target_candidates` candidates PER AGENT in the pool (one modality: the heads are calibrated on its batch)."""
+        groups = self._groups(scene)
+        if len(groups) != 1:
+            raise NotImplementedError("calibrate_cls_bias of a late scene: one modality (every modality has its own heads)")
+        return calibrate_heads(self.model, scene.inputs_for(groups[0][1]),
+                               self.hypes["postprocess"]["target_args"]["score_threshold"],
+                               target_candidates * scene.n_agents)
+
+    def _decode(self, inputs, sync):
+        from heal_amd import ops
+        per = self.forward(inputs)
+        n = inputs.n_agents
+        dir_args = self.post.params.get("dir_args", {"dir_offset": 0.7853, "num_bins": 2})
+        anchors = self.post._anchors_f32(self.anchor_box, self.device)
+        with_dir = all("dir_preds" in o for o in per)
+        pw = inputs.pairwise
+        tfms = pw[0, :n, 0] if isinstance(pw, torch.Tensor) else np.asarray(pw)[0, :n, 0]   # cav k -> ego
+        return ops.decode_nms_agents([o["cls_preds"] for o in per], [o["reg_preds"] for o in per],
+                                     [o["dir_preds"] for o in per] if with_dir else None, [anchors] * n, tfms,
+                                     self.post.params["target_args"]["score_threshold"], dir_args["dir_offset"],
+                                     dir_args["num_bins"], self.post.params["nms_thresh"], self.post.params["gt_range"],
+                                     sync=sync)
+
+    @torch.no_grad()
+    def step(self, scene):
+        return self._decode(scene, sync=True)
+
+    def _device_step(self, inputs):
+        return self._decode(inputs, sync=False)
 
 
 class _Slot:

@@ -117,3 +117,51 @@ def camera_rig(seed, n_cams=4, H=384, W=512):
         "post_rots": np.tile(np.eye(3), (n_cams, 1, 1)).astype(np.float32),
         "post_trans": np.zeros((n_cams, 3), np.float32),
     }
+
+
+# ---- detection-head maps for the late-fusion decode (tests, tests/golden/gen_golden_late.py, scripts/late_bench.py) ---------
+BACKGROUND = -6.0
+
+
+def make_cav(rng, anchors, tfm, n_clusters, mode="normal", density=0.8):
+    """One cav's maps (tfm: its 4x4 cav -> ego matrix).  Background everywhere; `n_clusters` 3 x 3 neighbourhoods (both
+    anchors) marked as candidates (their logits are filled from the ladder later).  mode "empty": no candidate; "filtered":
+    every candidate far too high or too long; "dense": every anchor a candidate."""
+    H, W, A = anchors.shape[:3]
+    cls = rng.uniform(BACKGROUND - 2.0, BACKGROUND + 2.0, (1, A, H, W)).astype(np.float32)
+    reg = np.zeros((1, 7 * A, H, W), np.float32)
+    dirp = np.zeros((1, 2 * A, H, W), np.float32)
+    cand = np.zeros((A, H, W), bool)
+    if mode == "dense":
+        cand[:] = True
+    elif mode != "empty":
+        for _ in range(n_clusters):
+            h0, w0 = rng.integers(1, H - 1), rng.integers(1, W - 1)
+            cand[:, h0 - 1:h0 + 2, w0 - 1:w0 + 2] |= rng.random((A, 3, 3)) < density
+    a, h, w = np.nonzero(cand)
+    d = (rng.standard_normal((len(a), 7)) * 0.2).astype(np.float32)
+    if mode == "filtered":
+        half = np.arange(len(a)) % 2 == 0
+        d[half, 2] = 4.0 + rng.uniform(0, 1, half.sum())             # z centre ~ 5 m: zmax > 1
+        d[~half, 5] = 1.2 + rng.uniform(0, 0.3, (~half).sum())       # l = 3.9 e^1.2 ~ 13 m: x_len or y_len > 6
+    for k in range(7):
+        reg[0, a * 7 + k, h, w] = d[:, k]
+    for b in range(2):
+        dirp[0, a * 2 + b, h, w] = rng.standard_normal(len(a)).astype(np.float32)
+    tfm = np.asarray(tfm, np.float32)
+    return {"cls": cls, "reg": reg, "dir": dirp, "anchors": anchors, "tfm": tfm, "_cand": cand}
+
+
+def deal_ladder(rng, cavs, lo=0.25, hi=0.95, min_step=2e-5):
+    """Distinct scores lo, lo + step, ... < hi dealt to the candidates of all cavs in random order; the step must be at least
+    `min_step` (twice the score margin the late-fusion fixtures keep)."""
+    total = sum(int(c["_cand"].sum()) for c in cavs)
+    step = (hi - lo) / total
+    assert step >= min_step, step
+    scores = lo + step * rng.permutation(total).astype(np.float64)
+    logits = np.log(scores / (1.0 - scores)).astype(np.float32)
+    off = 0
+    for c in cavs:
+        n = int(c["_cand"].sum())
+        c["cls"][0][c["_cand"]] = logits[off:off + n]
+        off += n

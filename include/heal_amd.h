@@ -24,12 +24,13 @@
 extern "C" {
 #endif
 
-#define HEAL_AMD_ABI_VERSION 11  /* 6 (round 6): + heal_pfn_pillars / heal_pillar_canvas / heal_pillar_stem_block; the measured-negative entry
+#define HEAL_AMD_ABI_VERSION 12  /* 6 (round 6): + heal_pfn_pillars / heal_pillar_canvas / heal_pillar_stem_block; the measured-negative entry
                                    points moved to include/heal_amd_experimental.h (HEAL_BUILD_EXPERIMENTAL=1 builds only);
                                    8: + heal_agent_window_attention / heal_agent_mean (CoBEVT fusion);
                                    9: + heal_v2v_message[_workspace] / heal_gru_zero_state (V2VNet fusion);
                                    10: + heal_warp_att_fuse_levels (CoAlign multiscale fusion);
-                                   11: + heal_disco_fuse (DiscoNet fusion) */
+                                   11: + heal_disco_fuse (DiscoNet fusion);
+                                   12: + heal_decode_nms_agents[_workspace] (late fusion: pooled decode + one NMS) */
 
 int heal_abi_version(void);
 const char* heal_last_error(void);
@@ -254,6 +255,30 @@ int heal_decode_nms(const float* cls, const float* reg, const float* dir, const 
                     const float* tfm_host, const float* gt_range_host,
                     float* out_corners, float* out_scores, int32_t* out_count, int max_out,
                     void* ws, size_t ws_bytes, void* stream);
+
+/* heal_decode_nms_agents: K8 for LATE fusion -- VoxelPostprocessor.post_process with several cavs in output_dict
+ *   (opencood/data_utils/post_processor/voxel_postprocessor.py:277-405, driven by inference_utils.py:18-47
+ *   inference_late_fusion): every cav's anchors are decoded, each projected with its OWN cav -> ego matrix, the candidates of
+ *   all cavs pooled in cav order, the size / z filters applied, ONE rotated NMS over the top nms_top of the pool, then the
+ *   range filter.  Agents 0 .. n_agents-1 are the entries of output_dict in order; 1..8 agents.
+ *   cls_host / reg_host / dir_host / anchors_host: HOST arrays of n_agents device pointers, agent k's maps [A,H_k,W_k],
+ *   [7A,H_k,W_k], [num_bins*A,H_k,W_k] and anchors [H_k,W_k,A,7] f32 (dir_host NULL, or every entry non-NULL); h_host / w_host
+ *   the map sizes.  anchor_num, num_bins, the thresholds and gt_range are shared (one YAML fixes them).
+ *   Poses, exactly one of: tfm_host HOST [n_agents,16] row-major 4x4, or tfm_dev DEVICE [n_agents,4,4] f32 read at run
+ *   time (a replayed HIP graph follows the poses of the frame that was loaded).
+ *   Per candidate the arithmetic is heal_decode_nms's, operation for operation; with one agent the results are bit-equal to it.
+ *   Pooled order: descending score, exact ties larger pooled index (= anchor offset of agent k + anchor index) first -- later
+ *   cav, larger anchor -- the order of box_utils.nms_rotated over the pooled list.
+ *   out_agent [max_out] i32 or NULL: the source agent of kept box i.  Other outputs as heal_decode_nms.
+ *   ws: heal_decode_nms_agents_workspace(sum_k H_k*W_k*A, nms_top) bytes.  No atomics beyond the wave-aggregated candidate
+ *   slot counter (the composites are distinct, so the slot order does not matter): repeated launches are bit-equal.       */
+size_t heal_decode_nms_agents_workspace(int anchors_total, int nms_top);
+int heal_decode_nms_agents(int n_agents, const float* const* cls_host, const float* const* reg_host,
+                           const float* const* dir_host, const float* const* anchors_host, const int32_t* h_host,
+                           const int32_t* w_host, int anchor_num, int num_bins, float score_thr, float dir_offset,
+                           float nms_thr, int nms_top, const float* tfm_host, const float* tfm_dev,
+                           const float* gt_range_host, float* out_corners, float* out_scores, int32_t* out_agent,
+                           int32_t* out_count, int max_out, void* ws, size_t ws_bytes, void* stream);
 
 /* Pairwise rotated IoU of convex quads given as 4 (x,y) fp32 corners; fp64 geometry, fp32 result.
  * Same arithmetic as the NMS above (common_utils.py:230-251 compute_iou).  a [n,4,2], b [m,4,2],
