@@ -8,7 +8,7 @@ import copy
 
 import yaml
 
-from heal_amd.opencood.hypes_yaml.yaml_utils import load_general_params
+from heal_amd.opencood.hypes_yaml.yaml_utils import load_general_params, load_point_pillar_params
 
 FULL_RANGE = [-102.4, -102.4, -3, 102.4, 102.4, 1]
 ANCHOR_YAW = [0, 90]
@@ -272,6 +272,35 @@ def oldstyle_pointpillar(fusion_method=None, lidar_range=FULL_RANGE, max_cav=5, 
     h["name"] = f"heal_amd_{core}"
     h["model"] = {"core_method": core, "args": args}
     return load_general_params(h)
+
+
+def lidar_disco_kd(lidar_range=FULL_RANGE, max_cav=5):
+    """DiscoNet with distillation (opv2v/LiDAROnly/lidar_disco.yaml): the student `point_pillar_disconet`, the early-fusion
+    teacher of `kd_flag` (same architecture arguments, as the YAML's `*model_args` alias) and `point_pillar_disconet_loss` with
+    its KD weight.  `kd_flag.teacher_path` is left empty: the YAML's points into its author's file system."""
+    h = _common(lidar_range, max_cav)
+    h["name"] = "heal_amd_opv2v_point_pillar_lidar_disconet"
+    h["train_params"]["batch_size"] = 2
+    args = {"voxel_size": [0.4, 0.4, 4], "lidar_range": list(lidar_range), "anchor_number": 2,
+            "pillar_vfe": {"use_norm": True, "with_distance": False, "use_absolute_xyz": True, "num_filters": [64]},
+            "point_pillar_scatter": {"num_features": 64},
+            "base_bev_backbone": {"layer_nums": [3, 5, 8], "layer_strides": [2, 2, 2], "num_filters": [64, 128, 256],
+                                  "upsample_strides": [1, 2, 4], "num_upsample_filter": [128, 128, 128]},
+            "shrink_header": {"kernal_size": [3], "stride": [1], "padding": [1], "dim": [256], "input_dim": 384},
+            "dir_args": copy.deepcopy(DIR_ARGS)}
+    h["model"] = {"core_method": "point_pillar_disconet", "args": args}
+    h["kd_flag"] = {"teacher_model": "point_pillar_disconet_teacher", "teacher_model_config": args,      # the YAML's alias: one dict
+                    "teacher_path": ""}
+    h["loss"] = {"core_method": "point_pillar_disconet_loss", "args": {
+        "pos_cls_weight": 2.0,
+        "cls": {"type": "SigmoidFocalLoss", "alpha": 0.25, "gamma": 2.0, "weight": 2.0},
+        "reg": {"type": "WeightedSmoothL1Loss", "sigma": 3.0, "codewise": True, "weight": 2.0},
+        "dir": {"type": "WeightedSoftmaxClassificationLoss", "weight": 0.2, "args": copy.deepcopy(DIR_ARGS)},
+        "kd": {"weight": 10000}}}
+    h["optimizer"] = {"core_method": "Adam", "lr": 0.002, "args": {"eps": 1e-10, "weight_decay": 1e-4}}
+    h["lr_scheduler"] = {"core_method": "multistep", "gamma": 0.1, "step_size": [10, 15, 40]}
+    h["yaml_parser"] = "load_point_pillar_params"
+    return load_point_pillar_params(h)
 
 
 def oldstyle_lss(encoder="EfficientNet", final_dim=(384, 512), lidar_range=FULL_RANGE, max_cav=5):

@@ -1,6 +1,6 @@
 """Model / loss discovery, checkpoint loading, optimizer set-up and host->device transfer (reference:
 opencood/tools/train_utils.py:28-102 check_missing_key + load_saved_model, :141-174 create_model, :177-210 create_loss,
-:213-274 setup_optimizer + setup_lr_schedular, :277-286 to_device)."""
+:213-274 setup_optimizer + setup_lr_schedular, :277-286 to_device; opencood/tools/train_w_kd.py:99-124 create_teacher)."""
 import glob
 import importlib
 import os
@@ -94,6 +94,34 @@ def create_loss(hypes):
         if cname.lower() == target:
             return cls(hypes['loss']['args'])
     raise ImportError(f"no class matching '{target}' in heal_amd.opencood.loss.{name}")
+
+
+def create_teacher(hypes, device=None):
+    """train_w_kd.py:99-124: the frozen teacher of a distillation recipe (`kd_flag` of LiDAROnly/lidar_disco.yaml).  The class in
+    heal_amd.opencood.models.<kd_flag.teacher_model> whose lower-cased name is that name without underscores, constructed
+    with kd_flag.teacher_model_config; kd_flag.teacher_path is loaded with strict=False (the early-fusion checkpoint has no
+    `teacher_` prefix and the same module names) when the file exists -- the reference fails on a missing file, here the
+    teacher then keeps its initial weights and says so; every parameter frozen, eval() mode, moved to `device` if given."""
+    kd = hypes['kd_flag']
+    name = kd['teacher_model']
+    lib = importlib.import_module("heal_amd.opencood.models." + name)
+    target = name.replace('_', '').lower()
+    cls = next((c for cname, c in lib.__dict__.items() if cname.lower() == target), None)
+    if cls is None:
+        raise ImportError(f"no class matching '{target}' in heal_amd.opencood.models.{name}")
+    teacher = cls(kd['teacher_model_config'])
+    path = kd.get('teacher_path')
+    if path and os.path.exists(path):
+        state = torch.load(path, map_location='cpu')
+        check_missing_key(teacher.state_dict(), state)
+        teacher.load_state_dict(state, strict=False)
+    else:
+        print(f"create_teacher: no checkpoint at {path!r}; the teacher keeps its initial weights")
+    for p in teacher.parameters():
+        p.requires_grad_(False)
+    if device is not None:
+        teacher.to(device)
+    return teacher.eval()
 
 
 def to_device(inputs, device):

@@ -1855,6 +1855,79 @@ def agent_attention_train_supported(q, heads):
     return bool(q.is_cuda and q.dtype == torch.float32 and q.shape[-1] == 256 and heads in (1, 4, 8, 16))
 
 
+# ------------------------------------------------------------------------------------------------ KD
+def kd_kl_torch(student, teacher):
+    """The reference's composition (point_pillar_disconet_loss.py:37-44): KLDivLoss(size_average=True, reduce=True), i.e.
+    reduction 'mean' over ELEMENTS, of log_softmax(student) against softmax(teacher) over the channels of every pixel.  The CPU,
+    non-fp32 and teacher-with-gradient path, and the HEAL_KD_FUSED=0 side of the A/B."""
+    import warnings
+    N, C, H, W = teacher.shape
+    t = teacher.permute(0, 2, 3, 1).reshape(N * H * W, C)
+    s = student.permute(0, 2, 3, 1).reshape(N * H * W, C)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)        # torch recommends 'batchmean'; the reference asks for 'mean'
+        return torch.nn.functional.kl_div(torch.nn.functional.log_softmax(s, dim=1), torch.nn.functional.softmax(t, dim=1),
+                                          reduction="mean")
+
+
+def kd_kl_supported(student, teacher):
+    """The fused distillation term: CUDA fp32 maps of one 4-D shape and a teacher outside the autograd graph (the kernel has no
+    gradient for it).  HEAL_KD_FUSED=0 forces the torch composition (scripts/kd_bench.py)."""
+    return bool(isinstance(student, torch.Tensor) and isinstance(teacher, torch.Tensor) and student.is_cuda and teacher.is_cuda
+                and student.dtype == torch.float32 and teacher.dtype == torch.float32 and student.dim() == 4
+                and student.shape == teacher.shape and student.numel() > 0 and student.device == teacher.device
+                and not (teacher.requires_grad and torch.is_grad_enabled())
+                and os.environ.get("HEAL_KD_FUSED", "1") != "0")
+
+
+def kd_kl_loss(student, teacher, need_grad=True, grad_out=None):
+    """KD.  student, teacher [N, C, H, W] f32 cuda (made contiguous) -> (loss [1], grad | None): the KL term of DiscoNet's
+    distillation, mean over the N*C*H*W elements, and d loss / d student = (softmax(student) - softmax(teacher)) / (N*C*H*W).
+    need_grad=False passes a NULL gradient: the kernel only reads.  grad_out: a contiguous f32 buffer of the student's shape to
+    write the gradient into.  Two launches, no host synchronisation, no atomics (bit-equal from run to run)."""
+    for t, name in ((student, "student"), (teacher, "teacher")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _capi.HealAmdError(f"kd_kl_loss: {name} must be a CUDA/HIP tensor (heal_amd has no CPU path)")
+        if t.dtype != torch.float32:
+            raise _capi.HealAmdError(f"kd_kl_loss: {name} must have dtype torch.float32, got {t.dtype}")
+    if student.dim() != 4 or student.shape != teacher.shape or student.numel() == 0:
+        raise _capi.HealAmdError(f"kd_kl_loss: student {tuple(student.shape)} and teacher {tuple(teacher.shape)} must be equal, "
+                                 "non-empty [N, C, H, W] maps")
+    student, teacher = student.detach().contiguous(), teacher.detach().contiguous()
+    N, C, H, W = (int(v) for v in student.shape)
+    grad = None
+    if need_grad:
+        grad = grad_out if grad_out is not None else torch.empty_like(student)
+        if (not grad.is_cuda or grad.dtype != torch.float32 or grad.shape != student.shape or not grad.is_contiguous()):
+            raise _capi.HealAmdError("kd_kl_loss: grad_out must be a contiguous f32 CUDA tensor of the student's shape")
+    nbytes = _capi.query("heal_kd_kl_loss_workspace", N, C, H, W)
+    if nbytes == 0:
+        raise _capi.HealAmdError(f"kd_kl_loss: shape {(N, C, H, W)} is out of range")
+    ws = _workspace("kd_kl", nbytes, student.device)
+    loss = torch.empty(1, dtype=torch.float32, device=student.device)
+    with _Timed(f"kd_kl_loss_c{C}", nbytes=4.0 * student.numel() * (3 if need_grad else 2)):
+        _capi.call("heal_kd_kl_loss", _ptr(student), _ptr(teacher), N, C, H, W, _ptr(loss), _ptr(grad), _ptr(ws),
+                   ctypes.c_size_t(nbytes), _stream())
+    return loss, grad
+
+
+class KdKlLoss(torch.autograd.Function):
+    """kd_kl_loss under autograd: forward = heal_kd_kl_loss, which also writes d loss / d student (saved); backward scales it by
+    the incoming gradient.  The teacher receives none."""
+
+    @staticmethod
+    def forward(ctx, student, teacher):
+        loss, grad = kd_kl_loss(student, teacher, need_grad=ctx.needs_input_grad[0])
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (grad,) = ctx.saved_tensors
+        return grad_out * grad, None
+
+
 # ------------------------------------------------------------------------------------------------ K6c
 def ln_stats(x, eps):
     """(mean, rstd) of every token of x [..., C] -> [T, 2] f32: the statistics half of a LayerNorm whose application is

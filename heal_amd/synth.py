@@ -97,6 +97,32 @@ def pairwise_t_matrix(poses, max_cav):
     return out
 
 
+def teacher_points(clouds, poses, lidar_range):
+    """The early-fusion cloud DiscoNet's teacher sees (intermediate_fusion_dataset.py:96-117, 391-395): every agent's cloud
+    [N_k,4] projected into the ego frame (agent 0; T_{0<-k} = inv(T_0) T_k, float32 arithmetic as project_points_by_matrix_torch),
+    stacked in agent order, and masked to the open box of `lidar_range` (pcd_utils.py:41-67).  -> float32 [N,4]."""
+    T0 = x_to_world(poses[0])
+    out = []
+    for pts, pose in zip(clouds, poses):
+        pts = np.asarray(pts, np.float32)
+        tfm = np.linalg.solve(T0, x_to_world(pose)).astype(np.float32)
+        xyz1 = np.concatenate([pts[:, :3], np.ones((pts.shape[0], 1), np.float32)], 1)
+        out.append(np.concatenate([(xyz1 @ tfm.T)[:, :3], pts[:, 3:4]], 1))
+    p = np.vstack(out)
+    r = lidar_range
+    keep = ((p[:, 0] > r[0]) & (p[:, 0] < r[3]) & (p[:, 1] > r[1]) & (p[:, 1] < r[4]) & (p[:, 2] > r[2]) & (p[:, 2] < r[5]))
+    return np.ascontiguousarray(p[keep], dtype=np.float32)
+
+
+def teacher_processed_lidar(scenes, lidar_range, voxelize):
+    """`teacher_processed_lidar` of a batch: scenes = [(clouds, poses), ...]; each scene's teacher_points voxelised ONCE
+    (intermediate_fusion_dataset.py:396) by `voxelize(points, batch_idx) -> (voxels, coords (b,z,y,x), num_points)` (numpy; the
+    oracle's voxeliser on the CPU, heal_voxelize on the device) and collated like collate_batch_list: one sample per scene."""
+    parts = [voxelize(teacher_points(clouds, poses, lidar_range), b) for b, (clouds, poses) in enumerate(scenes)]
+    return {"voxel_features": np.concatenate([v for v, _, _ in parts]), "voxel_coords": np.concatenate([c for _, c, _ in parts]),
+            "voxel_num_points": np.concatenate([n for _, _, n in parts])}
+
+
 def camera_rig(seed, n_cams=4, H=384, W=512):
     """Four cameras yawed 0/100/-100/180 deg, 90-degree FoV, no post-augmentation.
     Returns dict of float32 arrays: rots [n,3,3], trans [n,3], intrins [n,3,3], post_rots, post_trans."""

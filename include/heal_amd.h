@@ -30,7 +30,10 @@ extern "C" {
                                    9: + heal_v2v_message[_workspace] / heal_gru_zero_state (V2VNet fusion);
                                    10: + heal_warp_att_fuse_levels (CoAlign multiscale fusion);
                                    11: + heal_disco_fuse (DiscoNet fusion);
-                                   12: + heal_decode_nms_agents[_workspace] (late fusion: pooled decode + one NMS) */
+                                   12: + heal_decode_nms_agents[_workspace] (late fusion: pooled decode + one NMS);
+                                   still 12: + heal_kd_kl_loss[_workspace] (DiscoNet distillation).  Purely additive -- no existing
+                                   signature changed -- so the version was not raised: a library built before them passes the
+                                   version check and fails at the missing symbol in _capi.call ("does not export") */
 
 int heal_abi_version(void);
 const char* heal_last_error(void);
@@ -829,6 +832,23 @@ size_t heal_label_assign_workspace(int n_gt);
 int heal_label_assign(const float* anchor_boxes, int n_anchors, const float* gt_boxes, int n_gt,
                       float pos_threshold, float neg_threshold, int32_t* assigned, uint8_t* neg, void* ws,
                       size_t ws_bytes, void* stream);
+
+/* ---- DiscoNet distillation (training) ---------------------------------------------------------------------
+ * heal_kd_kl_loss: the KD term of opencood/loss/point_pillar_disconet_loss.py:35-46,
+ *   KLDivLoss(size_average=True, reduce=True)(log_softmax(S', 1), softmax(T', 1)) with S', T' the student and teacher maps
+ *   [n, channels, H, W] permuted to [n*H*W, channels], and its gradient with respect to the student, in one pass over the NCHW
+ *   maps (no permuted copies):
+ *     loss[0]        = sum_{n,p,c} p_t (log p_t - log p_s) / (n*channels*H*W)     (the mean over ELEMENTS, as that torch call)
+ *     grad[n, c, p]  = (p_s - p_t) / (n*channels*H*W)                             (grad may be NULL: nothing is stored)
+ *   with p = softmax over the channels of one pixel, log p = x - max - log sum exp.  A teacher probability that underflows
+ *   contributes 0; finite inputs of any magnitude give finite results; student == teacher gives exactly 0 and an all-zero
+ *   gradient.  fp32, any channels >= 1 (64 / 128 / 256 read every input byte once), any H, W.  No atomics: per-block partial
+ *   sums go to ws and a second kernel adds them in a fixed order, so repeated launches are bit-equal.  Capture-safe (two kernel
+ *   launches, no host synchronisation).  ws: heal_kd_kl_loss_workspace(n, channels, H, W) bytes (0 for a bad shape), need not
+ *   be initialised.                                                                                                          */
+size_t heal_kd_kl_loss_workspace(int n, int channels, int H, int W);
+int heal_kd_kl_loss(const float* student, const float* teacher, int n, int channels, int H, int W, float* loss, float* grad,
+                    void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
