@@ -44,6 +44,8 @@ _SIGNATURES = {
                                c_void_p, c_void_p]),
     "heal_warp_fuse_levels": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p]),
+    "heal_warp_fuse_levels_src": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                          c_void_p, c_void_p, c_void_p]),
     "heal_warp_att_fuse_levels": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                           c_int, c_void_p, c_void_p]),
     "heal_disco_fuse": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 11),

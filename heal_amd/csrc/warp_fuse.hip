@@ -193,14 +193,23 @@ constexpr int WL_BMAX = 32;         // largest staged source box side
 constexpr int WL_CC = 8;            // channels per staging round
 constexpr int WL_MAXL = 4;          // pyramid levels per launch
 
+// Where agent a's map of a level lies: the map is defined on box = (y0, y1, x0, x1) of the level's H x W grid (a full map, a dense
+// crop, or a window of a larger tensor) and is exactly zero -- features and score -- outside it.  feat / occ point at the box's
+// (y0, x0) element.  keep = the rectangle on which the score is read: the crop window of a camera agent (inside its box, checked on
+// the host), else the box.
+struct WfSource {
+    const float* feat;      // element (c, y, x) of the box at feat[c * plane + (y - y0) * row + (x - x0)]
+    const float* occ;       // logit (y, x) at occ[(y - y0) * orow + (x - x0)]
+    int row, plane, orow;
+    int box[4];
+    int keep[4];
+};
 struct WfLevel {
-    const float* feats;     // [n_agents, C, H, W]
-    const float* occ;       // [n_agents, 1, H, W]
+    WfSource src[WF_MAXA];
     float* out;             // [C, H, W]
     int C, H, W;
     int tiles_x, cgroups, cpb;   // tiles per row, channel slices per tile, channels per slice
     int block0;                  // first block of this level
-    int crop[WF_MAXA][4];
 };
 struct WfLevels {
     WfLevel lv[WL_MAXL];
@@ -208,6 +217,22 @@ struct WfLevels {
     const double* mdev;
     double m[WF_MAXA][6];
 };
+
+// sample_score on a source descriptor: tap k at (ty + (k >> 1), tx + (k & 1)); sigmoid(occ) + 1e-4 inside `keep`, exactly zero (and
+// no load) outside it.  Same products, same order as sample_score.
+__device__ __forceinline__ float score_src(const WfSource& S, int y, int x) {
+    if (y < S.keep[0] || y >= S.keep[1] || x < S.keep[2] || x >= S.keep[3]) return 0.f;
+    return 1.f / (1.f + expf(-S.occ[(size_t)(y - S.box[0]) * S.orow + (x - S.box[2])])) + 1e-4f;
+}
+
+__device__ __forceinline__ float sample_score_src(const WfSource& S, const Taps& t, int ty, int tx) {
+    float acc = 0.f;
+    if (t.ok & 1u) acc = score_src(S, ty, tx) * t.w[0];
+    if (t.ok & 2u) acc += score_src(S, ty, tx + 1) * t.w[1];
+    if (t.ok & 4u) acc += score_src(S, ty + 1, tx) * t.w[2];
+    if (t.ok & 8u) acc += score_src(S, ty + 1, tx + 1) * t.w[3];
+    return acc;
+}
 
 template <int NA>
 __global__ __launch_bounds__(256) void k_warp_fuse_lds(const WfLevels P) {
@@ -263,12 +288,18 @@ __global__ __launch_bounds__(256) void k_warp_fuse_lds(const WfLevels P) {
                 gx = (float)(((float)m[0] * xs + (float)m[1] * ys) + (float)m[2]);
                 gy = (float)(((float)m[3] * xs + (float)m[4] * ys) + (float)m[5]);
             }
-            const Taps t = make_taps(gx, gy, L.H, L.W);
-            prob[a] = sample_score(L.occ + (size_t)a * HW, t, L.W, L.crop[a]);
+            Taps t = make_taps(gx, gy, L.H, L.W);
             // north-west tap coordinates: the clamps of make_taps on the coordinates themselves (t.off = y0 * W + x0)
             const float ix = ((gx + 1.f) * (float)L.W - 1.f) / 2.f, iy = ((gy + 1.f) * (float)L.H - 1.f) / 2.f;
             tx[a] = (int)fminf(fmaxf(floorf(ix), -2.f), (float)L.W);
             ty[a] = (int)fminf(fmaxf(floorf(iy), -2.f), (float)L.H);
+            // a tap outside the agent's box is a tap outside its map: feature 0, score 0, never dereferenced.  (With the host's
+            // checks -- window +- 1 inside the box -- such a tap never carries weight: its pixel's score is zero anyway.)
+            const WfSource& S = L.src[a];
+            const unsigned in_y0 = ty[a] >= S.box[0] && ty[a] < S.box[1], in_y1 = ty[a] + 1 >= S.box[0] && ty[a] + 1 < S.box[1];
+            const unsigned in_x0 = tx[a] >= S.box[2] && tx[a] < S.box[3], in_x1 = tx[a] + 1 >= S.box[2] && tx[a] + 1 < S.box[3];
+            t.ok &= (in_y0 & in_x0) | ((in_y0 & in_x1) << 1) | ((in_y1 & in_x0) << 2) | ((in_y1 & in_x1) << 3);
+            prob[a] = sample_score_src(S, t, ty[a], tx[a]);
             okb[a] = t.ok;
 #pragma unroll
             for (int k = 0; k < 4; ++k) wt[a][k] = ((t.ok >> k) & 1u) ? t.w[k] : 0.f;
@@ -310,7 +341,11 @@ __global__ __launch_bounds__(256) void k_warp_fuse_lds(const WfLevels P) {
         for (int a = 0; a < NA; ++a) {
             const int bx0 = s_box[a][0], by0 = s_box[a][1], bw = s_box[a][2] - bx0 + 1, bh = s_box[a][3] - by0 + 1;
             if (bw <= 0 || bh <= 0) continue;                       // block-uniform: no pixel of the tile sees agent a
-            const float* __restrict__ base = L.feats + ((size_t)a * L.C + c0) * HW;
+            const WfSource& S = L.src[a];
+            const int row = S.row;
+            const size_t plane = (size_t)S.plane;
+            // the staged box lies inside the agent's box (it bounds taps that passed the box test): offsets relative to its origin
+            const float* __restrict__ base = S.feat + (size_t)c0 * plane + (size_t)(by0 - S.box[0]) * row + (bx0 - S.box[2]);
             if (bw <= WL_BMAX && bh <= WL_BMAX) {
                 const int pitch = bw | 1;
                 // the [nc][bh][bw] box: lane lx = column, row worker ry takes rows ry, ry + 8, ry + 16, ry + 24 of every channel.
@@ -321,9 +356,9 @@ __global__ __launch_bounds__(256) void k_warp_fuse_lds(const WfLevels P) {
                 const int xs = min(lx, bw - 1);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float* rowp = base + (size_t)(by0 + min(ry + 8 * j, bh - 1)) * L.W + bx0 + xs;
+                    const float* rowp = base + (size_t)min(ry + 8 * j, bh - 1) * row + xs;
 #pragma unroll
-                    for (int u = 0; u < WL_CC; ++u) st[j][u] = (P.dbg & 2) ? 1.f : rowp[(size_t)min(u, nc - 1) * HW];
+                    for (int u = 0; u < WL_CC; ++u) st[j][u] = (P.dbg & 2) ? 1.f : rowp[(size_t)min(u, nc - 1) * plane];
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -354,13 +389,14 @@ __global__ __launch_bounds__(256) void k_warp_fuse_lds(const WfLevels P) {
                 }
                 __syncthreads();
             } else if (okb[a]) {                                      // a box larger than the staging tile: direct gather
-                const int o = ty[a] * L.W + tx[a];
+                // offsets from the staged box's origin (a live tap lies inside it; the others are clamped onto it, weight 0)
+                const int o = (ty[a] - by0) * row + (tx[a] - bx0);
                 const int o0 = (okb[a] & 1u) ? o : 0, o1 = (okb[a] & 2u) ? o + 1 : 0;
-                const int o2 = (okb[a] & 4u) ? o + L.W : 0, o3 = (okb[a] & 8u) ? o + L.W + 1 : 0;
+                const int o2 = (okb[a] & 4u) ? o + row : 0, o3 = (okb[a] & 8u) ? o + row + 1 : 0;
 #pragma unroll
                 for (int u = 0; u < WL_CC; ++u) {
                     if (u < nc) {
-                        const float* src = base + (size_t)u * HW;
+                        const float* src = base + (size_t)u * plane;
                         float v = src[o0] * wt[a][0];
                         v += src[o1] * wt[a][1];
                         v += src[o2] * wt[a][2];
@@ -738,13 +774,11 @@ extern "C" int heal_warp_fuse(const float* feats, const float* occ, int n_agents
     return 0;
 }
 
-extern "C" int heal_warp_fuse_levels(int n_levels, const float* const* feats_host, const float* const* occ_host,
-                                     int n_agents, const int32_t* channels_host, const int32_t* h_host, const int32_t* w_host,
-                                     const double* affine_host, const double* affine_dev, int grid_f64,
-                                     const int32_t* crop_host, float* const* out_host, void* stream) {
-    HEAL_REQUIRE(n_levels >= 1 && n_levels <= WL_MAXL, "warp_fuse_levels: 1..%d levels per launch (got %d)", WL_MAXL, n_levels);
-    HEAL_REQUIRE(n_agents >= 1 && n_agents <= WF_MAXA, "warp_fuse_levels: n_agents must be in [1,%d] (got %d)", WF_MAXA, n_agents);
-    HEAL_REQUIRE(affine_host != nullptr || affine_dev != nullptr, "warp_fuse_levels: affine is NULL (host and device)");
+// Fills the launch descriptor from per-(level, agent) sources and launches k_warp_fuse_lds.  `who` names the entry point in messages.
+static int launch_warp_fuse_levels(const char* who, int n_levels, const heal_k5_source* src_host, int n_agents,
+                                   const int32_t* channels_host, const int32_t* h_host, const int32_t* w_host,
+                                   const double* affine_host, const double* affine_dev, int grid_f64, const int32_t* crop_host,
+                                   float* const* out_host, void* stream) {
     WfLevels P;
     P.n_levels = n_levels; P.n_agents = n_agents; P.grid_f64 = grid_f64; P.mdev = affine_dev;
     P.dbg = HEAL_DEBUG_ENV("HEAL_K5_DBG");   // timing experiments only (read once, announced on stderr)
@@ -754,9 +788,8 @@ extern "C" int heal_warp_fuse_levels(int n_levels, const float* const* feats_hos
     for (int l = 0; l < WL_MAXL; ++l) {
         WfLevel& L = P.lv[l];
         if (l >= n_levels) { L = P.lv[0]; L.block0 = 1 << 30; continue; }
-        HEAL_REQUIRE(feats_host[l] && occ_host[l] && out_host[l] && channels_host[l] >= 1 && h_host[l] >= 1 && w_host[l] >= 1,
-                     "warp_fuse_levels: bad level %d", l);
-        L.feats = feats_host[l]; L.occ = occ_host[l]; L.out = out_host[l];
+        HEAL_REQUIRE(out_host[l] && channels_host[l] >= 1 && h_host[l] >= 1 && w_host[l] >= 1, "%s: bad level %d", who, l);
+        L.out = out_host[l];
         L.C = channels_host[l]; L.H = h_host[l]; L.W = w_host[l];
         L.tiles_x = ceil_div(L.W, WL_T);
         const int tiles = L.tiles_x * ceil_div(L.H, WL_T);
@@ -774,11 +807,31 @@ extern "C" int heal_warp_fuse_levels(int n_levels, const float* const* feats_hos
         L.cgroups = ceil_div(L.C, cpb);
         L.block0 = (int)blocks;
         blocks += (long long)tiles * L.cgroups;
-        for (int a = 0; a < WF_MAXA; ++a)
-            for (int k = 0; k < 4; ++k)
-                L.crop[a][k] = (a < n_agents && crop_host) ? crop_host[((size_t)l * n_agents + a) * 4 + k] : 0;
+        for (int a = 0; a < WF_MAXA; ++a) {
+            WfSource& S = L.src[a];
+            if (a >= n_agents) { S = L.src[0]; continue; }
+            const heal_k5_source& h = src_host[(size_t)l * n_agents + a];
+            const int* b = h.box;
+            HEAL_REQUIRE(h.feat && h.occ, "%s: level %d agent %d: null source", who, l, a);
+            HEAL_REQUIRE(0 <= b[0] && b[0] < b[1] && b[1] <= L.H && 0 <= b[2] && b[2] < b[3] && b[3] <= L.W,
+                         "%s: level %d agent %d: box (%d,%d,%d,%d) is empty or leaves the %d x %d map", who, l, a, b[0], b[1], b[2],
+                         b[3], L.H, L.W);
+            const long long bh = b[1] - b[0], bw = b[3] - b[2];
+            HEAL_REQUIRE(h.feat_row >= bw && h.occ_row >= bw && h.feat_plane >= (bh - 1) * h.feat_row + bw &&
+                             h.feat_plane < (1ll << 31) && (long long)L.C * h.feat_plane < (1ll << 40),
+                         "%s: level %d agent %d: strides (row %lld, plane %lld, occ row %lld) do not hold a %lld x %lld box", who, l, a,
+                         (long long)h.feat_row, (long long)h.feat_plane, (long long)h.occ_row, bh, bw);
+            S.feat = h.feat; S.occ = h.occ;
+            S.row = (int)h.feat_row; S.plane = (int)h.feat_plane; S.orow = (int)h.occ_row;
+            const int32_t* c = crop_host ? crop_host + ((size_t)l * n_agents + a) * 4 : nullptr;
+            const bool window = c && c[1] > c[0];
+            for (int k = 0; k < 4; ++k) S.box[k] = b[k];
+            // the score is read on the window (clipped to the box: outside the box the map is zero), or on the whole box
+            S.keep[0] = window ? (c[0] > b[0] ? c[0] : b[0]) : b[0]; S.keep[1] = window ? (c[1] < b[1] ? c[1] : b[1]) : b[1];
+            S.keep[2] = window ? (c[2] > b[2] ? c[2] : b[2]) : b[2]; S.keep[3] = window ? (c[3] < b[3] ? c[3] : b[3]) : b[3];
+        }
     }
-    HEAL_REQUIRE(blocks < (1ll << 30), "warp_fuse_levels: grid too large");
+    HEAL_REQUIRE(blocks < (1ll << 30), "%s: grid too large", who);
     hipStream_t st = (hipStream_t)stream;
     switch (n_agents) {
 #define HEAL_WFL(N) case N: HEAL_LAUNCH_EV(k_warp_fuse_lds<N>, dim3((unsigned)blocks), dim3(256), 0, st, P); break;
@@ -787,6 +840,70 @@ extern "C" int heal_warp_fuse_levels(int n_levels, const float* const* feats_hos
     }
     HEAL_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int heal_warp_fuse_levels(int n_levels, const float* const* feats_host, const float* const* occ_host,
+                                     int n_agents, const int32_t* channels_host, const int32_t* h_host, const int32_t* w_host,
+                                     const double* affine_host, const double* affine_dev, int grid_f64,
+                                     const int32_t* crop_host, float* const* out_host, void* stream) {
+    HEAL_REQUIRE(n_levels >= 1 && n_levels <= WL_MAXL, "warp_fuse_levels: 1..%d levels per launch (got %d)", WL_MAXL, n_levels);
+    HEAL_REQUIRE(n_agents >= 1 && n_agents <= WF_MAXA, "warp_fuse_levels: n_agents must be in [1,%d] (got %d)", WF_MAXA, n_agents);
+    HEAL_REQUIRE(affine_host != nullptr || affine_dev != nullptr, "warp_fuse_levels: affine is NULL (host and device)");
+    // the stacked tensors as sources: agent a's full map at feats + a C HW
+    heal_k5_source src[WL_MAXL * WF_MAXA];
+    for (int l = 0; l < n_levels; ++l) {
+        HEAL_REQUIRE(feats_host[l] && occ_host[l] && out_host[l] && channels_host[l] >= 1 && h_host[l] >= 1 && w_host[l] >= 1,
+                     "warp_fuse_levels: bad level %d", l);
+        const long long HW = (long long)h_host[l] * w_host[l];
+        for (int a = 0; a < n_agents; ++a) {
+            heal_k5_source& h = src[l * n_agents + a];
+            h.feat = feats_host[l] + (size_t)a * channels_host[l] * HW;
+            h.occ = occ_host[l] + (size_t)a * HW;
+            h.feat_row = w_host[l]; h.feat_plane = HW; h.occ_row = w_host[l];
+            h.box[0] = 0; h.box[1] = h_host[l]; h.box[2] = 0; h.box[3] = w_host[l];
+        }
+    }
+    return launch_warp_fuse_levels("warp_fuse_levels", n_levels, src, n_agents, channels_host, h_host, w_host, affine_host, affine_dev,
+                                   grid_f64, crop_host, out_host, stream);
+}
+
+extern "C" int heal_warp_fuse_levels_src(int n_levels, const heal_k5_source* src_host, int n_agents, const int32_t* channels_host,
+                                         const int32_t* h_host, const int32_t* w_host, const double* affine_host,
+                                         const double* affine_dev, int grid_f64, const int32_t* crop_host, float* const* out_host,
+                                         void* stream) {
+    HEAL_REQUIRE(n_levels >= 1 && n_levels <= WL_MAXL, "warp_fuse_levels_src: 1..%d levels per launch (got %d)", WL_MAXL, n_levels);
+    HEAL_REQUIRE(n_agents >= 1 && n_agents <= WF_MAXA, "warp_fuse_levels_src: n_agents must be in [1,%d] (got %d)", WF_MAXA, n_agents);
+    HEAL_REQUIRE(affine_host != nullptr || affine_dev != nullptr, "warp_fuse_levels_src: affine is NULL (host and device)");
+    HEAL_REQUIRE(src_host && channels_host && h_host && w_host && out_host, "warp_fuse_levels_src: null argument");
+    for (int l = 0; l < n_levels; ++l) {
+        const int H = h_host[l], W = w_host[l];
+        for (int a = 0; a < n_agents; ++a) {
+            const heal_k5_source& h = src_host[(size_t)l * n_agents + a];
+            const int* b = h.box;
+            const int32_t* c = crop_host ? crop_host + ((size_t)l * n_agents + a) * 4 : nullptr;
+            if (c && c[1] > c[0]) {
+                // Exactness: a pixel whose score is not zero has a score tap inside the window, so all its taps lie in window +- 1;
+                // with that ring inside the box the kernel reads what the zero-padded stack holds there
+                const int y0 = c[0] - 1 > 0 ? c[0] - 1 : 0, y1 = c[1] + 1 < H ? c[1] + 1 : H;
+                const int x0 = c[2] - 1 > 0 ? c[2] - 1 : 0, x1 = c[3] + 1 < W ? c[3] + 1 : W;
+                HEAL_REQUIRE(b[0] <= y0 && y1 <= b[1] && b[2] <= x0 && x1 <= b[3],
+                             "warp_fuse_levels_src: level %d agent %d: crop window (%d,%d,%d,%d) +- 1 is not inside its box (%d,%d,%d,%d)",
+                             l, a, c[0], c[1], c[2], c[3], b[0], b[1], b[2], b[3]);
+            } else {
+                HEAL_REQUIRE(b[0] == 0 && b[1] == H && b[2] == 0 && b[3] == W,
+                             "warp_fuse_levels_src: level %d agent %d has no crop window: its box must be the full %d x %d map (got "
+                             "(%d,%d,%d,%d))", l, a, H, W, b[0], b[1], b[2], b[3]);
+            }
+            // 16-byte row segments: column 0 of every map row of every plane starts on a 16-byte boundary
+            HEAL_REQUIRE(h.feat_row % 4 == 0 && h.feat_plane % 4 == 0 && h.occ_row % 4 == 0 &&
+                             (((uintptr_t)h.feat >> 2) - (uintptr_t)b[2]) % 4 == 0 && ((uintptr_t)h.feat & 3) == 0 &&
+                             (((uintptr_t)h.occ >> 2) - (uintptr_t)b[2]) % 4 == 0 && ((uintptr_t)h.occ & 3) == 0,
+                         "warp_fuse_levels_src: level %d agent %d: misaligned box (strides must be multiples of 4 floats and column 0 "
+                         "of the map rows 16-byte aligned: pointer - 4 x0 bytes)", l, a);
+        }
+    }
+    return launch_warp_fuse_levels("warp_fuse_levels_src", n_levels, src_host, n_agents, channels_host, h_host, w_host, affine_host,
+                                   affine_dev, grid_f64, crop_host, out_host, stream);
 }
 
 extern "C" int heal_warp_att_fuse_levels(int n_levels, const float* const* feats_host, int n_agents, const int32_t* channels_host,

@@ -57,9 +57,19 @@ def crop_camera_feature(model, m, feature):
     boxes = model.__dict__.setdefault("_heal_cam_boxes", {})
     if th > H and tw > W:
         boxes[m] = ((th - H) // 2, (th - H) // 2 + H, (tw - W) // 2, (tw - W) // 2 + W)
+        if model.__dict__.get("_heal_lean_walk"):
+            # lean inference walk (LEAN_WALK_KEY): the map stays unpadded; the model pads it itself (pad_camera_feature) if the fusion
+            # pyramid cannot read it in place
+            model.__dict__.setdefault("_heal_cam_unpadded", {})[m] = (th, tw)
+            return feature
     else:
         boxes.pop(m, None)
     return center_crop(feature, th, tw)
+
+
+# Opt-in key of the model's input dict: the caller wants the detection heads only, so the fusion pyramid may fuse every agent's map from
+# where its stage left it (PyramidFusion.forward_collab_lean: no stack, no padded camera maps, no `occ_single_list` in the output).
+LEAN_WALK_KEY = "heal_lean_walk"
 
 
 def wants_depth_items(model, m):

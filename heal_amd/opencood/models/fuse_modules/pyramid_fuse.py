@@ -243,6 +243,139 @@ class PyramidFusion(ResNetBEVBackbone):
             return self.get_multiscale_feature_camcrop(spatial_features, *cc)
         return self.get_multiscale_feature(spatial_features)
 
+    # ---- lean inference walk: every agent's map is fused from where its stage left it -------------------------------------------------
+    # The camera-crop walk above still receives a STACK of the agents' maps, with the camera maps zero-padded to the LiDAR range, and
+    # rebuilds a full-size stack after stage 0 (crop copy, zero-response broadcast, paste) -- although K5 multiplies everything outside a
+    # camera agent's crop window by a score of exactly zero.  Here the caller hands over the LiDAR agents' tensor and the camera agents'
+    # UNPADDED maps; stage 0 runs on the LiDAR tensor as it is and on the camera crop (content + halo), and K5 reads both results in place
+    # (ops.warp_fuse_levels_src: per agent a pointer, strides and the box its map is defined on).  Stage 1's camera input is the cached
+    # zero response PRE-CROPPED to that stage's input crop with the valid stage-0 box pasted in.  From stage 1 on the assembly is the
+    # camera-crop walk's (the last stage runs on all agents in one launch).  Same kernels on the same values as the camera-crop walk.
+    def _zero_response_crop(self, like, level, crop):
+        """The zero-input response of stage `level` on crop = (y0, y1, x0, x1), contiguous [1, C, h, w]."""
+        tag, sources, extra = self._zero_response_slot(like)
+        return "pyramid_zero_response_crop", sources, extra + (int(level), tuple(int(v) for v in crop))
+
+    @staticmethod
+    def _cam_window(H, W, mod, cam_crop_info):
+        return crop_window(H, W, cam_crop_info[mod][f"crop_ratio_H_{mod}"], cam_crop_info[mod][f"crop_ratio_W_{mod}"])
+
+    def lean_plan(self, like, record_len, agent_modality_list, cam_boxes, cam_crop_info):
+        """What forward_collab_lean needs, or None when the lean walk does not apply: one scene of at most 8 agents at inference, the
+        conditions of the camera-crop walk (_camcrop_args), a crop window for every camera agent, a cropped stage 0, the other agents
+        of ONE modality (their encoder's output is then the LiDAR tensor in scene order), cached responses ready under capture.
+        like: a [k, C, H, W] tensor of the full map size on the model's device (k may be 0)."""
+        import os
+        if (len(record_len) != 1 or not 1 <= self.num_levels <= 4 or int(record_len[0]) > 8 or self.training
+                or os.environ.get("HEAL_K5_LEVELS", "1") != "1" or os.environ.get("HEAL_PYRAMID_LEAN", "1") != "1"):
+            return None
+        cc = self._camcrop_args(like, agent_modality_list, cam_boxes)
+        if cc is None:
+            return None
+        (c0, c1), box = cc
+        n = len(agent_modality_list)
+        other = (0, c0) if c0 > 0 else (c1, n)
+        if not cam_crop_info or any(agent_modality_list[k] not in cam_crop_info for k in range(c0, c1)):
+            return None
+        if len({agent_modality_list[k] for k in range(*other)}) > 1:
+            return None
+        plan = self._camcrop_plan(like, (c0, c1), box)
+        if plan[0] is None:
+            return None
+        H, W = int(like.shape[2]), int(like.shape[3])
+        gbox = plan[0][1]
+        for k in range(c0, c1):     # K5 reads a camera agent's stage-0 crop on its valid box: the window's bilinear ring must lie inside
+            wy0, wy1, wx0, wx1 = self._cam_window(H, W, agent_modality_list[k], cam_crop_info)
+            if not (gbox[0] <= max(0, wy0 - 1) and min(H, wy1 + 1) <= gbox[1] and gbox[2] <= max(0, wx0 - 1) and min(W, wx1 + 1) <= gbox[3]):
+                return None
+        if self.layernum_ > 1 and plan[1] is not None:
+            slot = self._zero_response_crop(like, 0, plan[1][0])
+            if derived.capturing() and not derived.ready(slot[0], slot[1], slot[2]):
+                return None
+        return (c0, c1), other, plan
+
+    def forward_collab_lean(self, lidar, cam_maps, like, lean, affine_matrix, agent_modality_list, cam_crop_info, cam_boxes,
+                            grid_f64=True):
+        """forward_collab of one scene by the lean walk.  lidar: [n_l, C, H, W] (the non-camera agents in scene order) or None;
+        cam_maps: the camera agents' unpadded [C, h, w] maps in scene order; lean: lean_plan's result -> fused feature (no occupancy
+        list: the full-size occupancy maps of the camera agents are never formed)."""
+        (c0, c1), other, plan = lean
+        n, nc, nl = len(agent_modality_list), c1 - c0, other[1] - other[0]
+        bg = self._zero_response(like)
+        dt, dev = like.dtype, like.device
+        # stage 0: the camera agents enter as the stage's input crop (their content inside a zero halo)
+        (cy0, cy1, cx0, cx1), gbox, pbox = plan[0]
+        layer = self.resnet.layer0
+        xc = torch.zeros((nc, int(like.shape[1]), cy1 - cy0, cx1 - cx0), dtype=dt, device=dev)
+        for j, m in enumerate(cam_maps):
+            b = cam_boxes[agent_modality_list[c0 + j]]
+            xc[j, :, b[0] - cy0:b[1] - cy0, b[2] - cx0:b[3] - cx0] = m
+        yc = layer(xc)
+        full, xl = None, None
+        if self.layernum_ > 1 and plan[1] is None:      # the next stage runs on the full maps of all agents: assemble them
+            full = torch.empty((n,) + tuple(bg[0].shape[1:]), dtype=dt, device=dev)
+            full[c0:c1] = bg[0]
+            full[c0:c1, :, gbox[0]:gbox[1], gbox[2]:gbox[3]] = yc[:, :, pbox[0]:pbox[1], pbox[2]:pbox[3]]
+        if nl:
+            xl = lidar
+            for j, blk in enumerate(layer):
+                xl = blk(xl, out=full[other[0]:other[1]]) if (full is not None and j == len(layer) - 1) else blk(xl)
+        sources, shapes = [], []
+        occ_c = self.occupancy_head(0, yc)
+        occ_l = self.occupancy_head(0, xl) if nl else None
+        level = [None] * n
+        for j in range(nl):
+            level[other[0] + j] = (xl[j], occ_l[j, 0], (0, 0))
+        for j in range(nc):
+            level[c0 + j] = (yc[j, :, pbox[0]:pbox[1], pbox[2]:pbox[3]], occ_c[j, 0, pbox[0]:pbox[1], pbox[2]:pbox[3]],
+                             (gbox[0], gbox[2]))
+        sources.append(level)
+        shapes.append(tuple(int(v) for v in bg[0].shape[2:]))
+        for i in range(1, self.layernum_):
+            layer = getattr(self.resnet, f"layer{i}")
+            if plan[i] is None:
+                full = self.resnet.run_stage(layer, full)
+            else:
+                (cy0, cy1, cx0, cx1), g2, p2 = plan[i]
+                nxt = torch.empty((n,) + tuple(bg[i].shape[1:]), dtype=dt, device=dev)
+                if nl:
+                    xa = full[other[0]:other[1]] if full is not None else xl
+                    for j, blk in enumerate(layer):
+                        xa = blk(xa, out=nxt[other[0]:other[1]]) if j == len(layer) - 1 else blk(xa)
+                if full is not None:
+                    xin = full[c0:c1, :, cy0:cy1, cx0:cx1].contiguous()
+                else:       # the cached zero response on this stage's input crop + the valid box of the previous stage's crop
+                    crop = (cy0, cy1, cx0, cx1)
+                    tag, src, extra = self._zero_response_crop(like, i - 1, crop)
+                    bgc = derived.derived(tag, src, lambda: bg[i - 1][:, :, cy0:cy1, cx0:cx1].contiguous(), extra)
+                    xin = bgc.repeat(nc, 1, 1, 1)
+                    iy0, iy1, ix0, ix1 = max(gbox[0], cy0), min(gbox[1], cy1), max(gbox[2], cx0), min(gbox[3], cx1)
+                    xin[:, :, iy0 - cy0:iy1 - cy0, ix0 - cx0:ix1 - cx0] = yc[:, :, pbox[0] + iy0 - gbox[0]:pbox[0] + iy1 - gbox[0],
+                                                                             pbox[2] + ix0 - gbox[2]:pbox[2] + ix1 - gbox[2]]
+                yc = layer(xin)
+                nxt[c0:c1] = bg[i]
+                nxt[c0:c1, :, g2[0]:g2[1], g2[2]:g2[3]] = yc[:, :, p2[0]:p2[1], p2[2]:p2[3]]
+                gbox, pbox, full = g2, p2, nxt
+            occ = self.occupancy_head(i, full)
+            H, W = int(full.shape[2]), int(full.shape[3])
+            level = []
+            for k in range(n):
+                y0, y1, x0, x1 = 0, H, 0, W
+                if c0 <= k < c1:
+                    # the stack holds the camera agents' whole map; K5 needs it on the crop window's bilinear ring only (columns
+                    # rounded out to 16 bytes): its staging is clipped to that box
+                    wy0, wy1, wx0, wx1 = self._cam_window(H, W, agent_modality_list[k], cam_crop_info)
+                    y0, y1 = max(0, wy0 - 1), min(H, wy1 + 1)
+                    x0, x1 = max(0, wx0 - 1) // 4 * 4, min(W, -(-(wx1 + 1) // 4) * 4)
+                level.append((full[k, :, y0:y1, x0:x1], occ[k, 0, y0:y1, x0:x1], (y0, x0)))
+            sources.append(level)
+            shapes.append((H, W))
+        crops_all = []
+        for (H, W) in shapes:
+            crops_all.append([self._cam_window(H, W, mod, cam_crop_info) if mod in cam_crop_info else None for mod in agent_modality_list])
+        fused = ops.warp_fuse_levels_src(sources, shapes, affine_matrix[0][0, :n], grid_f64, crops_all)
+        return self.decode_multiscale_feature([f.unsqueeze(0) for f in fused])
+
     def forward_collab(self, spatial_features, record_len, affine_matrix, agent_modality_list=None,
                        cam_crop_info=None, grid_f64=True, cam_boxes=None):
         """affine_matrix: host numpy [B,L,L,2,3] (normalize_pairwise_tfm of the host pairwise matrix);

@@ -644,6 +644,66 @@ def warp_fuse_levels(feats_list, occ_list, affine_rows, grid_f64=True, crops=Non
     return outs
 
 
+class K5Source(ctypes.Structure):
+    """heal_k5_source (include/heal_amd.h): where one agent's map of one level lies."""
+    _fields_ = [("feat", ctypes.c_void_p), ("occ", ctypes.c_void_p), ("feat_row", ctypes.c_int64), ("feat_plane", ctypes.c_int64),
+                ("occ_row", ctypes.c_int64), ("box", ctypes.c_int32 * 4)]
+
+
+def warp_fuse_levels_src(sources, shapes, affine_rows, grid_f64=True, crops=None, outs=None):
+    """warp_fuse_levels with every agent's map read IN PLACE (heal_warp_fuse_levels_src): no stacked [n, C, H, W] tensor.
+    sources[l][a] = (feat, occ, (y0, x0)): feat a [C_l, bh, bw] view and occ a [bh, bw] view (unit stride along x, any row / plane
+    stride: a dense crop or a slice of a larger tensor) that hold the agent's map on the box (y0, y0 + bh, x0, x0 + bw) of the
+    level's H_l x W_l grid; shapes[l] = (H_l, W_l); crops as warp_fuse_levels.  An agent with a crop window needs window +- 1 inside
+    its box, an agent without one the full map (checked by the library) -> list of [C_l, H_l, W_l], bit-identical to
+    warp_fuse_levels on the zero-padded stack.  outs: optional preallocated contiguous [C_l, H_l, W_l] outputs."""
+    L = len(sources)
+    n = len(sources[0])
+    desc = (K5Source * (L * n))()
+    given, outs = outs, []
+    chans, keep, nbytes = [], [], 0.0
+    for l, (level, (H, W)) in enumerate(zip(sources, shapes)):
+        if len(level) != n:
+            raise _capi.HealAmdError("warp_fuse_levels_src: every level needs one source per agent")
+        C = int(level[0][0].shape[0])
+        for a, (f, o, (y0, x0)) in enumerate(level):
+            for t, name in ((f, "feat"), (o, "occ")):
+                if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+                    raise _capi.HealAmdError(f"warp_fuse_levels_src: {name} must be a float32 CUDA/HIP tensor")
+            if (f.dim() != 3 or o.dim() != 2 or int(f.shape[0]) != C or tuple(f.shape[1:]) != tuple(o.shape)
+                    or (f.shape[2] > 1 and f.stride(2) != 1) or (o.shape[1] > 1 and o.stride(1) != 1)):
+                raise _capi.HealAmdError("warp_fuse_levels_src: feat [C, bh, bw] and occ [bh, bw] views with unit stride along x")
+            bh, bw = int(o.shape[0]), int(o.shape[1])
+            d = desc[l * n + a]
+            d.feat, d.occ = f.data_ptr(), o.data_ptr()
+            d.feat_row, d.feat_plane, d.occ_row = int(f.stride(1)), int(f.stride(0)), int(o.stride(0))
+            d.box[:] = [int(y0), int(y0) + bh, int(x0), int(x0) + bw]
+            keep += [f, o]
+            nbytes += 4.0 * bh * bw * (C + 1)
+        dev = level[0][0].device
+        if given is not None:
+            y = _need(given[l], torch.float32, "out")
+            if y is not given[l] or tuple(y.shape) != (C, int(H), int(W)):
+                raise _capi.HealAmdError("warp_fuse_levels_src: outs[l] must be a contiguous [C_l, H_l, W_l] tensor")
+        outs.append(given[l] if given is not None else torch.empty((C, int(H), int(W)), dtype=torch.float32, device=dev))
+        chans.append(C)
+        nbytes += 4.0 * C * H * W
+    a, ap, adev = _affine_args(affine_rows, n)
+    cp, carr = ctypes.c_void_p(0), None
+    if crops is not None and any(c is not None for c in crops):
+        carr = np.zeros((L, n, 4), dtype=np.int32)
+        for l, c in enumerate(crops):
+            if c is not None:
+                carr[l] = np.asarray([ci if ci is not None else (0, 0, 0, 0) for ci in c], dtype=np.int32).reshape(n, 4)
+        cp = carr.ctypes.data_as(ctypes.c_void_p)
+    yp = _host_array([y.data_ptr() for y in outs], ctypes.c_void_p)
+    with _Timed("warp_fuse_levels", 0.0, nbytes, kernel_events=True):
+        _capi.call("heal_warp_fuse_levels_src", L, ctypes.cast(desc, ctypes.c_void_p), n, _host_array(chans, ctypes.c_int32),
+                   _host_array([int(s[0]) for s in shapes], ctypes.c_int32), _host_array([int(s[1]) for s in shapes], ctypes.c_int32),
+                   ap, adev, int(bool(grid_f64)), cp, yp, _stream())
+    return outs
+
+
 WARP_ATT_MAX_AGENTS, WARP_ATT_MAX_LEVELS = 8, 4
 
 

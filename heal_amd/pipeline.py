@@ -232,10 +232,19 @@ class ScenePipeline:
     def forward(self, scene):
         return self.model(scene.model_input())
 
+    @staticmethod
+    def _lean_input(inputs):
+        """The model input of the inference steps (step, capture, replay, FramesInFlight): only the detection heads are read, so a model
+        that knows the key may skip intermediate outputs (HeterPyramidCollab: the lean pyramid walk); other models ignore it."""
+        from heal_amd.opencood.models._heter_common import LEAN_WALK_KEY
+        d = inputs.model_input()
+        d[LEAN_WALK_KEY] = True
+        return d
+
     @torch.no_grad()
     def step(self, scene):
         """One scene end to end; returns (pred_box3d [K,8,3] | None, scores | None)."""
-        out = self.model(scene.model_input())
+        out = self.model(self._lean_input(scene))
         batch = {"ego": {"transformation_matrix": self.tfm, "anchor_box": self.anchor_box}}
         return self.post.post_process(batch, {"ego": out})
 
@@ -245,7 +254,7 @@ class ScenePipeline:
         from heal_amd import ops
         dir_args = self.post.params.get("dir_args", {"dir_offset": 0.7853, "num_bins": 2})
         anchors = self.post._anchors_f32(self.anchor_box, self.device)
-        out = self.model(inputs.model_input())
+        out = self.model(self._lean_input(inputs))
         return ops.decode_nms(out["cls_preds"], out["reg_preds"], out.get("dir_preds"), anchors,
                               self.post.params["target_args"]["score_threshold"], dir_args["dir_offset"],
                               dir_args["num_bins"], self.post.params["nms_thresh"],

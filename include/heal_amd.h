@@ -31,7 +31,8 @@ extern "C" {
                                    10: + heal_warp_att_fuse_levels (CoAlign multiscale fusion);
                                    11: + heal_disco_fuse (DiscoNet fusion);
                                    12: + heal_decode_nms_agents[_workspace] (late fusion: pooled decode + one NMS);
-                                   still 12: + heal_kd_kl_loss[_workspace] (DiscoNet distillation).  Purely additive -- no existing
+                                   still 12: + heal_kd_kl_loss[_workspace] (DiscoNet distillation), + heal_warp_fuse_levels_src (K5 on
+                                   per-agent source descriptors).  Purely additive -- no existing
                                    signature changed -- so the version was not raised: a library built before them passes the
                                    version check and fails at the missing symbol in _capi.call ("does not export") */
 
@@ -180,6 +181,27 @@ int heal_warp_fuse_levels(int n_levels, const float* const* feats_host, const fl
                           const int32_t* channels_host, const int32_t* h_host, const int32_t* w_host,
                           const double* affine_host, const double* affine_dev, int grid_f64, const int32_t* crop_host,
                           float* const* out_host, void* stream);
+
+/* heal_warp_fuse_levels_src: heal_warp_fuse_levels with every agent's map read IN PLACE -- no stacked [n_agents, C, H, W] tensor and no
+ *   zero padding of maps that are defined on a part of the grid only (camera agents).  src_host [n_levels][n_agents] (HOST array):
+ *     feat, occ      device pointers to element (y0, x0) of the agent's features / occupancy logits
+ *     feat_row, feat_plane, occ_row   strides in floats: feature (c, y, x) at feat[c feat_plane + (y - y0) feat_row + (x - x0)]
+ *     box            (y0, y1, x0, x1) in the level's map coordinates: where the agent's map is defined; outside it the map counts as
+ *                    zero (feature 0, score 0) and is never read.  A dense crop tensor and a window of a larger tensor are both of
+ *                    this form; a full map is box (0, H, 0, W).
+ *   Checked before anything is launched: an agent WITH a crop window (crop_host) needs window +- 1 (clipped to the map) inside its
+ *   box -- the condition under which the result is bit-identical to heal_warp_fuse_levels on the zero-padded stack; an agent
+ *   WITHOUT one needs the full box; strides multiples of 4 floats and (pointer - 4 x0 bytes) 16-byte aligned (column 0 of every map
+ *   row on a 16-byte boundary).  Everything else as heal_warp_fuse_levels (which is this kernel on full boxes).                    */
+typedef struct heal_k5_source {
+    const float* feat;
+    const float* occ;
+    int64_t feat_row, feat_plane, occ_row;
+    int32_t box[4];
+} heal_k5_source;
+int heal_warp_fuse_levels_src(int n_levels, const heal_k5_source* src_host, int n_agents, const int32_t* channels_host,
+                              const int32_t* h_host, const int32_t* w_host, const double* affine_host, const double* affine_dev,
+                              int grid_f64, const int32_t* crop_host, float* const* out_host, void* stream);
 
 /* heal_warp_att_fuse_levels: the multiscale fusion of HeterModelBaselineMs (heter_model_baseline_ms.py:199-207: one AttFusion or
  *   MaxFusion per level, all with the same normalised affine matrix) for every level of one scene in ONE launch.  Per ego pixel:
