@@ -184,6 +184,10 @@ _SIGNATURES = {
     "heal_nms_bev": (c_int, [c_void_p, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "heal_kd_kl_loss_workspace": (c_size_t, [c_int] * 4),
     "heal_kd_kl_loss": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "heal_eval_match_workspace": (c_size_t, [c_int, c_int]),
+    "heal_eval_match": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_size_t, c_void_p]),
 }
 
 

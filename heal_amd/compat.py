@@ -32,7 +32,7 @@ def install_as_opencood(force=False):
 # datasets, evaluation and visualisation code.  overlay_reference() keeps the reference's package and replaces, under
 # the reference's module names, only what this repo implements: the model files, the losses, the pcdet IoU/NMS API and
 # the voxel pre / post processors.  Nothing of spconv, the CUDA extensions or the Cython module is imported any more.
-_OVERLAY_LEAVES = ("pcdet_utils.iou3d_nms.iou3d_nms_utils",)
+_OVERLAY_LEAVES = ("pcdet_utils.iou3d_nms.iou3d_nms_utils", "utils.eval_utils")
 _OVERLAY_TREES = ("models", "loss")
 
 

@@ -1032,6 +1032,93 @@ def quad_iou(a, b):
     return out
 
 
+EVAL_MAX_DET, EVAL_MAX_GT, EVAL_MAX_THR = 1024, 256, 8
+
+
+def eval_match_supported(n, m, n_thr):
+    """The limits of heal_eval_match (capacities): n <= 1024 detections, m <= 256 ground-truth boxes, 1..8 thresholds."""
+    return 0 <= int(n) <= EVAL_MAX_DET and 0 <= int(m) <= EVAL_MAX_GT and 1 <= int(n_thr) <= EVAL_MAX_THR
+
+
+def _need_boxes(t, name, who):
+    t = _need(t, torch.float32, name)
+    if t.dim() != 3 or tuple(t.shape[1:]) not in ((8, 3), (4, 2)):
+        raise _capi.HealAmdError(f"{who}: {name} must be [n,8,3] or [n,4,2], got {tuple(t.shape)}")
+    return t, int(t.shape[1]) * int(t.shape[2])
+
+
+def _need_count(t, name, who, dev):
+    if t is None:
+        return None
+    t = _need(t, torch.int32, name)
+    if t.numel() != 1 or t.device != dev:
+        raise _capi.HealAmdError(f"{who}: {name} must be one int32 word on {dev}")
+    return t
+
+
+def eval_match(det, score, gt, thresholds, n_dev=None, m_dev=None, sync=True, want_gt_index=False, out=None):
+    """AP evaluation of one frame (heal_eval_match; eval_utils.py:40-91 caluclate_tp_fp for every threshold at once): detections
+    det [n,8,3] or [n,4,2] with score [n] against ground truth gt [m,8,3] or [m,4,2], all f32 cuda; thresholds: 1..8 floats,
+    passed by value.  n_dev / m_dev (int32 [1] cuda): the live counts, read on the device; n / m are then capacities and the
+    tails may hold anything -- decode_nms(sync=False)'s (corners, scores, count) are scored in place.
+    -> (order [n] i32, tp [T,n] u8, score_sorted [n] f32[, gt_index [T,n] i32]) in descending-score order.  sync=True slices
+    them to the live n (one host read of n_dev, none without it); sync=False returns the full-capacity buffers.
+    out: the APPEND form -- a dict of persistent buffers order [cap] i32, tp [T,cap] u8, score [cap] f32, optionally gt_index
+    [T,cap] i32, and the int32 words cursor, gt_total, overflow.  Rows go to offset `cursor`, which then advances by the live n
+    (gt_total by the live m); a frame that does not fit sets `overflow` and writes nothing.  Never reads on the host; returns out."""
+    who = "eval_match"
+    det, det_f = _need_boxes(det, "det", who)
+    gt, gt_f = _need_boxes(gt, "gt", who)
+    score = _need(score, torch.float32, "score")
+    n, m = int(det.shape[0]), int(gt.shape[0])
+    thr = [float(v) for v in thresholds]
+    T = len(thr)
+    if score.numel() != n:
+        raise _capi.HealAmdError(f"{who}: {score.numel()} scores for {n} detections")
+    if not eval_match_supported(n, m, T):
+        raise _capi.HealAmdError(f"{who}: {n} detections x {m} ground-truth boxes x {T} thresholds exceeds the kernel's limits "
+                                 f"({EVAL_MAX_DET} x {EVAL_MAX_GT} x 1..{EVAL_MAX_THR})")
+    dev = det.device
+    if gt.device != dev or score.device != dev:
+        raise _capi.HealAmdError(f"{who}: det, score and gt must be on one device")
+    n_dev = _need_count(n_dev, "n_dev", who, dev)
+    m_dev = _need_count(m_dev, "m_dev", who, dev)
+    null = ctypes.c_void_p(0)
+    if out is None:
+        order = torch.empty((n,), dtype=torch.int32, device=dev)
+        tp = torch.empty((T, n), dtype=torch.uint8, device=dev)
+        sorted_score = torch.empty((n,), dtype=torch.float32, device=dev)
+        gi = torch.empty((T, n), dtype=torch.int32, device=dev) if want_gt_index else None
+        stride, cur, tot, ovf = n, null, null, null
+    else:
+        order, tp, sorted_score, gi = out["order"], out["tp"], out["score"], out.get("gt_index")
+        stride = int(order.numel())
+        for name, t, dt, shape in (("order", order, torch.int32, (stride,)), ("tp", tp, torch.uint8, (T, stride)),
+                                   ("score", sorted_score, torch.float32, (stride,)), ("gt_index", gi, torch.int32, (T, stride)),
+                                   ("cursor", out["cursor"], torch.int32, None), ("gt_total", out["gt_total"], torch.int32, None),
+                                   ("overflow", out["overflow"], torch.int32, None)):
+            if t is None and name == "gt_index":
+                continue
+            if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or not t.is_contiguous()
+                    or (tuple(t.shape) != shape if shape is not None else t.numel() != 1)):
+                raise _capi.HealAmdError(f"{who}: out['{name}'] must be a contiguous {dt} tensor on {dev}"
+                                         + (f" of shape {shape}" if shape is not None else " of one element"))
+        cur, tot, ovf = _ptr(out["cursor"]), _ptr(out["gt_total"]), _ptr(out["overflow"])
+    nbytes = _capi.query("heal_eval_match_workspace", n, m)
+    ws = _workspace("eval_match", nbytes, dev)
+    with _Timed("eval_match"):
+        _capi.call("heal_eval_match", _ptr(det), det_f, n, _ptr(n_dev), _ptr(score), _ptr(gt), gt_f, m, _ptr(m_dev),
+                   _host_array(thr, ctypes.c_float), T, _ptr(order), _ptr(tp), _ptr(gi), _ptr(sorted_score), stride,
+                   cur, tot, ovf, _ptr(ws), ws.numel(), _stream())
+    if out is not None:
+        return out
+    if sync and n_dev is not None:
+        k = max(0, min(int(n_dev.item()), n))
+        order, tp, sorted_score = order[:k], tp[:, :k], sorted_score[:k]
+        gi = gi[:, :k] if gi is not None else None
+    return (order, tp, sorted_score, gi) if want_gt_index else (order, tp, sorted_score)
+
+
 _WINDOW_ATTN_SHAPES = {(4, 16), (8, 32), (16, 64), (4, 32), (8, 16), (8, 64), (4, 64)}
 
 

@@ -32,7 +32,7 @@ extern "C" {
                                    11: + heal_disco_fuse (DiscoNet fusion);
                                    12: + heal_decode_nms_agents[_workspace] (late fusion: pooled decode + one NMS);
                                    still 12: + heal_kd_kl_loss[_workspace] (DiscoNet distillation), + heal_warp_fuse_levels_src (K5 on
-                                   per-agent source descriptors).  Purely additive -- no existing
+                                   per-agent source descriptors), + heal_eval_match[_workspace] (AP evaluation).  Purely additive -- no existing
                                    signature changed -- so the version was not raised: a library built before them passes the
                                    version check and fails at the missing symbol in _capi.call ("does not export") */
 
@@ -309,6 +309,40 @@ int heal_decode_nms_agents(int n_agents, const float* const* cls_host, const flo
  * Same arithmetic as the NMS above (common_utils.py:230-251 compute_iou).  a [n,4,2], b [m,4,2],
  * iou [n,m].                                                                                       */
 int heal_quad_iou(const float* a, int n, const float* b, int m, float* iou, void* stream);
+
+/* heal_eval_match: the per-frame step of AP evaluation -- pairwise footprint IoU and the greedy TP / FP match, for up to 8 IoU
+ *   thresholds at once, read from and written to device buffers.
+ * Replaces: opencood/utils/eval_utils.py:40-91 (caluclate_tp_fp) with opencood/utils/common_utils.py:230-270 (convert_format,
+ *           compute_iou: shapely) inside it; the reference runs it once per threshold (tools/inference.py:171-185).
+ *   det [n,8,3] (det_floats_per_box = 24) or [n,4,2] (8); gt likewise; the footprint is corners 0..3, x and y (convert_format).
+ *   det_score [n].  n_dev / m_dev: when non-NULL, int32 device words holding the LIVE counts, read by the kernels (clamped to
+ *   0..n / 0..m); n / m are then the capacities of the buffers, whose tail may hold anything.  So the output of
+ *   heal_decode_nms (out_corners, out_scores, out_count) is scored in place, and a replayed HIP graph follows the frame loaded.
+ *   Limits: n <= 1024, m <= 256, 1 <= n_thr <= 8 (thr_host: HOST floats, passed by value); anything else is an error.
+ *   Semantics, per threshold t, the reference's: detections are walked in descending score; the IoU is taken against the
+ *   ground-truth boxes still unmatched; if none is left or the maximum is < thr[t] (compared in fp32) the detection is FP,
+ *   otherwise TP, and the FIRST maximum in original ground-truth order is removed for every later detection -- which may still
+ *   match a different box (unlike the VOC variant that looks at its best box only).
+ *   Equal scores go by ascending detection index (-0 == +0).  The reference's order on ties is np.argsort's, which is
+ *   implementation-defined.  A NaN score is ordered by its bit pattern (deterministic, not the reference's "last").
+ *   Documented deviation: a NaN IoU (a zero-area pair, 0 / 0; the reference raises ZeroDivisionError or propagates NaN depending
+ *   on the shapely version) counts as 0.
+ *   Outputs, in sorted order, rank r < live n: out_order[r] the detection index, out_score_sorted[r], out_tp[t*out_stride + r]
+ *   (1 = TP, 0 = FP), out_gt_index[t*out_stride + r] the original ground-truth index or -1 (out_gt_index may be NULL).
+ *   Plain form (cursor_dev NULL): rows at offset 0, out_stride >= n; gt_total_dev / overflow_dev are not touched.
+ *   Append form (cursor_dev non-NULL; gt_total_dev and overflow_dev then too): rows are written at offset *cursor_dev, then
+ *   *cursor_dev advances by the live n and *gt_total_dev by the live m.  If *cursor_dev + n > out_stride nothing is written,
+ *   nothing advances and *overflow_dev is set to 1; the kernels never clear it.
+ *   ws: heal_eval_match_workspace(n, m) bytes (the capacities): the IoU matrix and its row maxima.  Two kernels, no memset /
+ *   memcpy node, no atomics: repeated launches are bit-equal.                                                              */
+size_t heal_eval_match_workspace(int n_cap, int m_cap);
+int heal_eval_match(const float* det, int det_floats_per_box, int n, const int32_t* n_dev,
+                    const float* det_score,
+                    const float* gt, int gt_floats_per_box, int m, const int32_t* m_dev,
+                    const float* thr_host, int n_thr,
+                    int32_t* out_order, uint8_t* out_tp, int32_t* out_gt_index, float* out_score_sorted,
+                    int out_stride, int32_t* cursor_dev, int32_t* gt_total_dev, int32_t* overflow_dev,
+                    void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K4  Lift-Splat frustum -> BEV pooling, fused with the depth softmax and the outer product.
