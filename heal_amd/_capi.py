@@ -23,6 +23,7 @@ _SIGNATURES = {
     "heal_fill_bytes": (c_int, [c_void_p, c_int, c_size_t, c_void_p]),
     "heal_next_launch_events": (c_int, [c_void_p, c_void_p]),
     "heal_voxelize_workspace": (c_size_t, [c_int, c_int, c_int, ctypes.c_longlong]),
+    "heal_voxelize_layout": (c_int, [c_int, c_int, c_int, ctypes.c_longlong, c_void_p]),
     "heal_voxelize": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "heal_voxelize_batch_workspace": (c_size_t, [c_int, c_int, c_int, c_int, ctypes.c_longlong]),

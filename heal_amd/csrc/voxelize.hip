@@ -472,6 +472,8 @@ struct VoxWs {
     unsigned long long *tile_pub, *part_pub;     // published tile sums / agent-boundary partial counts (all-ones: unpublished)
     uint32_t tcap;
     size_t clean_bytes;     // tmin | tcnt | tseg | tkey | tile_pub | part_pub: all-ones between calls (self-cleaning); meta follows (zero-initialised)
+    // Up to and including meta the carve depends on (table slots, dense or hash) alone -- tile_pub has its fixed maximum -- so any call on
+    // that table finds a clean workspace clean, whatever its n, rows and P; what follows meta is scratch that a call writes before it reads.
 };
 
 static uint32_t table_cap(int n) {
@@ -498,10 +500,11 @@ static bool carve(Arena& a, int n, int cap, int P, long long agents_x_cells, Vox
     w.tcnt = a.take<uint32_t>(w.tcap);
     w.tseg = a.take<uint32_t>(w.tcap);
     w.tkey = a.take<uint32_t>(table_dense(agents_x_cells) ? 1 : w.tcap);
-    w.tile_pub = a.take<unsigned long long>(ceil_div(n, VOX_TILE) + 1);
+    w.tile_pub = a.take<unsigned long long>(VOX_MAX_TILES + 1);
     w.part_pub = a.take<unsigned long long>(VOX_MAX_BATCH + 1);
     w.meta = a.take<int>(64);
     w.clean_bytes = (size_t)((char*)w.meta - (char*)w.tmin);
+    // ---- scratch of this call ----
     w.cand = a.take<uint32_t>(P > 64 ? (size_t)cap * P : 1);
     w.tvid = a.take<uint32_t>(P > 64 ? w.tcap : 1);
     w.st = a.take<int2>(n);
@@ -583,14 +586,30 @@ static bool vox_grid(const float* range_host, const float* voxel_size_host, VoxG
 
 using namespace heal;
 
-extern "C" size_t heal_voxelize_workspace(int n_points, int max_points, int max_voxels, long long agents_x_cells) {
+// the carve of a call with these sizes, as offsets (a null arena); -> the bytes a workspace needs for it
+static size_t carve_bytes(int n_points, long long rows, int max_points, long long agents_x_cells, VoxWs& w) {
     if (n_points < 1) n_points = 1;
-    int cap = n_points < max_voxels ? n_points : max_voxels;
-    if (cap < 1) cap = 1;
+    if (rows > n_points) rows = n_points;
     Arena a(nullptr, 0);
-    VoxWs w;
-    carve(a, n_points, cap, max_points < 1 ? 1 : max_points, agents_x_cells, w);
+    carve(a, n_points, rows < 1 ? 1 : (int)rows, max_points < 1 ? 1 : max_points, agents_x_cells, w);
     return a.off + 256;
+}
+
+extern "C" int heal_voxelize_layout(int n_points, int rows, int max_points, long long agents_x_cells, size_t* out) {
+    HEAL_REQUIRE(out != nullptr, "voxelize_layout: out is NULL");
+    VoxWs w;
+    out[5] = carve_bytes(n_points, rows, max_points, agents_x_cells, w);
+    out[0] = w.tcap;
+    out[1] = table_dense(agents_x_cells) ? 1 : 0;
+    out[2] = (size_t)(uintptr_t)w.tmin;
+    out[3] = w.clean_bytes;
+    out[4] = (size_t)(uintptr_t)w.meta;
+    return 0;
+}
+
+extern "C" size_t heal_voxelize_workspace(int n_points, int max_points, int max_voxels, long long agents_x_cells) {
+    VoxWs w;
+    return carve_bytes(n_points, max_voxels, max_points, agents_x_cells, w);
 }
 
 namespace heal {
@@ -664,15 +683,10 @@ extern "C" int heal_voxelize(const float* points, int n_points, const float* ran
 
 extern "C" size_t heal_voxelize_batch_workspace(int n_points_total, int n_agents, int max_points, int max_voxels,
                                                 long long agents_x_cells) {
-    if (n_points_total < 1) n_points_total = 1;
-    (void)n_agents;
-    Arena a(nullptr, 0);
     VoxWs w;
     // rows: sum_b min(n_b, max_voxels) <= min(n_total, n_agents * max_voxels)
-    long long cap = (long long)(n_agents < 1 ? 1 : n_agents) * (max_voxels < 1 ? 1 : max_voxels);
-    if (cap > n_points_total) cap = n_points_total;
-    carve(a, n_points_total, (int)cap, max_points < 1 ? 1 : max_points, agents_x_cells, w);
-    return a.off + 256;
+    return carve_bytes(n_points_total, (long long)(n_agents < 1 ? 1 : n_agents) * (max_voxels < 1 ? 1 : max_voxels), max_points,
+                       agents_x_cells, w);
 }
 
 extern "C" int heal_voxelize_batch(const float* points, const int32_t* point_offsets_host, int n_agents,

@@ -255,8 +255,9 @@ def _host_array(values, ctype):
 
 
 # ------------------------------------------------------------------------------------------------
-# K1's per-cell table is self-cleaning (round 6): a workspace that a finished call left behind needs no fill.  One workspace per
-# (stream, layout) -- a call with other sizes carves the buffer differently -- and the set of buffers known to be clean.
+# K1's per-cell table is self-cleaning: a workspace that a finished call left behind needs no fill.  What persists in it is laid out by
+# the table alone (heal_voxelize_layout), so there is ONE workspace per (stream, table slots, table kind) whatever the point count, and
+# the scratch behind the table grows with the clouds.  _VOX_CLEAN: the (data_ptr, numel) of the buffers known to be clean.
 _VOX_CLEAN = set()
 
 
@@ -268,21 +269,28 @@ def _vox_cells(lidar_range, voxel_size):
     return max(c, 0)
 
 
-def _vox_workspace(kind, nbytes, dev, layout):
-    ws = _workspace(("voxelize", kind) + tuple(layout), nbytes, dev)
-    return ws, (ws.data_ptr(), ws.numel(), kind) + tuple(layout)
-
-
-def _vox_call(name, key, *args):
-    """Call a voxelize entry point with tables_clean from the bookkeeping; any failure leaves the workspace 'unknown'."""
-    clean = key in _VOX_CLEAN
-    _VOX_CLEAN.discard(key)
-    _capi.call(name, *args[:-1], 1 if clean else 0, args[-1])
+def _vox_chain(name, dev, n, n_agents, max_points, max_voxels, agents_x_cells, *args):
+    """Call heal_voxelize / heal_voxelize_batch (`args`: everything in front of ws) on the workspace of its table, with tables_clean
+    from the bookkeeping; any failure leaves the workspace 'unknown'."""
+    lay = (ctypes.c_size_t * 6)()
+    _capi.call("heal_voxelize_layout", n, 1, max_points, agents_x_cells, lay)
+    # sized for the next power of two of points (the carve is monotone in points and rows, so the call fits): a buffer is outgrown at
+    # most once per doubling, and what _workspace retires on the way stays below the size of the live one
+    capacity = max(1024, 1 << max(n - 1, 0).bit_length())
+    nbytes = _capi.query("heal_voxelize_batch_workspace", capacity, n_agents, max_points, max_voxels, agents_x_cells)
+    ws = _workspace(("voxelize", int(lay[0]), bool(lay[1])), nbytes, dev)
+    ident = (ws.data_ptr(), ws.numel())
+    clean = ident in _VOX_CLEAN
+    if not clean:       # first use of this buffer: forget the one it replaced, if any (retired, it is never called again)
+        _VOX_CLEAN.intersection_update({(b.data_ptr(), b.numel()) for b in _WS.values()})
+    _VOX_CLEAN.discard(ident)
+    with _Timed("voxelize"):
+        _capi.call(name, *args, _ptr(ws), ws.numel(), 1 if clean else 0, _stream())
     # A call RECORDED into a graph has not run: if it carries the initial fill (workspace first seen inside a capture), the tables are
     # clean only once that graph has been replayed -- later calls must not rely on it, so the workspace stays 'unknown' (every capture
     # then carries its own fill; the first eager call settles it).
     if clean or not torch.cuda.is_current_stream_capturing():
-        _VOX_CLEAN.add(key)
+        _VOX_CLEAN.add(ident)
 
 
 def voxelize(points, lidar_range, voxel_size, max_points, max_voxels, batch_idx=0, sync=True):
@@ -301,14 +309,11 @@ def voxelize(points, lidar_range, voxel_size, max_points, max_voxels, batch_idx=
     coords = torch.empty((cap, 4), dtype=torch.int32, device=dev)
     num = torch.empty((cap,), dtype=torch.int32, device=dev)
     count = torch.zeros((1,), dtype=torch.int32, device=dev)
-    cells = _vox_cells(lidar_range, voxel_size)
-    nbytes = _capi.query("heal_voxelize_workspace", n, int(max_points), int(max_voxels), cells)
-    ws, key = _vox_workspace("one", nbytes, dev, (n, int(max_points), int(max_voxels), cells))
     rng = _host_array([float(v) for v in lidar_range], ctypes.c_float)
     vs = _host_array([float(v) for v in voxel_size], ctypes.c_float)
-    with _Timed("voxelize"):
-        _vox_call("heal_voxelize", key, _ptr(points), n, rng, vs, int(max_points), int(max_voxels), int(batch_idx),
-                  _ptr(voxels), _ptr(coords), _ptr(num), _ptr(count), None, None, _ptr(ws), ws.numel(), _stream())
+    _vox_chain("heal_voxelize", dev, n, 1, int(max_points), int(max_voxels), _vox_cells(lidar_range, voxel_size),
+               _ptr(points), n, rng, vs, int(max_points), int(max_voxels), int(batch_idx),
+               _ptr(voxels), _ptr(coords), _ptr(num), _ptr(count), None, None)
     if not sync:
         return voxels, coords, num, count
     m = int(count.item())
@@ -355,26 +360,19 @@ def voxelize_collated(point_list, lidar_range, voxel_size, max_points, max_voxel
         adjacent = all(p.is_contiguous() for p in pts) and all(
             pts[i].data_ptr() + pts[i].numel() * 4 == pts[i + 1].data_ptr() for i in range(len(pts) - 1))
         allp = pts[0] if (len(pts) == 1 or adjacent) else torch.cat(pts, 0)
-        axc = len(pts) * _vox_cells(lidar_range, voxel_size)
-        nbytes = _capi.query("heal_voxelize_batch_workspace", bounds[-1], len(pts), int(max_points), int(max_voxels), axc)
-        # (the carve depends on the total point count, the row capacity = sum of min(n_b, max_voxels), max_points and the table kind)
-        ws, key = _vox_workspace("batch", nbytes, dev, (bounds[-1], cap, int(max_points), axc))
-        with _Timed("voxelize"):
-            _vox_call("heal_voxelize_batch", key, _ptr(allp), _host_array(bounds, ctypes.c_int32), len(pts), rng, vs,
-                      int(max_points), int(max_voxels), _ptr(voxels), _ptr(coords), _ptr(num), _ptr(offsets), _ptr(ws),
-                      ws.numel(), _stream())
+        _vox_chain("heal_voxelize_batch", dev, bounds[-1], len(pts), int(max_points), int(max_voxels),
+                   len(pts) * _vox_cells(lidar_range, voxel_size),
+                   _ptr(allp), _host_array(bounds, ctypes.c_int32), len(pts), rng, vs, int(max_points), int(max_voxels),
+                   _ptr(voxels), _ptr(coords), _ptr(num), _ptr(offsets))
         _remember("voxelize", lambda: voxelize_collated(point_list, lidar_range, voxel_size, max_points, max_voxels))
         return voxels, coords, num, offsets
     counts = torch.zeros((len(pts),), dtype=torch.int32, device=dev)
+    cells = _vox_cells(lidar_range, voxel_size)
     for b, p in enumerate(pts):
         n = int(p.shape[0])
-        cells = _vox_cells(lidar_range, voxel_size)
-        nbytes = _capi.query("heal_voxelize_workspace", n, int(max_points), int(max_voxels), cells)
-        ws, key = _vox_workspace("one", nbytes, dev, (n, int(max_points), int(max_voxels), cells))
-        with _Timed("voxelize"):
-            _vox_call("heal_voxelize", key, _ptr(p), n, rng, vs, int(max_points), int(max_voxels), b, _ptr(voxels),
-                      _ptr(coords), _ptr(num), _ptr(counts[b:b + 1]), _ptr(offsets[b:b + 1]),
-                      _ptr(offsets[b + 1:b + 2]), _ptr(ws), ws.numel(), _stream())
+        _vox_chain("heal_voxelize", dev, n, 1, int(max_points), int(max_voxels), cells,
+                   _ptr(p), n, rng, vs, int(max_points), int(max_voxels), b, _ptr(voxels), _ptr(coords), _ptr(num),
+                   _ptr(counts[b:b + 1]), _ptr(offsets[b:b + 1]), _ptr(offsets[b + 1:b + 2]))
     return voxels, coords, num, offsets
 
 
@@ -1417,7 +1415,6 @@ def _frustum_separable(frustum):
 
 
 def bev_pool_pm_supported(D, fH, C):
-    import os
     mtot = (D + 15) // 16 * 16
     fh4 = (fH + 3) // 4 * 4
     lds = (fh4 * (C + 16) + 2 * mtot * 66) * 4   # LssLds, bev_pool.hip
@@ -2194,7 +2191,6 @@ def grouped_conv3x3(x, weight, bias, groups, stride=1, relu=True):
     98, 256 ch 128^2 84 -> 59, 512 ch 64^2 78 -> 49, stride 2: 256 ch 256^2 207 -> 107, 512 ch 128^2 122 -> 68);
     HEAL_GCONV_MFMA=16 | 8 selects the older 16x16x4 kernel (one m-tile per 16-channel group: 53 us; pairs of 8-channel groups
     with block-diagonal weights: 98 us), =0 the vector-ALU stencil, which also takes the shapes the MFMA kernels do not."""
-    import os
     x = _need(x, torch.float32, "x")
     weight = _need(weight, torch.float32, "weight")
     n, C, H, W = (int(v) for v in x.shape)
@@ -2519,7 +2515,6 @@ def conv3x3_winograd_waves(n=1, cout=64, H=256, W=256):
     """Waves per Winograd block: 8 (16x16-pixel tiles, one block per CU: best operand reuse) when that still gives every CU two
     or more blocks, else 4 (8x16-pixel tiles, two independent blocks per CU whose transform / MFMA phases overlap; measured
     crossover, scripts/conv3x3_bench.py); HEAL_WG_WAVES overrides."""
-    import os
     e = os.environ.get("HEAL_WG_WAVES", "")
     if e in ("4", "8"):
         return int(e)
@@ -2531,7 +2526,6 @@ def conv3x3_winograd_kc(cin, waves, H=1, W=1):
     """Input channels per chunk of the Winograd K loop: 16 where the kernel has it (an experimental build, 8-wave blocks,
     cin % 16 == 0, a map whose 16-channel chunk stays below 2^31 bytes) and HEAL_WG_KC asks for it, else 8.  Measured in round 5
     (profiles/r05_wino_kc16.txt): 4-13 % slower, hence experimental."""
-    import os
     want = os.environ.get("HEAL_WG_KC", _WG_KC_DEFAULT)
     ok16 = (want == "16" and waves == 8 and cin % 16 == 0 and 16 * H * W * 4 < 2 ** 31 and experimental_build())
     return 16 if ok16 else 8
@@ -2583,7 +2577,6 @@ def conv3x3_winograd4_ok(n, cout, H, W):
     """F(4x4,3x3) (heal_conv3x3_winograd4) is OPT-IN: HEAL_C3_ALGO=winograd4.  Measured 0.80 - 1.03x of F(2x2,3x3) at the scenes'
     shapes (profiles/r03_wino_f44_vs_f22.json): a quarter of the multiplications instead of 4/9, but twice the transform work per
     output at 32 output channels per block."""
-    import os
     return os.environ.get("HEAL_C3_ALGO", "") == "winograd4" and experimental_build()
 
 
@@ -2591,7 +2584,6 @@ def conv3x3_algo(stride, n=1, cout=64, H=256, W=256):
     """'winograd' | 'direct' for a shape; HEAL_C3_ALGO overrides for A/B.  Winograd F(2x2,3x3) is the stride-1 formulation
     and runs one 8-wave block per CU on a 16x16-pixel x 64-channel tile: below ~one block per CU the implicit GEMM with its
     smaller tiles fills the chip better (measured crossover ~100 blocks, scripts/conv3x3_bench.py)."""
-    import os
     a = os.environ.get("HEAL_C3_ALGO", "")
     if stride != 1 or a == "direct":
         return "direct"
@@ -2602,7 +2594,6 @@ def conv3x3_algo(stride, n=1, cout=64, H=256, W=256):
 
 
 def conv_gemm_supported(cin, cout, Wo):
-    import os
     return cout % 128 == 0 and cin % 32 == 0 and Wo % 4 == 0 and os.environ.get("HEAL_CONV_GEMM", "1") == "1"
 
 

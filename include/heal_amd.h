@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define HEAL_AMD_ABI_VERSION 12  /* 6 (round 6): + heal_pfn_pillars / heal_pillar_canvas / heal_pillar_stem_block; the measured-negative entry
+#define HEAL_AMD_ABI_VERSION 13  /* 6 (round 6): + heal_pfn_pillars / heal_pillar_canvas / heal_pillar_stem_block; the measured-negative entry
                                    points moved to include/heal_amd_experimental.h (HEAL_BUILD_EXPERIMENTAL=1 builds only);
                                    8: + heal_agent_window_attention / heal_agent_mean (CoBEVT fusion);
                                    9: + heal_v2v_message[_workspace] / heal_gru_zero_state (V2VNet fusion);
@@ -34,7 +34,8 @@ extern "C" {
                                    still 12: + heal_kd_kl_loss[_workspace] (DiscoNet distillation), + heal_warp_fuse_levels_src (K5 on
                                    per-agent source descriptors), + heal_eval_match[_workspace] (AP evaluation).  Purely additive -- no existing
                                    signature changed -- so the version was not raised: a library built before them passes the
-                                   version check and fails at the missing symbol in _capi.call ("does not export") */
+                                   version check and fails at the missing symbol in _capi.call ("does not export");
+                                   13: + heal_voxelize_layout, and K1's ws / tables_clean contract now holds across point counts */
 
 int heal_abi_version(void);
 const char* heal_last_error(void);
@@ -65,14 +66,23 @@ int heal_next_launch_events(void* start_event, void* stop_event);
  *   row_offset / row_offset_next  device i32 or NULL: collate_batch_list without a host round trip -- this agent's
  *               rows go to [*row_offset, *row_offset + M) of voxels/coords/num_points (buffers shared by the agents
  *               of a modality) and *row_offset_next <- *row_offset + M feeds the next agent's call.
- *   ws / tables_clean  round 6: the per-cell table inside the workspace is SELF-CLEANING -- the chain's last kernel resets every record it
- *               used -- so only the FIRST call on a workspace has to initialise it: tables_clean = 0 "contents unknown" (the call fills the
- *               tables first: two more launches), 1 "the previous call on this workspace used the same (n_points, max_points, max_voxels)
- *               and ran to completion" (no fill; three kernels).  A call with other sizes carves the workspace differently: pass 0 again.
+ *   ws / tables_clean  the per-cell table inside the workspace is SELF-CLEANING -- the chain's last kernel resets every record and every
+ *               publication word it used -- so only the FIRST call on a workspace has to initialise it.  The part of the workspace that
+ *               persists between calls (the table, the publication words, the generation counters) is laid out by the table alone:
+ *               its slots and its kind, dense or hash (heal_voxelize_layout reports both); what depends on n_points, the rows or
+ *               max_points lies behind it and is scratch.  tables_clean = 0: "contents unknown" (the call fills the persistent part
+ *               first: two more launches).  tables_clean = 1: "the previous call on this workspace -- heal_voxelize or
+ *               heal_voxelize_batch, with any n_points, rows and max_points -- ran to completion and used the same table slots and the
+ *               same table kind" (no fill; three kernels).  A workspace only has to be large enough for the call at hand.
  * -----------------------------------------------------------------------------------------------*/
 /* agents_x_cells (size queries): agents x grid cells of the call, or 0.  Grids of up to 2^21 cells in total (every PointPillars grid: 3 agents
  *   at 512 x 512 = 786 432) then get a per-cell table instead of a hash grid -- no key, no probe; free per call because the table cleans itself. */
 size_t heal_voxelize_workspace(int n_points, int max_points, int max_voxels, long long agents_x_cells);
+/* heal_voxelize_layout: how a call with these sizes (rows = those of its outputs) carves its workspace, from the carve the chain itself uses.
+ *   out [6] (host): table slots | 1 dense table, 0 hash grid | offset and bytes of the part that is all-ones between calls | offset of the
+ *   generation counters right behind it | bytes the workspace needs.  The first five depend on (table slots, kind) alone; the bytes grow
+ *   monotonically with n_points and rows.                                                                                              */
+int heal_voxelize_layout(int n_points, int rows, int max_points, long long agents_x_cells, size_t* out);
 int heal_voxelize(const float* points, int n_points,
                   const float* range_host, const float* voxel_size_host,
                   int max_points, int max_voxels, int batch_idx,

@@ -55,6 +55,47 @@ def test_product_never_imports_oracle():
                 assert "/root/reference" not in text, os.path.join(dirpath, f)
 
 
+def _vox_layout(n, rows, P, axc):
+    from heal_amd import _capi
+    out = (ctypes.c_size_t * 6)()
+    _capi.call("heal_voxelize_layout", n, rows, P, axc, out)
+    return dict(zip(("slots", "dense", "clean_off", "clean_bytes", "meta_off", "total"), (int(v) for v in out)))
+
+
+@pytest.mark.parametrize("axc,dense", [(3 * 400, 1), (3 * 512 * 512, 1), (0, 0), (400 * 400 * 80, 0)],
+                         ids=["dense-3x400", "dense-3x512x512", "hash-unsized", "hash-12.8M-cells"])
+def test_voxelize_workspace_layout_depends_on_the_table_alone(axc, dense):
+    """What persists in K1's workspace between calls (the all-ones region and the meta words right behind it) is placed by (table slots,
+    dense or hash) alone, the total grows monotonically with points and rows, and the size the Python layer asks for -- the size query
+    at the next power of two of points -- holds every call below that capacity."""
+    from heal_amd import _capi
+    NS, PS = (1, 63, 1024, 1025, 4097, 70_000, 1_000_000), (1, 32, 64, 65, 200)
+    lay = {(n, r, P): _vox_layout(n, r, P, axc) for n in NS for r in (1, 37, n) for P in PS}
+    classes = {}
+    for (n, r, P), L in lay.items():
+        assert L["dense"] == dense and L["slots"] == (axc if dense else max(1024, 2 * (1 << (n - 1).bit_length())))
+        assert L["meta_off"] == L["clean_off"] + L["clean_bytes"] and L["meta_off"] + 256 <= L["total"]
+        # the region holds the table words (3 per slot, 4 with hash keys) and the publication words of the largest call
+        assert L["clean_bytes"] >= 4 * L["slots"] * (3 if dense else 4) + 8 * (4096 + 1 + 16 + 1)
+        classes.setdefault((L["slots"], L["dense"]), set()).add((L["clean_off"], L["clean_bytes"], L["meta_off"]))
+    assert all(len(v) == 1 for v in classes.values()), classes
+    assert len(classes) == (1 if dense else len({max(1024, 2 * (1 << (n - 1).bit_length())) for n in NS}))
+    for (n1, r1, P), a in lay.items():
+        for (n2, r2, P2), b in lay.items():
+            if P2 == P and n1 <= n2 and min(r1, n1) <= min(r2, n2):
+                assert a["total"] <= b["total"], ((n1, r1), (n2, r2), P)
+    for n in NS + (512, 513, 2048, 65_536, 65_537):
+        capacity = max(1024, 1 << (n - 1).bit_length())
+        for P in PS:
+            for mv in (1, 37, 50, 70_000):
+                one = _capi.query("heal_voxelize_workspace", capacity, P, mv, axc)
+                assert one >= _vox_layout(n, min(n, mv), P, axc)["total"], (n, P, mv)
+                for agents in (1, 3, 16):
+                    got = _capi.query("heal_voxelize_batch_workspace", capacity, agents, P, mv, axc)
+                    assert got >= _vox_layout(n, min(n, agents * mv), P, axc)["total"], (n, P, mv, agents)
+                    assert agents > 1 or got == one        # the single-cloud form is the one-agent batch: they share a buffer
+
+
 # ------------------------------------------------------------------------------------- host mirror
 def test_state_dict_keys_match_reference():
     from heal_amd import configs

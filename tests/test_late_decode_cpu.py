@@ -17,11 +17,11 @@ def test_abi_12_declares_and_exports_the_agents_entry_points():
     for name in NEW_SYMBOLS:
         assert name in declared, f"{name} is not declared in include/heal_amd.h"
         assert name in _capi._SIGNATURES, f"{name} has no ctypes signature"
-    assert _capi.abi_version_of_header() == 12
+    assert _capi.abi_version_of_header() == 13
     from heal_amd import build
     build.build()
     lib = _capi.lib()
-    assert int(lib.heal_abi_version()) == 12
+    assert int(lib.heal_abi_version()) == 13
     for name in NEW_SYMBOLS:
         assert hasattr(lib, name), f"libheal_amd.so does not export {name}"
     header = open(_capi.HEADER).read()
