@@ -185,6 +185,15 @@ _SIGNATURES = {
     "heal_nms_bev": (c_int, [c_void_p, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "heal_kd_kl_loss_workspace": (c_size_t, [c_int] * 4),
     "heal_kd_kl_loss": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "heal_det_loss_workspace": (c_size_t, [c_int] * 4),
+    "heal_det_loss": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_float] * 6 + [c_void_p, ctypes.c_double] + [c_void_p] * 5
+                      + [c_size_t, c_void_p]),
+    "heal_occ_loss_workspace": (c_size_t, [c_int] * 4 + [c_void_p]),
+    "heal_occ_loss": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                              c_size_t, c_void_p]),
+    "heal_depth_focal_loss_workspace": (c_size_t, [c_int] * 4),
+    "heal_depth_focal_loss": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     "heal_eval_match_workspace": (c_size_t, [c_int, c_int]),
     "heal_eval_match": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,

@@ -1,13 +1,16 @@
 """Detection losses of the anchor heads (training side; reference: opencood/loss/point_pillar_loss.py:14-244).
 
-Host-side torch code in the reference and here (no native op on either side): sigmoid focal loss on the anchor
-scores, smooth-L1 with the sin-difference yaw encoding on the box deltas, softmax cross-entropy on the direction bins.
+Host-side torch code in the reference: sigmoid focal loss on the anchor scores, smooth-L1 with the sin-difference yaw
+encoding on the box deltas, softmax cross-entropy on the direction bins.  Here the same composition, and -- for CUDA fp32
+maps with gamma = 2, two direction bins and no IoU branch (ops.det_loss_supported; HEAL_LOSS_FUSED=0 turns it off) -- one
+pass of heal_det_loss that writes the three terms and their gradients.
 Same constructor `args` (the yaml `loss.args` subtree), `forward(output_dict, target_dict, suffix="")`, `loss_dict`
 bookkeeping and `logging` signature.  The optional IoU branch (:99-117) is kept with the reference's key spelling."""
 import numpy as np
 import torch
 import torch.nn as nn
 
+from heal_amd import ops
 from heal_amd.opencood.data_utils.post_processor.voxel_postprocessor import resolve_deferred_labels
 from heal_amd.opencood.utils.common_utils import limit_period
 
@@ -82,6 +85,9 @@ class PointPillarLoss(nn.Module):
         for old, new in (('psm', 'cls_preds'), ('rm', 'reg_preds'), ('dm', 'dir_preds')):  # old-style head names
             if f'{old}{suffix}' in output_dict:
                 output_dict[f'{new}{suffix}'] = output_dict[f'{old}{suffix}']
+        fused = self._forward_fused(output_dict, target_dict, batch_size, suffix)
+        if fused is not None:
+            return fused
         total_loss = 0
 
         cls_weights = positives * self.pos_cls_weight + negatives * 1.0
@@ -123,6 +129,38 @@ class PointPillarLoss(nn.Module):
 
         total_loss += reg_loss + cls_loss
         self.loss_dict.update({'total_loss': total_loss.item(), 'reg_loss': reg_loss.item(), 'cls_loss': cls_loss.item()})
+        return total_loss
+
+    def _forward_fused(self, output_dict, target_dict, batch_size, suffix):
+        """The same three terms from heal_det_loss (one pass over the head maps, gradients written by the forward), where
+        ops.det_loss_supported holds; None otherwise.  loss_dict is filled from ONE device-to-host copy of the terms; the total
+        is added on the host in the composition's order and precision."""
+        cls_preds, reg_preds = output_dict[f'cls_preds{suffix}'], output_dict[f'reg_preds{suffix}']
+        dir_preds = None
+        if self.dir:
+            dir_preds = output_dict.get(f'dir_preds{suffix}')
+            if dir_preds is None:
+                return None
+        dir_args = self.dir['args'] if self.dir else {}
+        if not ops.det_loss_supported(cls_preds, reg_preds, dir_preds, target_dict['pos_equal_one'], target_dict['neg_equal_one'],
+                                      target_dict['targets'], gamma=self.cls.get('gamma'), num_bins=dir_args.get('num_bins', 2),
+                                      iou=self.iou, batch_size=batch_size) or 'alpha' not in self.cls:
+            return None
+        if self.dir and len(dir_args['anchor_yaw']) != cls_preds.shape[1]:
+            return None
+        terms = ops.det_loss_terms(
+            cls_preds, reg_preds, dir_preds, target_dict['pos_equal_one'], target_dict['neg_equal_one'], target_dict['targets'],
+            pos_cls_weight=self.pos_cls_weight, alpha=self.cls['alpha'], sigma=self.reg['sigma'],
+            weights=(self.cls['weight'], self.reg['weight'], self.dir['weight'] if self.dir else 0.0),
+            anchor_yaw=np.deg2rad(np.array(dir_args['anchor_yaw'], dtype=np.float64)) if self.dir else None,
+            dir_offset=dir_args.get('dir_offset', 0.0))
+        cls_loss, reg_loss, dir_loss = terms[0], terms[1], terms[2]
+        host = np.asarray(terms.detach().tolist(), dtype=np.float32)
+        total_loss, total_host = reg_loss + cls_loss, host[1] + host[0]
+        if self.dir:
+            total_loss, total_host = dir_loss + total_loss, host[2] + total_host
+            self.loss_dict.update({'dir_loss': float(host[2])})
+        self.loss_dict.update({'total_loss': float(total_host), 'reg_loss': float(host[1]), 'cls_loss': float(host[0])})
         return total_loss
 
     @staticmethod

@@ -2072,6 +2072,310 @@ class KdKlLoss(torch.autograd.Function):
         return grad_out * grad, None
 
 
+# ------------------------------------------------------------------------------------------------ DL
+# The criterion terms of the training step (csrc/det_loss.hip).  HEAL_LOSS_FUSED=0 forces the torch compositions of
+# heal_amd/opencood/loss/ (scripts/loss_bench.py), =1 the kernels wherever *_supported holds.
+_LABEL_DTYPES = (torch.float32, torch.float64)
+
+
+def loss_fused_enabled():
+    return os.environ.get("HEAL_LOSS_FUSED", "1") != "0"
+
+
+def _loss_map_ok(t):
+    return bool(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.numel() > 0)
+
+
+def _loss_labels_ok(device, *labels):
+    """Labels float32 or float64 (one type for all of them) on the maps' device."""
+    return bool(all(isinstance(t, torch.Tensor) and t.device == device and t.dtype in _LABEL_DTYPES for t in labels)
+                and len({t.dtype for t in labels}) == 1)
+
+
+def det_loss_supported(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targets, gamma=2.0, num_bins=2, iou=None,
+                       batch_size=None):
+    """The fused detection terms: CUDA fp32 head maps [N, A, H, W], [N, 7A, H, W] and (with a `dir` block) [N, 2A, H, W], A <= 4,
+    labels float32 or float64 on the same device with N*H*W*A (x 7) elements, gamma == 2, two direction bins, no `iou` block.  With
+    a `dir` block A must be 2: the composition's own direction term is only defined there.  batch_size: what the loss module
+    derived from record_len, when it differs from N the composition runs.  HEAL_LOSS_FUSED=0 forces the composition."""
+    if not loss_fused_enabled() or iou or gamma != 2.0 or not (_loss_map_ok(cls_preds) and _loss_map_ok(reg_preds)):
+        return False
+    N, A, H, W = (int(v) for v in cls_preds.shape)
+    maps = [cls_preds, reg_preds]
+    if dir_preds is not None:
+        if num_bins != 2 or A != 2 or not _loss_map_ok(dir_preds) or tuple(dir_preds.shape) != (N, 2 * A, H, W):
+            return False
+        maps.append(dir_preds)
+    return bool(A <= 4 and tuple(reg_preds.shape) == (N, 7 * A, H, W) and all(m.device == cls_preds.device for m in maps)
+                and (batch_size is None or int(batch_size) == N)
+                and _loss_labels_ok(cls_preds.device, pos_equal_one, neg_equal_one, targets)
+                and pos_equal_one.numel() == N * H * W * A and neg_equal_one.numel() == N * H * W * A
+                and targets.numel() == N * H * W * A * 7
+                and _capi.query("heal_det_loss_workspace", N, A, H, W) > 0)
+
+
+def _loss_inputs(who, maps, labels):
+    """Checked, detached, contiguous copies of the fp32 maps (None passes through) and the labels."""
+    out = []
+    dev = None
+    for name, t in maps:
+        if t is None:
+            out.append(None)
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _capi.HealAmdError(f"{who}: {name} must be a CUDA/HIP tensor (heal_amd has no CPU path)")
+        if t.dtype != torch.float32 or t.dim() != 4 or t.numel() == 0:
+            raise _capi.HealAmdError(f"{who}: {name} must be a non-empty 4-D torch.float32 map, got {t.dtype} {tuple(t.shape)}")
+        dev = dev if dev is not None else t.device
+        if t.device != dev:
+            raise _capi.HealAmdError(f"{who}: {name} is on {t.device}, the first map on {dev}")
+        out.append(t.detach().contiguous())
+    labs = []
+    for name, t in labels:
+        if not isinstance(t, torch.Tensor) or t.device != dev:
+            raise _capi.HealAmdError(f"{who}: {name} must be a tensor on {dev}")
+        if t.dtype not in _LABEL_DTYPES or t.dtype != labels[0][1].dtype:
+            raise _capi.HealAmdError(f"{who}: {name} must be float32 or float64, the same for every label, got {t.dtype}")
+        labs.append(t.detach().contiguous())
+    return out, labs
+
+
+def _loss_grad_buffers(who, maps, need_grad, grad_out):
+    """need_grad: bool or one bool per map.  -> list of (buffer | None) per map; buffers from grad_out where given."""
+    need = [bool(need_grad)] * len(maps) if isinstance(need_grad, bool) else [bool(v) for v in need_grad]
+    if len(need) != len(maps):
+        raise _capi.HealAmdError(f"{who}: need_grad has {len(need)} entries for {len(maps)} maps")
+    grads = []
+    for i, (m, want) in enumerate(zip(maps, need)):
+        if m is None or not want:
+            grads.append(None)
+            continue
+        g = grad_out[i] if grad_out is not None and grad_out[i] is not None else torch.empty_like(m)
+        if not g.is_cuda or g.dtype != torch.float32 or g.shape != m.shape or not g.is_contiguous() or g.device != m.device:
+            raise _capi.HealAmdError(f"{who}: grad_out[{i}] must be a contiguous f32 CUDA tensor of its map's shape")
+        grads.append(g)
+    return grads
+
+
+def det_loss(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targets, pos_cls_weight, alpha, sigma, weights,
+             anchor_yaw=None, dir_offset=0.0, need_grad=True, grad_out=None):
+    """DL.  PointPillarLoss's three terms and their gradients in one pass: cls_preds [N, A, H, W], reg_preds [N, 7A, H, W],
+    dir_preds [N, 2A, H, W] | None, f32 cuda (made contiguous); pos_equal_one, neg_equal_one [N, H, W, A], targets [N, H, W, 7A],
+    float32 or float64, read in place.  weights = (cls, reg, dir) loss weights, anchor_yaw: A angles in RADIANS, gamma = 2 and two
+    direction bins.  -> (terms [3] = cls, reg, dir loss, each x weight / N, (grad_cls, grad_reg, grad_dir) | None).
+    need_grad: bool or one per map; False passes NULL gradients: the kernels only read.  grad_out: buffers to write into."""
+    who = "det_loss"
+    (cls_preds, reg_preds, dir_preds), (pos, neg, tgt) = _loss_inputs(
+        who, (("cls_preds", cls_preds), ("reg_preds", reg_preds), ("dir_preds", dir_preds)),
+        (("pos_equal_one", pos_equal_one), ("neg_equal_one", neg_equal_one), ("targets", targets)))
+    N, A, H, W = (int(v) for v in cls_preds.shape)
+    if (A > 4 or tuple(reg_preds.shape) != (N, 7 * A, H, W)
+            or (dir_preds is not None and tuple(dir_preds.shape) != (N, 2 * A, H, W))):
+        raise _capi.HealAmdError(f"{who}: maps {tuple(cls_preds.shape)}, {tuple(reg_preds.shape)}"
+                                 f"{'' if dir_preds is None else ', ' + str(tuple(dir_preds.shape))} are not [N, A, H, W], "
+                                 "[N, 7A, H, W] (, [N, 2A, H, W]) with A <= 4")
+    if pos.numel() != N * H * W * A or neg.numel() != N * H * W * A or tgt.numel() != 7 * N * H * W * A:
+        raise _capi.HealAmdError(f"{who}: labels of {pos.numel()}, {neg.numel()}, {tgt.numel()} elements for N*H*W*A = {N * H * W * A}")
+    yaw = None
+    if dir_preds is not None:
+        if anchor_yaw is None or len(anchor_yaw) != A:
+            raise _capi.HealAmdError(f"{who}: dir_preds needs anchor_yaw with {A} angles (radians)")
+        yaw = (ctypes.c_double * A)(*[float(v) for v in anchor_yaw])
+    if len(weights) != 3 or not float(sigma) > 0:
+        raise _capi.HealAmdError(f"{who}: weights must be (cls, reg, dir) and sigma positive")
+    maps = (cls_preds, reg_preds, dir_preds)
+    grads = _loss_grad_buffers(who, maps, need_grad, grad_out)
+    nbytes = _capi.query("heal_det_loss_workspace", N, A, H, W)
+    if nbytes == 0:
+        raise _capi.HealAmdError(f"{who}: shape {(N, A, H, W)} is out of range")
+    ws = _workspace("det_loss", nbytes, cls_preds.device)
+    terms = torch.empty(3, dtype=torch.float32, device=cls_preds.device)
+    moved = sum(4.0 * m.numel() for m in maps if m is not None) + sum(4.0 * g.numel() for g in grads if g is not None) \
+        + float(pos.element_size()) * (2 * pos.numel() + tgt.numel())
+    with _Timed(f"det_loss_a{A}", nbytes=moved):
+        _capi.call("heal_det_loss", _ptr(cls_preds), _ptr(reg_preds), _ptr(dir_preds), _ptr(pos), _ptr(neg), _ptr(tgt),
+                   int(pos.dtype == torch.float64), N, A, H, W, float(pos_cls_weight), float(alpha), float(sigma),
+                   float(weights[0]), float(weights[1]), float(weights[2]),
+                   ctypes.cast(yaw, ctypes.c_void_p) if yaw is not None else ctypes.c_void_p(0), float(dir_offset), _ptr(terms),
+                   _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(ws), ctypes.c_size_t(nbytes), _stream())
+    return terms, (tuple(grads) if any(g is not None for g in grads) else None)
+
+
+def _wants_grad(t):
+    return bool(t is not None and t.requires_grad and torch.is_grad_enabled())
+
+
+class DetLoss(torch.autograd.Function):
+    """det_loss under autograd: forward = heal_det_loss, which also writes d term / d map (saved); backward scales each by the
+    incoming gradient of its term.  Labels receive none."""
+
+    @staticmethod
+    def forward(ctx, cls_preds, reg_preds, dir_preds, pos, neg, targets, cfg, need):
+        terms, grads = det_loss(cls_preds, reg_preds, dir_preds, pos, neg, targets, need_grad=need, **cfg)
+        grads = grads if grads is not None else (None, None, None)
+        ctx.have = tuple(g is not None for g in grads)
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        return terms
+
+    @staticmethod
+    def backward(ctx, grad_terms):
+        saved = list(ctx.saved_tensors)
+        out = [grad_terms[i] * saved.pop(0) if have else None for i, have in enumerate(ctx.have)]
+        return (*out, None, None, None, None, None)
+
+
+def det_loss_terms(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targets, **cfg):
+    """The differentiable form of det_loss: -> terms [3] (cls, reg, dir), gradients for the maps that require one."""
+    need = tuple(_wants_grad(t) for t in (cls_preds, reg_preds, dir_preds))
+    return DetLoss.apply(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targets, cfg, need)
+
+
+def occ_loss_supported(occ_list, pos_equal_one, neg_equal_one, relative_downsample, gamma=2.0):
+    """The fused occupancy term: 1..4 CUDA fp32 maps [N, 1, H // k_i, W // k_i] (the pooled label's shape) for labels [N, H, W, 2]
+    float32 or float64 on the same device, gamma == 2.  Two anchors because the composition pools anchors 0 and 1 only.
+    HEAL_LOSS_FUSED=0 forces the composition."""
+    if not loss_fused_enabled() or gamma != 2.0 or not isinstance(occ_list, (list, tuple)) or not 1 <= len(occ_list) <= 4:
+        return False
+    if len(relative_downsample) < len(occ_list) or not all(_loss_map_ok(o) for o in occ_list):
+        return False
+    dev = occ_list[0].device
+    if not _loss_labels_ok(dev, pos_equal_one, neg_equal_one) or pos_equal_one.dim() != 4 or pos_equal_one.shape != neg_equal_one.shape:
+        return False
+    N, H, W, A = (int(v) for v in pos_equal_one.shape)
+    ks = [int(k) for k in relative_downsample[:len(occ_list)]]
+    return bool(A == 2 and all(k >= 1 and H // k >= 1 and W // k >= 1 for k in ks)
+                and all(o.device == dev and tuple(o.shape) == (N, 1, H // k, W // k) for o, k in zip(occ_list, ks))
+                and _capi.query("heal_occ_loss_workspace", N, H, W, len(ks), ctypes.cast((ctypes.c_int * len(ks))(*ks), ctypes.c_void_p)) > 0)
+
+
+def occ_loss(occ_list, pos_equal_one, neg_equal_one, relative_downsample, level_weight, pos_cls_weight, alpha, need_grad=True,
+             grad_out=None):
+    """DL.  The focal occupancy loss of every pyramid level in one pass: occ_list: 1..4 maps [N, 1, H // k_i, W // k_i] f32 cuda
+    (made contiguous), labels [N, H, W, A] float32 or float64 read in place and pooled on the fly (foreground: any anchor of the
+    k_i x k_i window positive, background: every one negative; floor mode).  -> (loss [1] = sum_i level_weight[i] / N * level sum,
+    [d loss / d occ_i] | None).  need_grad: bool or one per level; False only reads."""
+    who = "occ_loss"
+    if not isinstance(occ_list, (list, tuple)) or not 1 <= len(occ_list) <= 4:
+        raise _capi.HealAmdError(f"{who}: occ_list must hold 1..4 maps")
+    L = len(occ_list)
+    if len(relative_downsample) < L or len(level_weight) < L:
+        raise _capi.HealAmdError(f"{who}: {L} levels need as many relative_downsample and level_weight entries")
+    occ, (pos, neg) = _loss_inputs(who, [(f"occ_list[{i}]", o) for i, o in enumerate(occ_list)],
+                                   (("pos_equal_one", pos_equal_one), ("neg_equal_one", neg_equal_one)))
+    if pos.dim() != 4 or pos.shape != neg.shape or int(pos.shape[3]) > 4:
+        raise _capi.HealAmdError(f"{who}: labels {tuple(pos.shape)}, {tuple(neg.shape)} must be equal [N, H, W, A <= 4]")
+    N, H, W, A = (int(v) for v in pos.shape)
+    ks = [int(k) for k in relative_downsample[:L]]
+    for i, (o, k) in enumerate(zip(occ, ks)):
+        if k < 1 or tuple(o.shape) != (N, 1, H // max(k, 1), W // max(k, 1)):
+            raise _capi.HealAmdError(f"{who}: occ_list[{i}] is {tuple(o.shape)}, the labels pooled by {k} are {(N, 1, H // max(k, 1), W // max(k, 1))}")
+    grads = _loss_grad_buffers(who, occ, need_grad, grad_out)
+    k_arr = (ctypes.c_int * L)(*ks)
+    w_arr = (ctypes.c_float * L)(*[float(v) for v in level_weight[:L]])
+    o_arr = (ctypes.c_void_p * L)(*[o.data_ptr() for o in occ])
+    g_arr = (ctypes.c_void_p * L)(*[g.data_ptr() if g is not None else None for g in grads])
+    nbytes = _capi.query("heal_occ_loss_workspace", N, H, W, L, ctypes.cast(k_arr, ctypes.c_void_p))
+    if nbytes == 0:
+        raise _capi.HealAmdError(f"{who}: labels {(N, H, W, A)} with levels {ks} are out of range")
+    ws = _workspace("occ_loss", nbytes, pos.device)
+    loss = torch.empty(1, dtype=torch.float32, device=pos.device)
+    moved = sum(4.0 * o.numel() for o in occ) + sum(4.0 * g.numel() for g in grads if g is not None) \
+        + float(pos.element_size()) * 2 * pos.numel() * (L + 1)
+    with _Timed(f"occ_loss_l{L}", nbytes=moved):
+        _capi.call("heal_occ_loss", ctypes.cast(o_arr, ctypes.c_void_p), _ptr(pos), _ptr(neg), int(pos.dtype == torch.float64), N, A,
+                   H, W, L, ctypes.cast(k_arr, ctypes.c_void_p), ctypes.cast(w_arr, ctypes.c_void_p), float(pos_cls_weight),
+                   float(alpha), _ptr(loss), ctypes.cast(g_arr, ctypes.c_void_p), _ptr(ws), ctypes.c_size_t(nbytes), _stream())
+    return loss, (grads if any(g is not None for g in grads) else None)
+
+
+class OccLoss(torch.autograd.Function):
+    """occ_loss under autograd; the per-level gradients written by the forward are saved and scaled in backward."""
+
+    @staticmethod
+    def forward(ctx, pos, neg, cfg, need, *occ_list):
+        loss, grads = occ_loss(list(occ_list), pos, neg, need_grad=need, **cfg)
+        grads = grads if grads is not None else [None] * len(occ_list)
+        ctx.have = tuple(g is not None for g in grads)
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        saved = list(ctx.saved_tensors)
+        return (None, None, None, None, *[grad_out * saved.pop(0) if have else None for have in ctx.have])
+
+
+def occ_loss_term(occ_list, pos_equal_one, neg_equal_one, **cfg):
+    need = tuple(_wants_grad(o) for o in occ_list)
+    return OccLoss.apply(pos_equal_one, neg_equal_one, cfg, need, *occ_list)
+
+
+def depth_focal_loss_supported(depth_logit, depth_gt_indices, fg_mask=None, gamma=2.0, smooth_target=False):
+    """The fused depth-bin term: CUDA fp32 logits [M, D, h, w], int64 target indices [M, h, w] and an optional float32 mask of
+    that shape on the same device, gamma == 2, smooth_target off.  HEAL_LOSS_FUSED=0 forces the composition."""
+    if not loss_fused_enabled() or gamma != 2.0 or smooth_target or not _loss_map_ok(depth_logit):
+        return False
+    M, D, h, w = (int(v) for v in depth_logit.shape)
+    dev = depth_logit.device
+    if not (isinstance(depth_gt_indices, torch.Tensor) and depth_gt_indices.device == dev and depth_gt_indices.dtype == torch.int64
+            and tuple(depth_gt_indices.shape) == (M, h, w)):
+        return False
+    if fg_mask is not None and not (isinstance(fg_mask, torch.Tensor) and fg_mask.device == dev and fg_mask.dtype == torch.float32
+                                    and tuple(fg_mask.shape) == (M, h, w)):
+        return False
+    return _capi.query("heal_depth_focal_loss_workspace", M, D, h, w) > 0
+
+
+def depth_focal_loss(depth_logit, depth_gt_indices, fg_mask=None, alpha=0.25, weight=1.0, need_grad=True, grad_out=None):
+    """DL.  depth_logit [M, D, h, w] f32 cuda (made contiguous), depth_gt_indices [M, h, w] int64, fg_mask [M, h, w] f32 | None ->
+    (loss [1], grad | None): weight x the mean over M*h*w of -alpha (1 - p_g)^2 log p_g (x 3.25 where the mask is > 0, 0.25
+    where it is 0), p the channel softmax, and its gradient.  A target index outside [0, D) contributes 0 and receives an all-zero
+    gradient; the reference's one_hot raises there.  need_grad=False only reads."""
+    who = "depth_focal_loss"
+    (depth_logit,), _ = _loss_inputs(who, (("depth_logit", depth_logit),), ())
+    M, D, h, w = (int(v) for v in depth_logit.shape)
+    dev = depth_logit.device
+    if (not isinstance(depth_gt_indices, torch.Tensor) or depth_gt_indices.device != dev or depth_gt_indices.dtype != torch.int64
+            or tuple(depth_gt_indices.shape) != (M, h, w)):
+        raise _capi.HealAmdError(f"{who}: depth_gt_indices must be int64 {(M, h, w)} on {dev}")
+    if fg_mask is not None and (not isinstance(fg_mask, torch.Tensor) or fg_mask.device != dev or fg_mask.dtype != torch.float32
+                                or tuple(fg_mask.shape) != (M, h, w)):
+        raise _capi.HealAmdError(f"{who}: fg_mask must be float32 {(M, h, w)} on {dev}")
+    idx = depth_gt_indices.contiguous()
+    mask = fg_mask.detach().contiguous() if fg_mask is not None else None
+    (grad,) = _loss_grad_buffers(who, (depth_logit,), bool(need_grad), None if grad_out is None else (grad_out,))
+    nbytes = _capi.query("heal_depth_focal_loss_workspace", M, D, h, w)
+    if nbytes == 0:
+        raise _capi.HealAmdError(f"{who}: shape {(M, D, h, w)} is out of range")
+    ws = _workspace("depth_focal_loss", nbytes, dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    moved = 4.0 * depth_logit.numel() * (2 if grad is not None else 1) + 8.0 * idx.numel() + (4.0 * idx.numel() if mask is not None else 0)
+    with _Timed(f"depth_focal_loss_d{D}", nbytes=moved):
+        _capi.call("heal_depth_focal_loss", _ptr(depth_logit), _ptr(idx), _ptr(mask), M, D, h, w, float(alpha), float(weight),
+                   _ptr(loss), _ptr(grad), _ptr(ws), ctypes.c_size_t(nbytes), _stream())
+    return loss, grad
+
+
+class DepthFocalLoss(torch.autograd.Function):
+    """depth_focal_loss under autograd; the indices and the mask receive no gradient."""
+
+    @staticmethod
+    def forward(ctx, depth_logit, depth_gt_indices, fg_mask, alpha, weight, need):
+        loss, grad = depth_focal_loss(depth_logit, depth_gt_indices, fg_mask, alpha, weight, need_grad=need)
+        ctx.have = grad is not None
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return (grad_out * ctx.saved_tensors[0] if ctx.have else None, None, None, None, None, None)
+
+
+def depth_focal_loss_term(depth_logit, depth_gt_indices, fg_mask=None, alpha=0.25, weight=1.0):
+    return DepthFocalLoss.apply(depth_logit, depth_gt_indices, fg_mask, alpha, weight, _wants_grad(depth_logit))
+
+
 # ------------------------------------------------------------------------------------------------ K6c
 def ln_stats(x, eps):
     """(mean, rstd) of every token of x [..., C] -> [T, 2] f32: the statistics half of a LayerNorm whose application is

@@ -35,7 +35,9 @@ extern "C" {
                                    per-agent source descriptors), + heal_eval_match[_workspace] (AP evaluation).  Purely additive -- no existing
                                    signature changed -- so the version was not raised: a library built before them passes the
                                    version check and fails at the missing symbol in _capi.call ("does not export");
-                                   13: + heal_voxelize_layout, and K1's ws / tables_clean contract now holds across point counts */
+                                   13: + heal_voxelize_layout, and K1's ws / tables_clean contract now holds across point counts;
+                                   still 13: + heal_det_loss / heal_occ_loss / heal_depth_focal_loss [_workspace] (the criterion of the
+                                   training step), additive in the same way */
 
 int heal_abi_version(void);
 const char* heal_last_error(void);
@@ -915,6 +917,63 @@ int heal_label_assign(const float* anchor_boxes, int n_anchors, const float* gt_
 size_t heal_kd_kl_loss_workspace(int n, int channels, int H, int W);
 int heal_kd_kl_loss(const float* student, const float* teacher, int n, int channels, int H, int W, float* loss, float* grad,
                     void* ws, size_t ws_bytes, void* stream);
+
+/* ---- Criterion terms of the training step ------------------------------------------------------------------
+ * Three forward-plus-gradient operators (csrc/det_loss.hip).  Common to all: fp32 maps in NCHW read where they lie (no permuted
+ * copy), lanes along pixels, a tile = 64 consecutive pixels of one image; per-tile partial sums go to ws and a one-block kernel
+ * adds them in a fixed order in fp64 -- no floating-point atomics, repeated launches are bit-equal wherever the data lies.  Every
+ * gradient pointer may be NULL (nothing is stored, the maps are only read).  Capture-safe: kernel launches only, no host
+ * synchronisation, ws need not be initialised.  Each *_workspace is host arithmetic and returns 0 for a shape out of range
+ * (n < 1, an empty map, a map of 2^31 elements or more per sample).  With tiles(n, hw) = n * ceil(hw / 64) and
+ * up(x) = x rounded up to a multiple of 256:
+ *     heal_det_loss_workspace          = 256 n + up(12 tiles(n, H W))                 (64 count words per sample)
+ *     heal_occ_loss_workspace          = 256 levels n + up(4 sum_i tiles(n, (H / k_i) (W / k_i)))
+ *     heal_depth_focal_loss_workspace  = up(4 tiles(m, h w))
+ *
+ * heal_det_loss: PointPillarLoss.forward, opencood/loss/point_pillar_loss.py:36-122 (without its `iou` block), gamma = 2 and two
+ *   direction bins.  cls_preds [n, A, H, W], reg_preds [n, 7A, H, W], dir_preds [n, 2A, H, W] or NULL (no `dir` block); channels
+ *   are anchor-major (a*7+k, a*2+bin), A = anchors <= 4.  pos_equal_one, neg_equal_one [n, H, W, A] and targets [n, H, W, 7A]:
+ *   float32 (labels_f64 = 0) or float64 (1), read in place.  With nrm_n = max(#{pos > 0 in sample n}, 1):
+ *     terms[0] = cls_weight / n * sum (1 - p_t)^2 (t alpha + (1 - t)(1 - alpha)) ce w,   t = pos, p = sigmoid(x),
+ *                ce = max(x, 0) - x t + log1p(exp(-|x|)), p_t = t p + (1 - t)(1 - p), w = ((pos > 0) pos_cls_weight + (neg > 0)) / nrm_n
+ *     terms[1] = reg_weight / n * sum over positive anchors of the seven smooth-L1 terms / nrm_n (quadratic 0.5 sigma^2 d^2 where
+ *                |d| <= 1 / sigma^2, |d| - 0.5 / sigma^2 above), the yaw as sin(a) cos(b) against cos(a) sin(b) (add_sin_difference)
+ *     terms[2] = dir_weight / n * sum over positive anchors of the two-bin cross-entropy / nrm_n (0 without dir_preds), the target
+ *                bin = clamp(floor(limit_period(target_yaw + anchor_yaw[a] - dir_offset, 0, 2 pi) / pi), 0, 1) in double precision
+ *   grad_cls / grad_reg / grad_dir <- d terms[0] / d cls_preds, d terms[1] / d reg_preds, d terms[2] / d dir_preds.  An anchor with
+ *   pos = neg = 0 contributes exactly 0 and receives exactly 0; non-positive anchors receive exactly 0 in grad_reg and grad_dir.
+ *   anchor_yaw: HOST array of `anchors` radians (needed with dir_preds).  Three launches (counts, the pass, finish).
+ *
+ * heal_occ_loss: PointPillarPyramidLoss.calc_occ_loss, opencood/loss/point_pillar_pyramid_loss.py:71-107.  occ / grad: HOST arrays
+ *   of `levels` (1..4) device pointers to [n, 1, H / k_i, W / k_i] maps, k_i = relative_downsample[i] (host), level_weight (host).
+ *   A cell of level i is foreground if any anchor of any pixel of its k_i x k_i window (stride k_i, floor mode: trailing rows and
+ *   columns are dropped, as max_pool2d does) has pos != 0, background if every one has neg != 0; nrm = max(foreground cells of the
+ *   sample at that level, 1); the focal term above with t = fg, w = (fg pos_cls_weight + bg) / nrm.
+ *     loss[0] = sum_i level_weight[i] / n * sum of the level's terms,     grad[i] <- d loss / d occ[i]
+ *   Three launches for all levels together.
+ *
+ * heal_depth_focal_loss: FocalLoss with smooth_target = False and its use in PointPillarDepthLoss.forward,
+ *   opencood/loss/point_pillar_depth_loss.py:97-181 and :58-75, gamma = 2.  depth_logit [m, depth_bins, h, w] f32,
+ *   depth_gt_indices [m, h, w] int64, fg_mask [m, h, w] f32 or NULL.  Per pixel, with p = channel softmax and g the target index:
+ *     loss[0] = weight / (m h w) * sum -alpha (1 - p_g)^2 log p_g * (fg_mask ? (fg > 0 ? 3.25 : fg == 0 ? 0.25 : 0) : 1)
+ *     grad[m, k, p] = the same factors * -alpha F (delta_gk - p_k),   F = (1 - p_g)^2 - 2 (1 - p_g) p_g log p_g
+ *   A target index outside [0, depth_bins) contributes 0 and receives an all-zero gradient (the reference's one_hot raises there).
+ *   depth_bins <= 64 and a multiple of 4 keeps the pixel's logits in registers (every input byte read once); any other value takes
+ *   a three-pass loop.  Two launches.                                                                                         */
+size_t heal_det_loss_workspace(int n, int anchors, int H, int W);
+int heal_det_loss(const float* cls_preds, const float* reg_preds, const float* dir_preds, const void* pos_equal_one,
+                  const void* neg_equal_one, const void* targets, int labels_f64, int n, int anchors, int H, int W,
+                  float pos_cls_weight, float alpha, float sigma, float cls_weight, float reg_weight, float dir_weight,
+                  const double* anchor_yaw, double dir_offset, float* terms, float* grad_cls, float* grad_reg, float* grad_dir,
+                  void* ws, size_t ws_bytes, void* stream);
+size_t heal_occ_loss_workspace(int n, int H, int W, int levels, const int* relative_downsample);
+int heal_occ_loss(const float* const* occ, const void* pos_equal_one, const void* neg_equal_one, int labels_f64, int n, int anchors,
+                  int H, int W, int levels, const int* relative_downsample, const float* level_weight, float pos_cls_weight,
+                  float alpha, float* loss, float* const* grad, void* ws, size_t ws_bytes, void* stream);
+size_t heal_depth_focal_loss_workspace(int m, int depth_bins, int h, int w);
+int heal_depth_focal_loss(const float* depth_logit, const int64_t* depth_gt_indices, const float* fg_mask, int m, int depth_bins,
+                          int h, int w, float alpha, float weight, float* loss, float* grad, void* ws, size_t ws_bytes,
+                          void* stream);
 
 #ifdef __cplusplus
 }
