@@ -4,6 +4,7 @@ This is the only place the package touches the native library.  There is NO fall
 library is missing or a call fails, an exception is raised.
 """
 import ctypes
+import functools
 import os
 import re
 
@@ -14,210 +15,79 @@ HEADER_EXPERIMENTAL = os.path.join(os.path.dirname(HERE), "include", "heal_amd_e
 
 _lib = None
 
-c_void_p, c_int, c_float, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
-
-_SIGNATURES = {
-    # name: (restype, argtypes)
-    "heal_abi_version": (c_int, []),
-    "heal_last_error": (ctypes.c_char_p, []),
-    "heal_fill_bytes": (c_int, [c_void_p, c_int, c_size_t, c_void_p]),
-    "heal_next_launch_events": (c_int, [c_void_p, c_void_p]),
-    "heal_voxelize_workspace": (c_size_t, [c_int, c_int, c_int, ctypes.c_longlong]),
-    "heal_voxelize_layout": (c_int, [c_int, c_int, c_int, ctypes.c_longlong, c_void_p]),
-    "heal_voxelize": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
-                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
-    "heal_voxelize_batch_workspace": (c_size_t, [c_int, c_int, c_int, c_int, ctypes.c_longlong]),
-    "heal_voxelize_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                    c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
-    "heal_mask_points": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
-    "heal_pfn_scatter_workspace": (c_size_t, [c_int] * 5),
-    "heal_pfn_scatter": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                 c_void_p, c_void_p, c_void_p, c_int,
-                                 c_float, c_float, c_float, c_float, c_float, c_float,
-                                 c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "heal_pfn_pillars": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                 c_float, c_float, c_float, c_float, c_float, c_float, c_int, c_int, c_int, c_void_p, c_void_p,
-                                 c_void_p]),
-    "heal_pillar_canvas": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "heal_pillar_stem_block": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 3),
-    "heal_bev_pool_backward": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p] * 6),
-    "heal_warp_fuse": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                               c_void_p, c_void_p]),
-    "heal_warp_fuse_levels": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                      c_void_p, c_void_p, c_void_p]),
-    "heal_warp_fuse_levels_src": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                          c_void_p, c_void_p, c_void_p]),
-    "heal_warp_att_fuse_levels": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                          c_int, c_void_p, c_void_p]),
-    "heal_disco_fuse": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 11),
-    "heal_warp_fuse_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                        c_void_p, c_void_p, c_void_p, c_void_p]),
-    "heal_warp_agent": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                c_void_p, c_void_p, c_void_p]),
-    "heal_warp_agents_pm": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "heal_fuse_warped": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "heal_fuse_warped_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "heal_decode_nms_workspace": (c_size_t, [c_int, c_int]),
-    "heal_decode_nms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                c_float, c_float, c_float, c_int, c_void_p, c_void_p,
-                                c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
-    "heal_decode_nms_agents_workspace": (c_size_t, [c_int, c_int]),
-    "heal_decode_nms_agents": (c_int, [c_int] + [c_void_p] * 6 + [c_int, c_int, c_float, c_float, c_float, c_int] +
-                               [c_void_p] * 7 + [c_int, c_void_p, c_size_t, c_void_p]),
-    "heal_quad_iou": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
-    "heal_bev_pool_workspace": (c_size_t, [c_int] * 9),
-    "heal_bev_pool": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "heal_bev_pool_pm_workspace": (c_size_t, [c_int] * 5),
-    "heal_bev_pool_pm": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 5 + [c_size_t, c_void_p]),
-    "heal_bev_pool_scatter": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 4 + [c_size_t, c_void_p]),
-    "heal_bev_pool_scatter_multi": (c_int, [c_int] + [c_void_p] * 16),
-    "heal_bev_pool_emit": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "heal_bev_stem_block": (c_int, [c_int, c_int] + [c_void_p] * 8 + [c_size_t, c_void_p]),
-    "heal_pfn_train_blocks": (c_int, [c_int]),
-    "heal_pfn_features": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float,
-                                  c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
-    "heal_pfn_moments": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float,
-                                 c_void_p, c_void_p]),
-    "heal_pfn_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
-    "heal_mean_vfe": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "heal_sp_sort_workspace": (c_size_t, [c_int]),
-    "heal_sp_sort_sites": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
-                                   c_void_p]),
-    "heal_sp_wgrad_chunks": (c_int, [c_int]),
-    "heal_sp_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "heal_sp_gather_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "heal_sp_table_capacity": (c_size_t, [c_int]),
-    "heal_sp_hash_build": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
-    "heal_sp_neighbors": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                  c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
-    "heal_sp_out_sites_workspace": (c_size_t, [c_int, c_int]),
-    "heal_sp_out_sites": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                  c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
-    "heal_conv_gemm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p, c_void_p]),
-    "heal_ln_stats": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
-    "heal_linear": (c_int, [c_void_p, c_int, c_int, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                            c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                            ctypes.c_longlong, c_int, c_void_p]),
-    "heal_split_attn_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "heal_split_attn_weights": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_int] + [c_void_p] * 5 + [c_float] +
-                                [c_void_p] * 5),
-    "heal_split_attn_colsum": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "heal_split_attn_weights_from_colsum": (c_int, [c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 5 + [c_float] +
-                                            [c_void_p] * 4),
-    "heal_sp_rank_bytes": (c_size_t, [c_void_p, c_int]),
-    "heal_sp_out_sites_rank": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                       c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
-    "heal_sp_neighbors_rank": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                       c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "heal_sp_neighbors_root": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                       c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "heal_sp_root_rank_bytes": (c_size_t, [c_void_p, c_int]),
-    "heal_sp_pair_tiles_words": (c_size_t, [c_int, c_int]),
-    "heal_sp_neighbor_tiles": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                       c_void_p, c_size_t, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    "heal_sp_tiles_to_neighbors": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "heal_sp_conv_tiles_supported": (c_int, [c_int, c_int]),
-    "heal_sp_conv_tiles": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                   c_void_p, c_void_p, c_void_p]),
-    "heal_sp_root_rank": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                  c_size_t, c_void_p, c_void_p]),
-    "heal_gconv_conv3_supported": (c_int, [c_int] * 5),
-    "heal_gconv_conv3": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p, c_void_p]),
-    "heal_sp_transpose_neighbors": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "heal_sp_weight_fragments": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "heal_sp_conv": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                             c_void_p, c_void_p, c_void_p]),
-    "heal_sp_to_bev_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "heal_sp_to_bev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
-                               c_void_p, c_void_p]),
-    "heal_agent_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
-                                     c_int, c_void_p, c_int, c_void_p]),
-    "heal_agent_attention_backward": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_float, c_int] + [c_void_p] * 3 +
-                                      [c_int, c_void_p]),
-    "heal_grouped_conv3x3": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                     c_void_p, c_void_p]),
-    "heal_bias_act": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "heal_resnext_bottleneck": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "heal_upsample2x_bilinear": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "heal_depthwise_conv": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 11 + [c_void_p, c_void_p, c_void_p]),
-    "heal_camera_matrices": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p]),
-    "heal_channel_dot": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_void_p]),
-    "heal_layernorm_nchw": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_float, c_void_p, c_void_p]),
-    "heal_se_gate": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_float, c_int, c_void_p, c_void_p]),
-    "heal_conv1x1": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p, c_void_p]),
-    "heal_stem7x7": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "heal_conv1x1_split_supported": (c_int, [c_int] * 4),
-    "heal_conv1x1_split": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p, c_void_p]),
-    "heal_conv1x1_tiled_supported": (c_int, [c_int] * 5),
-    "heal_conv1x1_tiled": (c_int, [c_void_p] * 4 + [c_int] * 9 + [c_void_p, c_void_p]),
-    "heal_conv1x1_splitk_workspace": (c_size_t, [c_int] * 5),
-    "heal_conv1x1_splitk": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "heal_conv1x1_d2s": (c_int, [c_void_p] * 3 + [c_int] * 9 + [c_void_p, c_void_p]),
-    "heal_conv3x3": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p, c_void_p]),
-    "heal_conv3x3_same": (c_int, [c_void_p] * 3 + [c_int] * 11 + [c_void_p, c_void_p]),
-    "heal_grouped16_conv3x3": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_void_p]),
-    "heal_grouped_small_conv3x3": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_void_p, c_void_p]),
-    "heal_conv3x3_winograd4": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p, c_void_p]),
-    "heal_conv3x3_winograd": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p, c_void_p]),
-    "heal_conv3x3_winograd_kc": (c_int, [c_void_p] * 4 + [c_int] * 8 + [c_void_p, c_void_p]),
-    "heal_conv3x3_winograd_splitk_workspace": (c_size_t, [c_int] * 5),
-    "heal_conv3x3_winograd_splitk": (c_int, [c_void_p] * 4 + [c_int] * 8 + [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "heal_nms_quads_workspace": (c_size_t, [c_int]),
-    "heal_nms_quads": (c_int, [c_void_p, c_int, c_float, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
-    "heal_window_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
-                                      c_void_p]),
-    "heal_window_attention_backward_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "heal_window_attention_backward": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_float, c_void_p, c_void_p, c_void_p, c_size_t,
-                                                c_void_p]),
-    "heal_agent_window_attention": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [c_float, c_void_p, c_void_p]),
-    "heal_agent_mean": (c_int, [c_void_p, c_int, ctypes.c_longlong, c_void_p, c_void_p]),
-    "heal_v2v_message_workspace": (c_size_t, [c_int] * 5),
-    "heal_v2v_message": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p] + [c_int] * 9
-                         + [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "heal_gru_zero_state": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong] + [c_int] * 4 + [c_void_p, c_void_p]),
-    "heal_label_assign_workspace": (c_size_t, [c_int]),
-    "heal_label_assign": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
-                                  c_size_t, c_void_p]),
-    "heal_boxes_bev_matrix": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "heal_nms_bev_workspace": (c_size_t, [c_int]),
-    "heal_nms_bev": (c_int, [c_void_p, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
-    "heal_kd_kl_loss_workspace": (c_size_t, [c_int] * 4),
-    "heal_kd_kl_loss": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "heal_det_loss_workspace": (c_size_t, [c_int] * 4),
-    "heal_det_loss": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_float] * 6 + [c_void_p, ctypes.c_double] + [c_void_p] * 5
-                      + [c_size_t, c_void_p]),
-    "heal_occ_loss_workspace": (c_size_t, [c_int] * 4 + [c_void_p]),
-    "heal_occ_loss": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p,
-                              c_size_t, c_void_p]),
-    "heal_depth_focal_loss_workspace": (c_size_t, [c_int] * 4),
-    "heal_depth_focal_loss": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
-                                      c_void_p]),
-    "heal_eval_match_workspace": (c_size_t, [c_int, c_int]),
-    "heal_eval_match": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                c_void_p, c_size_t, c_void_p]),
-}
-
 
 class HealAmdError(RuntimeError):
     pass
 
 
+# The headers are the only place a prototype is written: the ctypes signatures are read from them.  The mapping is closed --
+# a parameter with a `*` is a pointer, a scalar is one of _SCALARS, and anything else (a struct by value, a function pointer,
+# `...`, an unknown type) is an error: an argument list that is guessed hands a kernel a wrong pointer or stride silently.
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
+            "long long": ctypes.c_longlong, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+            "uint64_t": ctypes.c_uint64, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint}
+_COMMENT = re.compile(r"/\*.*?\*/|//[^\n]*", re.S)
+_NOT_PROTOTYPE = re.compile(r"#ifdef __cplusplus.*?#endif|^[ \t]*#[^\n]*|typedef\s+struct\b[^{;]*\{[^}]*\}[^;]*;", re.S | re.M)
+_PROTOTYPE = re.compile(r"(.*?)\b(heal_[a-z0-9_]+)\s*\((.*)\)", re.S)
+
+
+def _ctype(symbol, text, restype=False):
+    words = [w for w in text.replace("*", " * ").split() if w != "const"]
+    if restype:
+        found = ctypes.c_char_p if words == ["char", "*"] else _SCALARS.get(" ".join(words))
+    elif "*" in words and "(" not in text:
+        found = ctypes.c_void_p
+    else:                                              # `type name` or `type`
+        found = _SCALARS.get(" ".join(words)) or (words[-1:] and words[-1].isidentifier() and _SCALARS.get(" ".join(words[:-1])))
+    if not found:
+        raise HealAmdError(f"{symbol}: cannot map the {'return type' if restype else 'parameter'} `{text.strip()}` to ctypes")
+    return found
+
+
+def parse_prototypes(text):
+    """{name: (restype, argtypes)} of every `ret heal_xxx(params);` in the text of a C header.  Comments, preprocessor lines,
+    the extern "C" bracket and struct bodies are dropped; whatever else is not such a prototype raises HealAmdError."""
+    out = {}
+    for statement in _NOT_PROTOTYPE.sub(" ", _COMMENT.sub(" ", text)).split(";"):
+        statement = " ".join(statement.split())
+        if not statement:
+            continue
+        m = _PROTOTYPE.fullmatch(statement)
+        if not m:
+            raise HealAmdError(f"not a prototype of an entry point: `{statement}`")
+        ret, name, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        out[name] = (_ctype(name, ret, restype=True), [_ctype(name, p) for p in params])
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def signatures(experimental=None):
+    """{name: (restype, argtypes)} of include/heal_amd.h (experimental=False), of include/heal_amd_experimental.h (True: the
+    measured-negative kernels of a HEAL_BUILD_EXPERIMENTAL=1 library), or of both (None)."""
+    if experimental is None:
+        return {**signatures(False), **signatures(True)}
+    with open(HEADER_EXPERIMENTAL if experimental else HEADER) as f:
+        return parse_prototypes(f.read())
+
+
 def declared_symbols(experimental=False):
     """Function names declared in include/heal_amd.h (the shipped C ABI), or with experimental=True in
-    include/heal_amd_experimental.h (the measured-negative kernels of a HEAL_BUILD_EXPERIMENTAL=1 library)."""
-    text = open(HEADER_EXPERIMENTAL if experimental else HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(heal_[a-z0-9_]+)\s*\(", text)))
+    include/heal_amd_experimental.h."""
+    return sorted(signatures(bool(experimental)))
+
+
+def header_define(name):
+    """The value of `#define name <integer>` in include/heal_amd.h: the ABI version and the kernels' compile-time limits."""
+    with open(HEADER) as f:
+        m = re.search(rf"^[ \t]*#define\s+{name}\s+(\d+)\b", f.read(), re.M)
+    if not m:
+        raise HealAmdError(f"{HEADER} does not define {name}")
+    return int(m.group(1))
 
 
 def abi_version_of_header():
-    m = re.search(r"#define\s+HEAL_AMD_ABI_VERSION\s+(\d+)", open(HEADER).read())
-    if not m:
-        raise HealAmdError(f"{HEADER} does not define HEAL_AMD_ABI_VERSION")
-    return int(m.group(1))
+    return header_define("HEAL_AMD_ABI_VERSION")
 
 
 def lib():
@@ -233,13 +103,13 @@ def lib():
         # process do not share devices, streams or allocations).
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in signatures().items():
             if not hasattr(L, name):
                 continue  # declared but not built yet -> surfaces in call() / the symbol test
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
-        # The argument lists above belong to ONE version of the C ABI: a stale library paired with newer Python (or the reverse)
+        # The argument lists belong to ONE version of the C ABI: a stale library paired with newer Python (or the reverse)
         # would be called with the wrong arguments and corrupt memory silently.
         want = abi_version_of_header()
         got = int(L.heal_abi_version()) if hasattr(L, "heal_abi_version") else -1

@@ -17,7 +17,7 @@
 
 namespace heal {
 
-constexpr int AA_MAXL = 8;
+constexpr int AA_MAXL = HEAL_AGENT_ATTENTION_MAX_AGENTS;
 
 template <int LANES_PER_HEAD, int L, bool AM /*agent-major tensors [L][n_pix][C] instead of [n_pix][L][C]*/>
 __global__ __launch_bounds__(256) void k_agent_attn(const float4* __restrict__ q, const float4* __restrict__ k,

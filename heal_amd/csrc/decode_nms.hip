@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void k_decode_key(const float* __restrict__ cl
 
 // ---- late fusion: the agents of one scene ---------------------------------------------------------------------------
 // Agent k's maps, anchor table and place in the pooled anchor range; the table travels by value in the launch arguments.
-constexpr int DEC_MAX_AGENTS = 8;
+constexpr int DEC_MAX_AGENTS = HEAL_DECODE_MAX_AGENTS;
 struct AgentDesc {
     const float *cls, *reg, *dir, *anchors;
     int H, W;

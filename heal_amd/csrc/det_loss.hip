@@ -30,8 +30,8 @@ namespace heal {
 
 constexpr int DL_TILE = 64;       // pixels per wave
 constexpr int DL_WAVES = 4;       // tiles per block
-constexpr int DL_MAX_A = 4;
-constexpr int DL_MAX_LEVELS = 4;
+constexpr int DL_MAX_A = HEAL_LOSS_MAX_ANCHORS;
+constexpr int DL_MAX_LEVELS = HEAL_OCC_LOSS_MAX_LEVELS;
 constexpr int DL_CB = 64;         // count blocks per sample (and level): the main kernels add their 64 words, one per lane
 
 struct DetParams {

@@ -23,9 +23,9 @@
 
 namespace heal {
 
-constexpr int EVAL_MAX_N = 1024;
-constexpr int EVAL_MAX_M = 256;
-constexpr int EVAL_MAX_THR = 8;
+constexpr int EVAL_MAX_N = HEAL_EVAL_MAX_DET;
+constexpr int EVAL_MAX_M = HEAL_EVAL_MAX_GT;
+constexpr int EVAL_MAX_THR = HEAL_EVAL_MAX_THR;
 constexpr int EVAL_THREADS = 64 * EVAL_MAX_THR;
 
 struct EvalThr { float v[EVAL_MAX_THR]; };

@@ -18,7 +18,7 @@ namespace heal {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int SWAP_WS = 4;           // window size: 16 tokens per agent and group
-constexpr int SWAP_MAX_AGENTS = 8;
+constexpr int SWAP_MAX_AGENTS = HEAL_AGENT_WINDOW_MAX_AGENTS;
 
 template <int L, int D>
 __global__ __launch_bounds__(64 * L) void k_agent_window_attn(

@@ -29,7 +29,7 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 constexpr int VM_KC = 8;                    // input channels per chunk
 constexpr int VM_KS = VM_KC / 4;            // MFMA k-steps per chunk
 constexpr int VM_WCHUNK = 9 * VM_KS * 4 * 64;
-constexpr int VM_MAX_AGENTS = 8;
+constexpr int VM_MAX_AGENTS = HEAL_V2V_MAX_AGENTS;
 
 template <int TH>
 struct VmGeom {

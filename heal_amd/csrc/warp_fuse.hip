@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256, 4) void k_warp_fuse(const float* __restrict__ 
 constexpr int WL_T = 16;            // ego tile side
 constexpr int WL_BMAX = 32;         // largest staged source box side
 constexpr int WL_CC = 8;            // channels per staging round
-constexpr int WL_MAXL = 4;          // pyramid levels per launch
+constexpr int WL_MAXL = HEAL_WARP_MAX_LEVELS;          // pyramid levels per launch
 
 // Where agent a's map of a level lies: the map is defined on box = (y0, y1, x0, x1) of the level's H x W grid (a full map, a dense
 // crop, or a window of a larger tensor) and is exactly zero -- features and score -- outside it.  feat / occ point at the box's

@@ -5,10 +5,11 @@
 // outside the image contribute zero.
 #pragma once
 #include "common.h"
+#include "../../include/heal_amd.h"
 
 namespace heal {
 
-constexpr int WF_MAXA = 8;     // agents handled per launch (max_cav is 5..8 in the reference configs)
+constexpr int WF_MAXA = HEAL_WARP_MAX_AGENTS;     // agents handled per launch (max_cav is 5..8 in the reference configs)
 
 struct Taps {
     int off;       // y0*W + x0 (may point outside; guarded by `ok`)

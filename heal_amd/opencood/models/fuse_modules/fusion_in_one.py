@@ -70,7 +70,8 @@ class AttFusion(_WarpThenFuse):
         x = ego.reshape(n, C, H * W).permute(2, 0, 1).contiguous()      # [HW, n, C]
         if torch.is_grad_enabled() and ego.requires_grad:
             # gradient path (fusion_in_one.py:14-45,126-151): softmax(x x^T / sqrt(C)) x per pixel, the ego row
-            if n <= 8 and ops.agent_attention_train_supported(x, 1) and os.environ.get("HEAL_ATTN_GRAD", "kernel") != "torch":
+            if (n <= ops.AGENT_ATTENTION_MAX_AGENTS and ops.agent_attention_train_supported(x, 1)
+                    and os.environ.get("HEAL_ATTN_GRAD", "kernel") != "torch"):
                 # K6 forward (ego row) + heal_agent_attention_backward; x enters as q, k and v: autograd sums the three gradients
                 return ops.AgentAttention.apply(x, x, x, 1, 1.0 / self.sqrt_dim, 1, False)[:, 0, :].t().reshape(C, H, W)
             attn = torch.softmax(torch.bmm(x, x.transpose(1, 2)) / self.sqrt_dim, dim=-1)
@@ -380,7 +381,7 @@ class V2VNetFusion(nn.Module):
         ks_ok = all(tuple(k) == (3, 3) for k in (c.conv_gates.kernel_size for c in self.conv_gru.cell_list))
         mlp_ok = (H * W) % 4 == 0 or ops.linear_supported(H * W, C, C)
         return (x.is_cuda and x.dtype == torch.float32 and not (torch.is_grad_enabled() and x.requires_grad) and ks_ok and mlp_ok
-                and max(lens) <= 8 and os.environ.get("HEAL_V2VNET_FUSED", "1") != "0")
+                and max(lens) <= ops.V2V_MAX_AGENTS and os.environ.get("HEAL_V2VNET_FUSED", "1") != "0")
 
     def _weights(self):
         """(W_n, stacked x_i weight, stacked bias, agg weight | None, [(layer weight, layer bias)] for GRU layers >= 1), from the

@@ -266,8 +266,8 @@ class PyramidFusion(ResNetBEVBackbone):
         of ONE modality (their encoder's output is then the LiDAR tensor in scene order), cached responses ready under capture.
         like: a [k, C, H, W] tensor of the full map size on the model's device (k may be 0)."""
         import os
-        if (len(record_len) != 1 or not 1 <= self.num_levels <= 4 or int(record_len[0]) > 8 or self.training
-                or os.environ.get("HEAL_K5_LEVELS", "1") != "1" or os.environ.get("HEAL_PYRAMID_LEAN", "1") != "1"):
+        if (len(record_len) != 1 or not 1 <= self.num_levels <= ops.WARP_MAX_LEVELS or int(record_len[0]) > ops.WARP_MAX_AGENTS
+                or self.training or os.environ.get("HEAL_K5_LEVELS", "1") != "1" or os.environ.get("HEAL_PYRAMID_LEAN", "1") != "1"):
             return None
         cc = self._camcrop_args(like, agent_modality_list, cam_boxes)
         if cc is None:
@@ -385,8 +385,8 @@ class PyramidFusion(ResNetBEVBackbone):
         use_crop = bool(cam_crop_info) and not self.training
         fused_feature_list, occ_map_list = [], []
         import os
-        if (len(record_len) == 1 and not torch.is_grad_enabled() and feature_list[0].is_cuda and 1 <= self.num_levels <= 4
-                and int(record_len[0]) <= 8 and os.environ.get("HEAL_K5_LEVELS", "1") == "1"):
+        if (len(record_len) == 1 and not torch.is_grad_enabled() and feature_list[0].is_cuda
+                and 1 <= self.num_levels <= ops.WARP_MAX_LEVELS and int(record_len[0]) <= ops.WARP_MAX_AGENTS and os.environ.get("HEAL_K5_LEVELS", "1") == "1"):
             # inference, one scene: the three levels are independent once the stages ran -> ONE K5 launch for all of them
             # (heal_warp_fuse_levels; HEAL_K5_LEVELS=0 keeps one heal_warp_fuse launch per level for A/B)
             n = int(record_len[0])

@@ -141,7 +141,7 @@ class HGTCavAttention(nn.Module):
             v = self.v_linears[0](flat).view(L, H * W, m, d)
             qa = torch.einsum("lphd,hde->lphe", q, self.relation_att[0])
             vm = torch.einsum("lphd,hde->lphe", v, self.relation_msg[0])
-            if (L <= 8 and m * d == 256 and ops.agent_attention_train_supported(flat, m)
+            if (L <= ops.AGENT_ATTENTION_MAX_AGENTS and m * d == 256 and ops.agent_attention_train_supported(flat, m)
                     and os.environ.get("HEAL_ATTN_GRAD", "kernel") != "torch"):
                 # on the device: K6 forward + heal_agent_attention_backward (no [HW, m, L, L] score / [L, HW, m, d] message tensors
                 # kept for the backward: q, k, v are saved and the probabilities recomputed per pixel)

@@ -15,6 +15,11 @@ from .derived import derived as _derived
 
 _WS = {}
 
+# The kernels' compile-time limits are `#define HEAL_..._MAX_...` in include/heal_amd.h, each next to the entry point it bounds; the
+# constants below that route a call to a kernel or to the torch path are read from there (the .hip files use the same defines).
+_limit = _capi.header_define
+WARP_MAX_AGENTS, WARP_MAX_LEVELS = _limit("HEAL_WARP_MAX_AGENTS"), _limit("HEAL_WARP_MAX_LEVELS")     # heal_warp_fuse[_levels[_src]]
+
 # Optional per-operator timing with HIP events on the launch stream (bench.py turns it on):
 # TIMING = {} enables it; every wrapper then appends (start_event, end_event) under its name.
 TIMING = None
@@ -702,7 +707,7 @@ def warp_fuse_levels_src(sources, shapes, affine_rows, grid_f64=True, crops=None
     return outs
 
 
-WARP_ATT_MAX_AGENTS, WARP_ATT_MAX_LEVELS = 8, 4
+WARP_ATT_MAX_AGENTS, WARP_ATT_MAX_LEVELS = WARP_MAX_AGENTS, WARP_MAX_LEVELS
 
 
 def warp_att_fuse_levels(feats_list, affine_rows, grid_f64=True, mode="att", sqrt_dims=None):
@@ -743,7 +748,7 @@ def warp_att_fuse_levels(feats_list, affine_rows, grid_f64=True, mode="att", sqr
     return outs
 
 
-DISCO_MAX_AGENTS = 8
+DISCO_MAX_AGENTS = WARP_MAX_AGENTS
 DISCO_WIDTHS = (128, 32, 8)        # PixelWeightLayer: 2C -> 128 -> 32 -> 8 -> 1
 
 
@@ -911,7 +916,7 @@ def decode_nms(cls, reg, dirp, anchors, score_thr, dir_offset, num_bins, nms_thr
     return out_c[:k], out_s[:k]
 
 
-DECODE_MAX_AGENTS = 8
+DECODE_MAX_AGENTS = _limit("HEAL_DECODE_MAX_AGENTS")
 
 
 def decode_nms_agents(cls_list, reg_list, dir_list, anchors_list, tfms, score_thr, dir_offset, num_bins, nms_thr, gt_range,
@@ -1030,7 +1035,7 @@ def quad_iou(a, b):
     return out
 
 
-EVAL_MAX_DET, EVAL_MAX_GT, EVAL_MAX_THR = 1024, 256, 8
+EVAL_MAX_DET, EVAL_MAX_GT, EVAL_MAX_THR = _limit("HEAL_EVAL_MAX_DET"), _limit("HEAL_EVAL_MAX_GT"), _limit("HEAL_EVAL_MAX_THR")
 
 
 def eval_match_supported(n, m, n_thr):
@@ -1187,10 +1192,12 @@ class WindowAttention(torch.autograd.Function):
 
 
 _AGENT_WINDOW_MODES = {"window": 0, "grid": 1}
+AGENT_WINDOW_MAX_AGENTS = _limit("HEAL_AGENT_WINDOW_MAX_AGENTS")
 
 
 def agent_window_attention_supported(n_agents, window, dim_head, H, W):
-    return 1 <= int(n_agents) <= 8 and int(window) == 4 and int(dim_head) == 32 and H % window == 0 and W % window == 0
+    return (1 <= int(n_agents) <= AGENT_WINDOW_MAX_AGENTS and int(window) == 4 and int(dim_head) == 32 and H % window == 0
+            and W % window == 0)
 
 
 def agent_window_attention(qkv, bias, n_valid, mode, heads, dim_head, window, scale, out=None):
@@ -1239,6 +1246,9 @@ def agent_mean(x):
     return out
 
 
+V2V_MAX_AGENTS = _limit("HEAL_V2V_MAX_AGENTS")
+
+
 def v2v_message_tile_h(n_ego, cout, H, W, mode):
     """Output rows per heal_v2v_message block: 8 for the mean (2 waves per SIMD at 138 VGPRs), 4 for the max (its fold keeps E
     and a running maximum: 8 rows would leave one wave per SIMD); HEAL_V2V_TH overrides (4 | 8 | 16)."""
@@ -1267,9 +1277,9 @@ def v2v_message(xs, mask, e, w, residual=None, mode="mean", nsplit=None):
     mask = _need(mask, torch.float32, "mask")
     n_ego, N, cin, H, W = (int(v) for v in xs.shape)
     cout = int(w.shape[0])
-    if tuple(w.shape) != (cout, cin, 3, 3) or mode not in ("mean", "max") or not 1 <= N <= 8:
+    if tuple(w.shape) != (cout, cin, 3, 3) or mode not in ("mean", "max") or not 1 <= N <= V2V_MAX_AGENTS:
         raise _capi.HealAmdError(f"v2v_message: unsupported weight {tuple(w.shape)} / mode {mode} / {N} agents for xs "
-                                 f"{tuple(xs.shape)} (3x3 weights, mean | max, 1..8 agents)")
+                                 f"{tuple(xs.shape)} (3x3 weights, mean | max, 1..{V2V_MAX_AGENTS} agents)")
     if tuple(mask.shape) != (n_ego, N, H, W):
         raise _capi.HealAmdError(f"v2v_message: mask {tuple(mask.shape)} for xs {tuple(xs.shape)}")
     if not (isinstance(e, torch.Tensor) and e.is_cuda and e.dtype == torch.float32 and e.dim() == 4
@@ -1994,8 +2004,12 @@ class AgentAttention(torch.autograd.Function):
         return gq, gk, gv, None, None, None, None
 
 
+AGENT_ATTENTION_MAX_AGENTS = _limit("HEAL_AGENT_ATTENTION_MAX_AGENTS")
+
+
 def agent_attention_train_supported(q, heads):
-    """The device gradient path: fp32 CUDA tensors, 256 channels, at most 8 agents, heads in {1, 4, 8, 16}."""
+    """The device gradient path: fp32 CUDA tensors, 256 channels, heads in {1, 4, 8, 16}; the caller checks that there are at most
+    AGENT_ATTENTION_MAX_AGENTS agents."""
     return bool(q.is_cuda and q.dtype == torch.float32 and q.shape[-1] == 256 and heads in (1, 4, 8, 16))
 
 
@@ -2078,6 +2092,9 @@ class KdKlLoss(torch.autograd.Function):
 _LABEL_DTYPES = (torch.float32, torch.float64)
 
 
+LOSS_MAX_ANCHORS, OCC_LOSS_MAX_LEVELS = _limit("HEAL_LOSS_MAX_ANCHORS"), _limit("HEAL_OCC_LOSS_MAX_LEVELS")
+
+
 def loss_fused_enabled():
     return os.environ.get("HEAL_LOSS_FUSED", "1") != "0"
 
@@ -2094,8 +2111,8 @@ def _loss_labels_ok(device, *labels):
 
 def det_loss_supported(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targets, gamma=2.0, num_bins=2, iou=None,
                        batch_size=None):
-    """The fused detection terms: CUDA fp32 head maps [N, A, H, W], [N, 7A, H, W] and (with a `dir` block) [N, 2A, H, W], A <= 4,
-    labels float32 or float64 on the same device with N*H*W*A (x 7) elements, gamma == 2, two direction bins, no `iou` block.  With
+    """The fused detection terms: CUDA fp32 head maps [N, A, H, W], [N, 7A, H, W] and (with a `dir` block) [N, 2A, H, W], at most
+    LOSS_MAX_ANCHORS anchors, labels float32 or float64 on the same device with N*H*W*A (x 7) elements, gamma == 2, two direction bins, no `iou` block.  With
     a `dir` block A must be 2: the composition's own direction term is only defined there.  batch_size: what the loss module
     derived from record_len, when it differs from N the composition runs.  HEAL_LOSS_FUSED=0 forces the composition."""
     if not loss_fused_enabled() or iou or gamma != 2.0 or not (_loss_map_ok(cls_preds) and _loss_map_ok(reg_preds)):
@@ -2106,7 +2123,7 @@ def det_loss_supported(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal
         if num_bins != 2 or A != 2 or not _loss_map_ok(dir_preds) or tuple(dir_preds.shape) != (N, 2 * A, H, W):
             return False
         maps.append(dir_preds)
-    return bool(A <= 4 and tuple(reg_preds.shape) == (N, 7 * A, H, W) and all(m.device == cls_preds.device for m in maps)
+    return bool(A <= LOSS_MAX_ANCHORS and tuple(reg_preds.shape) == (N, 7 * A, H, W) and all(m.device == cls_preds.device for m in maps)
                 and (batch_size is None or int(batch_size) == N)
                 and _loss_labels_ok(cls_preds.device, pos_equal_one, neg_equal_one, targets)
                 and pos_equal_one.numel() == N * H * W * A and neg_equal_one.numel() == N * H * W * A
@@ -2169,11 +2186,11 @@ def det_loss(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targ
         who, (("cls_preds", cls_preds), ("reg_preds", reg_preds), ("dir_preds", dir_preds)),
         (("pos_equal_one", pos_equal_one), ("neg_equal_one", neg_equal_one), ("targets", targets)))
     N, A, H, W = (int(v) for v in cls_preds.shape)
-    if (A > 4 or tuple(reg_preds.shape) != (N, 7 * A, H, W)
+    if (A > LOSS_MAX_ANCHORS or tuple(reg_preds.shape) != (N, 7 * A, H, W)
             or (dir_preds is not None and tuple(dir_preds.shape) != (N, 2 * A, H, W))):
         raise _capi.HealAmdError(f"{who}: maps {tuple(cls_preds.shape)}, {tuple(reg_preds.shape)}"
                                  f"{'' if dir_preds is None else ', ' + str(tuple(dir_preds.shape))} are not [N, A, H, W], "
-                                 "[N, 7A, H, W] (, [N, 2A, H, W]) with A <= 4")
+                                 f"[N, 7A, H, W] (, [N, 2A, H, W]) with at most {LOSS_MAX_ANCHORS} anchors")
     if pos.numel() != N * H * W * A or neg.numel() != N * H * W * A or tgt.numel() != 7 * N * H * W * A:
         raise _capi.HealAmdError(f"{who}: labels of {pos.numel()}, {neg.numel()}, {tgt.numel()} elements for N*H*W*A = {N * H * W * A}")
     yaw = None
@@ -2234,7 +2251,8 @@ def occ_loss_supported(occ_list, pos_equal_one, neg_equal_one, relative_downsamp
     """The fused occupancy term: 1..4 CUDA fp32 maps [N, 1, H // k_i, W // k_i] (the pooled label's shape) for labels [N, H, W, 2]
     float32 or float64 on the same device, gamma == 2.  Two anchors because the composition pools anchors 0 and 1 only.
     HEAL_LOSS_FUSED=0 forces the composition."""
-    if not loss_fused_enabled() or gamma != 2.0 or not isinstance(occ_list, (list, tuple)) or not 1 <= len(occ_list) <= 4:
+    if (not loss_fused_enabled() or gamma != 2.0 or not isinstance(occ_list, (list, tuple))
+            or not 1 <= len(occ_list) <= OCC_LOSS_MAX_LEVELS):
         return False
     if len(relative_downsample) < len(occ_list) or not all(_loss_map_ok(o) for o in occ_list):
         return False
@@ -2255,15 +2273,16 @@ def occ_loss(occ_list, pos_equal_one, neg_equal_one, relative_downsample, level_
     k_i x k_i window positive, background: every one negative; floor mode).  -> (loss [1] = sum_i level_weight[i] / N * level sum,
     [d loss / d occ_i] | None).  need_grad: bool or one per level; False only reads."""
     who = "occ_loss"
-    if not isinstance(occ_list, (list, tuple)) or not 1 <= len(occ_list) <= 4:
+    if not isinstance(occ_list, (list, tuple)) or not 1 <= len(occ_list) <= OCC_LOSS_MAX_LEVELS:
         raise _capi.HealAmdError(f"{who}: occ_list must hold 1..4 maps")
     L = len(occ_list)
     if len(relative_downsample) < L or len(level_weight) < L:
         raise _capi.HealAmdError(f"{who}: {L} levels need as many relative_downsample and level_weight entries")
     occ, (pos, neg) = _loss_inputs(who, [(f"occ_list[{i}]", o) for i, o in enumerate(occ_list)],
                                    (("pos_equal_one", pos_equal_one), ("neg_equal_one", neg_equal_one)))
-    if pos.dim() != 4 or pos.shape != neg.shape or int(pos.shape[3]) > 4:
-        raise _capi.HealAmdError(f"{who}: labels {tuple(pos.shape)}, {tuple(neg.shape)} must be equal [N, H, W, A <= 4]")
+    if pos.dim() != 4 or pos.shape != neg.shape or int(pos.shape[3]) > LOSS_MAX_ANCHORS:
+        raise _capi.HealAmdError(f"{who}: labels {tuple(pos.shape)}, {tuple(neg.shape)} must be equal [N, H, W, A] with at most "
+                                 f"{LOSS_MAX_ANCHORS} anchors")
     N, H, W, A = (int(v) for v in pos.shape)
     ks = [int(k) for k in relative_downsample[:L]]
     for i, (o, k) in enumerate(zip(occ, ks)):

@@ -37,7 +37,9 @@ extern "C" {
                                    version check and fails at the missing symbol in _capi.call ("does not export");
                                    13: + heal_voxelize_layout, and K1's ws / tables_clean contract now holds across point counts;
                                    still 13: + heal_det_loss / heal_occ_loss / heal_depth_focal_loss [_workspace] (the criterion of the
-                                   training step), additive in the same way */
+                                   training step), additive in the same way;
+                                   still 13: + the HEAL_*_MAX_* defines below (the kernels' compile-time limits, which the Python side reads
+                                   from this header): defines only, no signature changed */
 
 int heal_abi_version(void);
 const char* heal_last_error(void);
@@ -180,6 +182,8 @@ int heal_pillar_stem_block(const float* pillar_feat, const int32_t* cell_map, in
  *              (outside -> score 0); h1<=h0 means "no mask" (lidar agent); may be NULL
  *   out    [C,H,W]
  * -----------------------------------------------------------------------------------------------*/
+#define HEAL_WARP_MAX_AGENTS 8  /* agents handled per launch by every heal_warp_* / heal_fuse_warped* / heal_disco_fuse entry point
+                                   (max_cav is 5..8 in the reference configs) */
 int heal_warp_fuse(const float* feats, const float* occ, int n_agents, int channels, int H, int W,
                    const double* affine_host, const double* affine_dev, int grid_f64,
                    const int32_t* crop_host, float* out, void* stream);
@@ -189,6 +193,7 @@ int heal_warp_fuse(const float* feats, const float* occ, int n_agents, int chann
  *   word by word.  Level l: feats_host[l] [n_agents, C_l, H_l, W_l], occ_host[l] [n_agents, 1, H_l, W_l], out_host[l] [C_l, H_l, W_l]
  *   (HOST arrays of device pointers); the affine rows are shared by the levels (normalised coordinates); crop_host
  *   [n_levels][n_agents][4] or NULL.  Same arithmetic, operation for operation, as heal_warp_fuse: bit-identical results.  */
+#define HEAL_WARP_MAX_LEVELS 4  /* pyramid levels per launch of the heal_warp_*_levels* entry points */
 int heal_warp_fuse_levels(int n_levels, const float* const* feats_host, const float* const* occ_host, int n_agents,
                           const int32_t* channels_host, const int32_t* h_host, const int32_t* w_host,
                           const double* affine_host, const double* affine_dev, int grid_f64, const int32_t* crop_host,
@@ -223,7 +228,8 @@ int heal_warp_fuse_levels_src(int n_levels, const heal_k5_source* src_host, int 
  *     mode 1 (fusion_in_one.py:87-124): out = max_j x_j.
  *   Level l: feats_host[l] [n_agents, C_l, H_l, W_l], out_host[l] [C_l, H_l, W_l] (HOST arrays of device pointers); sqrt_dim_host[l]
  *   divides the logits (NULL: sqrt(C_l)); affine rows as heal_warp_fuse (host, or device memory read at run time).  Any C, H, W;
- *   1..4 levels, 1..8 agents.  No atomics: repeated launches are bit-equal.  Sampling arithmetic as heal_warp_fuse.              */
+ *   1..HEAL_WARP_MAX_LEVELS levels, 1..HEAL_WARP_MAX_AGENTS agents.  No atomics: repeated launches are bit-equal.  Sampling
+ *   arithmetic as heal_warp_fuse.                                                                                                */
 int heal_warp_att_fuse_levels(int n_levels, const float* const* feats_host, int n_agents, const int32_t* channels_host,
                               const int32_t* h_host, const int32_t* w_host, const float* sqrt_dim_host,
                               const double* affine_host, const double* affine_dev, int grid_f64, int mode,
@@ -238,7 +244,7 @@ int heal_warp_att_fuse_levels(int n_levels, const float* const* feats_host, int 
  *   the folded conv1_2 [32, 128] in the same order, b2 [32], w3 [8, 32], b3 [8], w4 [8], b4 [1].  feats [n_agents, C, H, W],
  *   out [C, H, W]; scores [n_agents, H, W] receives the post-ReLU logits when not NULL.  Samples outside a map are zeros and take
  *   part in the softmax.  With one agent and scores NULL the layer is skipped (weight exactly 1) and its operands may be NULL.
- *   C % 4 == 0, any H, W, 1..8 agents; affine rows as heal_warp_fuse (host, or device memory read at run time); sampling
+ *   C % 4 == 0, any H, W, 1..HEAL_WARP_MAX_AGENTS agents; affine rows as heal_warp_fuse (host, or device memory read at run time); sampling
  *   arithmetic as heal_warp_fuse.  fp32 on v_mfma_f32_16x16x4_f32; no atomics: repeated launches are bit-equal.                  */
 int heal_disco_fuse(const float* feats, int n_agents, int channels, int H, int W, const double* affine_host,
                     const double* affine_dev, int grid_f64, const float* e0, const float* w1n_frag, const float* w2_frag,
@@ -297,7 +303,7 @@ int heal_decode_nms(const float* cls, const float* reg, const float* dir, const 
  *   (opencood/data_utils/post_processor/voxel_postprocessor.py:277-405, driven by inference_utils.py:18-47
  *   inference_late_fusion): every cav's anchors are decoded, each projected with its OWN cav -> ego matrix, the candidates of
  *   all cavs pooled in cav order, the size / z filters applied, ONE rotated NMS over the top nms_top of the pool, then the
- *   range filter.  Agents 0 .. n_agents-1 are the entries of output_dict in order; 1..8 agents.
+ *   range filter.  Agents 0 .. n_agents-1 are the entries of output_dict in order; 1..HEAL_DECODE_MAX_AGENTS agents.
  *   cls_host / reg_host / dir_host / anchors_host: HOST arrays of n_agents device pointers, agent k's maps [A,H_k,W_k],
  *   [7A,H_k,W_k], [num_bins*A,H_k,W_k] and anchors [H_k,W_k,A,7] f32 (dir_host NULL, or every entry non-NULL); h_host / w_host
  *   the map sizes.  anchor_num, num_bins, the thresholds and gt_range are shared (one YAML fixes them).
@@ -309,6 +315,7 @@ int heal_decode_nms(const float* cls, const float* reg, const float* dir, const 
  *   out_agent [max_out] i32 or NULL: the source agent of kept box i.  Other outputs as heal_decode_nms.
  *   ws: heal_decode_nms_agents_workspace(sum_k H_k*W_k*A, nms_top) bytes.  No atomics beyond the wave-aggregated candidate
  *   slot counter (the composites are distinct, so the slot order does not matter): repeated launches are bit-equal.       */
+#define HEAL_DECODE_MAX_AGENTS 8  /* agents pooled by one heal_decode_nms_agents call (their table travels in the launch arguments) */
 size_t heal_decode_nms_agents_workspace(int anchors_total, int nms_top);
 int heal_decode_nms_agents(int n_agents, const float* const* cls_host, const float* const* reg_host,
                            const float* const* dir_host, const float* const* anchors_host, const int32_t* h_host,
@@ -330,7 +337,8 @@ int heal_quad_iou(const float* a, int n, const float* b, int m, float* iou, void
  *   det_score [n].  n_dev / m_dev: when non-NULL, int32 device words holding the LIVE counts, read by the kernels (clamped to
  *   0..n / 0..m); n / m are then the capacities of the buffers, whose tail may hold anything.  So the output of
  *   heal_decode_nms (out_corners, out_scores, out_count) is scored in place, and a replayed HIP graph follows the frame loaded.
- *   Limits: n <= 1024, m <= 256, 1 <= n_thr <= 8 (thr_host: HOST floats, passed by value); anything else is an error.
+ *   Limits: n <= HEAL_EVAL_MAX_DET, m <= HEAL_EVAL_MAX_GT, 1 <= n_thr <= HEAL_EVAL_MAX_THR (thr_host: HOST floats, passed by value);
+ *   anything else is an error.
  *   Semantics, per threshold t, the reference's: detections are walked in descending score; the IoU is taken against the
  *   ground-truth boxes still unmatched; if none is left or the maximum is < thr[t] (compared in fp32) the detection is FP,
  *   otherwise TP, and the FIRST maximum in original ground-truth order is removed for every later detection -- which may still
@@ -347,6 +355,9 @@ int heal_quad_iou(const float* a, int n, const float* b, int m, float* iou, void
  *   nothing advances and *overflow_dev is set to 1; the kernels never clear it.
  *   ws: heal_eval_match_workspace(n, m) bytes (the capacities): the IoU matrix and its row maxima.  Two kernels, no memset /
  *   memcpy node, no atomics: repeated launches are bit-equal.                                                              */
+#define HEAL_EVAL_MAX_DET 1024  /* detections (n) per heal_eval_match call */
+#define HEAL_EVAL_MAX_GT 256    /* ground-truth boxes (m) */
+#define HEAL_EVAL_MAX_THR 8     /* IoU thresholds matched at once (n_thr) */
 size_t heal_eval_match_workspace(int n_cap, int m_cap);
 int heal_eval_match(const float* det, int det_floats_per_box, int n, const int32_t* n_dev,
                     const float* det_score,
@@ -579,6 +590,7 @@ int heal_bev_pool_backward(const float* grad_cells, const float* depth_logit, co
  *   agent, masked to -inf as a key); out [n_pix, out_rows, 256]: rows 0..out_rows-1 of the result
  *   (out_rows = 1 keeps only the ego row, out_rows = n_agents keeps all).
  * -----------------------------------------------------------------------------------------------*/
+#define HEAL_AGENT_ATTENTION_MAX_AGENTS 8  /* n_agents of heal_agent_attention[_backward]: the sequence length of the attention */
 int heal_agent_attention(const float* q, const float* k, const float* v, const int32_t* key_mask, int n_pix,
                          int n_agents, int channels, int heads, float scale, int out_rows, float* out,
                          int agent_major /* 1: q, k, v, out are [n_agents, n_pix, 256] (the token order of the transformer) */,
@@ -819,10 +831,11 @@ int heal_window_attention_backward(const float* qkv, const float* pos_bias, cons
  *     out[token, h*d:(h+1)*d] = softmax(scale * Q K^T + bias[h], keys of agents >= n_valid masked to -inf) V.
  *   qkv [n_agents,H,W,3*heads*dim_head] f32 = the packed to_qkv projection (q | k | v chunks, each (head, dim)); bias [heads,T,T]
  *   (relative_position_bias_table[relative_position_index], token order (l w1 w2)) or NULL; out [n_agents,H,W,heads*dim_head].
- *   Queries of padded agents are not masked: their rows are written too.  window 4, dim_head 32, n_agents 1..8,
+ *   Queries of padded agents are not masked: their rows are written too.  window 4, dim_head 32, n_agents 1..HEAL_AGENT_WINDOW_MAX_AGENTS,
  *   1 <= n_valid <= n_agents, H and W multiples of window.  K / V of agents >= n_valid are never read.
  * heal_agent_mean: out[i] = mean over l of x[l, i] for x [n_agents, n_elems] (CoBEVT's mlp_head Reduce('b m d h w -> b d h w',
  *   'mean'), fusion_in_one.py:404-410, padded agents included); n_elems multiple of 4.                                            */
+#define HEAL_AGENT_WINDOW_MAX_AGENTS 8  /* n_agents of heal_agent_window_attention */
 int heal_agent_window_attention(const float* qkv, const float* bias, int n_agents, int n_valid, int H, int W, int heads,
                                 int dim_head, int window, int mode, float scale, float* out, void* stream);
 int heal_agent_mean(const float* x, int n_agents, long long n_elems, float* out, void* stream);
@@ -835,11 +848,12 @@ int heal_agent_mean(const float* x, int n_agents, long long n_elems, float* out,
  *   W_n * : 3x3 convolution, padding 1, of the warped neighbour maps xs [n_ego, N, cin, H, W]; w_frag = W_n [cout, cin, 3, 3] in
  *   heal_conv3x3's fragment order (ops.conv3x3_fragments, 16-B aligned); mask [n_ego, N, H, W]; E = the ego term W_e * x_e + bias,
  *   [cout, H, W] per ego, egos e_stride floats apart (a slice of a wider stacked convolution); residual [n_ego, cout, H, W] or
- *   NULL; out [n_ego, cout, H, W].  N in [1, 8].  nsplit in [1, N] splits the agent loop over blocks (partials in ws,
+ *   NULL; out [n_ego, cout, H, W].  N in [1, HEAL_V2V_MAX_AGENTS].  nsplit in [1, N] splits the agent loop over blocks (partials in ws,
  *   heal_v2v_message_workspace bytes, 16-B aligned; combined in split order); tile_h 4 | 8 | 16 output rows per block.
  * heal_gru_zero_state: the ConvGRU cell with a zero hidden state (sub_modules/convgru.py:52-72, h_cur = 0):
  *   h = sigmoid(u) * tanh(c),  u = gates[:, :C] (+ add[:, :C]),  c = gates[:, C:2C] (+ add[:, C:2C]);
  *   gates / add: n images of [2C, H, W] gates_stride / add_stride floats apart (add may be NULL); h [n, C, H, W].          */
+#define HEAL_V2V_MAX_AGENTS 8  /* n_agents (N) of heal_v2v_message */
 size_t heal_v2v_message_workspace(int n_ego, int cout, int H, int W, int nsplit);
 int heal_v2v_message(const float* xs, const float* mask, const float* e, long long e_stride, const float* w_frag,
                      const float* residual, int n_ego, int n_agents, int cin, int cout, int H, int W, int mode, int nsplit,
@@ -932,7 +946,7 @@ int heal_kd_kl_loss(const float* student, const float* teacher, int n, int chann
  *
  * heal_det_loss: PointPillarLoss.forward, opencood/loss/point_pillar_loss.py:36-122 (without its `iou` block), gamma = 2 and two
  *   direction bins.  cls_preds [n, A, H, W], reg_preds [n, 7A, H, W], dir_preds [n, 2A, H, W] or NULL (no `dir` block); channels
- *   are anchor-major (a*7+k, a*2+bin), A = anchors <= 4.  pos_equal_one, neg_equal_one [n, H, W, A] and targets [n, H, W, 7A]:
+ *   are anchor-major (a*7+k, a*2+bin), A = anchors <= HEAL_LOSS_MAX_ANCHORS.  pos_equal_one, neg_equal_one [n, H, W, A] and targets [n, H, W, 7A]:
  *   float32 (labels_f64 = 0) or float64 (1), read in place.  With nrm_n = max(#{pos > 0 in sample n}, 1):
  *     terms[0] = cls_weight / n * sum (1 - p_t)^2 (t alpha + (1 - t)(1 - alpha)) ce w,   t = pos, p = sigmoid(x),
  *                ce = max(x, 0) - x t + log1p(exp(-|x|)), p_t = t p + (1 - t)(1 - p), w = ((pos > 0) pos_cls_weight + (neg > 0)) / nrm_n
@@ -945,7 +959,7 @@ int heal_kd_kl_loss(const float* student, const float* teacher, int n, int chann
  *   anchor_yaw: HOST array of `anchors` radians (needed with dir_preds).  Three launches (counts, the pass, finish).
  *
  * heal_occ_loss: PointPillarPyramidLoss.calc_occ_loss, opencood/loss/point_pillar_pyramid_loss.py:71-107.  occ / grad: HOST arrays
- *   of `levels` (1..4) device pointers to [n, 1, H / k_i, W / k_i] maps, k_i = relative_downsample[i] (host), level_weight (host).
+ *   of `levels` (1..HEAL_OCC_LOSS_MAX_LEVELS) device pointers to [n, 1, H / k_i, W / k_i] maps, k_i = relative_downsample[i] (host), level_weight (host).
  *   A cell of level i is foreground if any anchor of any pixel of its k_i x k_i window (stride k_i, floor mode: trailing rows and
  *   columns are dropped, as max_pool2d does) has pos != 0, background if every one has neg != 0; nrm = max(foreground cells of the
  *   sample at that level, 1); the focal term above with t = fg, w = (fg pos_cls_weight + bg) / nrm.
@@ -960,6 +974,8 @@ int heal_kd_kl_loss(const float* student, const float* teacher, int n, int chann
  *   A target index outside [0, depth_bins) contributes 0 and receives an all-zero gradient (the reference's one_hot raises there).
  *   depth_bins <= 64 and a multiple of 4 keeps the pixel's logits in registers (every input byte read once); any other value takes
  *   a three-pass loop.  Two launches.                                                                                         */
+#define HEAL_LOSS_MAX_ANCHORS 4     /* anchors (A) of heal_det_loss and heal_occ_loss */
+#define HEAL_OCC_LOSS_MAX_LEVELS 4  /* pyramid levels of one heal_occ_loss call */
 size_t heal_det_loss_workspace(int n, int anchors, int H, int W);
 int heal_det_loss(const float* cls_preds, const float* reg_preds, const float* dir_preds, const void* pos_equal_one,
                   const void* neg_equal_one, const void* targets, int labels_f64, int n, int anchors, int H, int W,

@@ -45,7 +45,7 @@ def test_symbols_are_declared_bound_and_exported():
     lib = _capi.lib()
     for name in SYMBOLS:
         assert name in declared, name
-        assert name in _capi._SIGNATURES, name
+        assert name in _capi.signatures(), name
         assert hasattr(lib, name), name
     assert _capi.abi_version_of_header() == 13
     assert int(lib.heal_abi_version()) == 13

@@ -24,12 +24,12 @@ def test_library_loads_and_exports_every_declared_symbol():
     L = ctypes.CDLL(_capi.LIB_PATH)
     missing = [n for n in names if not hasattr(L, n)]
     assert not missing, f"declared in include/heal_amd.h but not exported: {missing}"
-    assert set(names) <= set(_capi._SIGNATURES), "ctypes signature table is missing a declared symbol"
+    assert set(names) <= set(_capi.signatures()), "the derived ctypes signatures are missing a declared symbol"
     assert _capi.lib().heal_abi_version() == _capi.abi_version_of_header() >= 2
     # the measured-negative kernels are NOT part of the shipped ABI: declared in their own header, bound by the
-    # signature table, exported only by a HEAL_BUILD_EXPERIMENTAL=1 library -- all of them or none
+    # signatures derived from it, exported only by a HEAL_BUILD_EXPERIMENTAL=1 library -- all of them or none
     exp = _capi.declared_symbols(experimental=True)
-    assert exp and not set(exp) & set(names) and set(exp) <= set(_capi._SIGNATURES)
+    assert exp and not set(exp) & set(names) and set(exp) <= set(_capi.signatures(experimental=True)) <= set(_capi.signatures())
     have = [n for n in exp if hasattr(L, n)]
     assert have == [] or have == exp, f"half an experimental build: {have}"
     import os
@@ -94,6 +94,144 @@ def test_voxelize_workspace_layout_depends_on_the_table_alone(axc, dense):
                     got = _capi.query("heal_voxelize_batch_workspace", capacity, agents, P, mv, axc)
                     assert got >= _vox_layout(n, min(n, agents * mv), P, axc)["total"], (n, P, mv, agents)
                     assert agents > 1 or got == one        # the single-cloud form is the one-agent batch: they share a buffer
+
+
+def test_signatures_are_read_from_the_header_known_answers():
+    """One prototype per rule of the header parser, written out: these are the argument lists ctypes converts with."""
+    from heal_amd import _capi
+    P, I, F, D, Z, LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t, ctypes.c_longlong
+    sig = _capi.signatures()
+    assert sig["heal_last_error"] == (ctypes.c_char_p, [])                                   # const char* return, ()
+    assert sig["heal_abi_version"] == (I, [])                                                # (void)
+    assert sig["heal_voxelize_workspace"] == (Z, [I, I, I, LL])                              # long long scalar, size_t return
+    assert sig["heal_voxelize_layout"] == (I, [I, I, I, LL, P])                              # size_t* is a pointer
+    assert sig["heal_det_loss"] == (I, [P] * 6 + [I] * 5 + [F] * 6 + [P, D] + [P] * 5 + [Z, P])   # const double* next to a double
+    assert sig["heal_warp_fuse_levels_src"] == (I, [I, P, I, P, P, P, P, P, I, P, P, P])     # const heal_k5_source*, float* const*
+    assert sig["heal_linear"] == (I, [P, I, I, LL, P, P, P, I, P, I, I, P, I, P] + [I] * 7 + [LL, I, P])
+    assert sig["heal_gru_zero_state"] == (I, [P, LL, P, LL, I, I, I, I, P, P])
+    assert sig["heal_occ_loss_workspace"] == (Z, [I, I, I, I, P])                            # const int* last
+    # int32_t / int64_t / unsigned by value: none in the headers today, the mapping is fixed all the same
+    assert _capi.parse_prototypes("int heal_x(int32_t a, const int64_t b, uint32_t, uint64_t d, unsigned e, unsigned int f, double);") == {
+        "heal_x": (I, [ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint, ctypes.c_uint, D])}
+    assert ctypes.c_int32 is I and ctypes.sizeof(ctypes.c_int64) == ctypes.sizeof(LL) == 8
+
+
+def test_signatures_cover_exactly_the_declared_symbols():
+    from heal_amd import _capi
+    main, exp = _capi.signatures(experimental=False), _capi.signatures(experimental=True)
+    assert sorted(main) == _capi.declared_symbols() and sorted(exp) == _capi.declared_symbols(experimental=True)
+    assert not set(main) & set(exp) and (len(main), len(exp)) == (126, 7)
+    assert _capi.signatures() == {**main, **exp}
+    # the names the pre-parser regex found: every `heal_xxx(` outside a block comment
+    for path, sig in ((_capi.HEADER, main), (_capi.HEADER_EXPERIMENTAL, exp)):
+        import re
+        text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+        assert sorted(set(re.findall(r"\b(heal_[a-z0-9_]+)\s*\(", text))) == sorted(sig)
+
+
+@pytest.mark.parametrize("text", ["int heal_x(short v);", "int heal_x(heal_k5_source s);", "int heal_x(int (*cb)(int));",
+                                  "int heal_x(int n, ...);", "void heal_x(int n);", "float* heal_x(int n);"],
+                         ids=["unknown-type", "struct-by-value", "function-pointer", "variadic", "void-return", "pointer-return"])
+def test_header_parser_refuses_what_it_cannot_map(text):
+    from heal_amd import _capi
+    with pytest.raises(_capi.HealAmdError, match="heal_x"):
+        _capi.parse_prototypes(text)
+    with pytest.raises(_capi.HealAmdError, match="heal_x"):                                  # ... wherever it stands in a header
+        _capi.parse_prototypes("/* c */\n#include <stddef.h>\nint heal_ok(int n);\n" + text + "\nint heal_ok2(void);\n")
+
+
+def test_header_parser_skips_nothing_silently():
+    from heal_amd import _capi
+    with pytest.raises(_capi.HealAmdError, match="not a prototype"):
+        _capi.parse_prototypes("int heal_ok(int n);\nstatic int helper(int n);\n")
+    assert _capi.parse_prototypes("// int heal_no(int);\n/* int heal_no2(int); */\ntypedef struct heal_s {\n    int a;  /* x */\n"
+                                  "    float b[4];\n} heal_s;\nint heal_ok(const heal_s* s);\n") == {
+        "heal_ok": (ctypes.c_int, [ctypes.c_void_p])}
+
+
+def test_derived_signatures_carry_size_t_long_long_and_out_pointers():
+    """Two host-only entry points through the derived argtypes, against values the suite asserts elsewhere."""
+    from heal_amd import _capi, build
+    build.build()
+    assert _capi.query("heal_kd_kl_loss_workspace", 2, 256, 256, 256) == 8192                # size_t return (test_kd_cpu.py)
+    lay = _vox_layout(70_000, 37, 32, 3 * 512 * 512)                                         # long long by value, size_t* out
+    assert lay["dense"] == 1 and lay["slots"] == 3 * 512 * 512 and lay["meta_off"] == lay["clean_off"] + lay["clean_bytes"]
+    # 2^32 + 1200 cells is a hash grid; truncated to 32 bits it would be the dense table of 1200 cells
+    assert _vox_layout(1025, 37, 32, 1200)["dense"] == 1 and _vox_layout(1025, 37, 32, 2 ** 32 + 1200)["dense"] == 0
+
+
+def test_k5_source_mirrors_the_c_struct(tmp_path):
+    """ops.K5Source is the one hand-written struct mirror: its size and field offsets against the C compiler's."""
+    import subprocess
+    from heal_amd import ops
+    fields = [f for f, _ in ops.K5Source._fields_]
+    assert fields == ["feat", "occ", "feat_row", "feat_plane", "occ_row", "box"]
+    src = tmp_path / "k5_layout.c"
+    src.write_text('#include <stdio.h>\n#include "heal_amd.h"\nint main(void) {\n    printf("%zu", sizeof(heal_k5_source));\n'
+                   + "".join(f'    printf(" %zu %zu", offsetof(heal_k5_source, {f}), sizeof(((heal_k5_source*)0)->{f}));\n'
+                             for f in fields) + "    return 0;\n}\n")
+    exe = tmp_path / "k5_layout"
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True, capture_output=True)
+    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    mirror = [getattr(ops.K5Source, f) for f in fields]
+    assert got == [ctypes.sizeof(ops.K5Source)] + [v for m in mirror for v in (m.offset, m.size)]
+    assert got[0] == 56
+
+
+# every place a bare 4 or 8 still follows a comparison under heal_amd/: tile arithmetic, layer widths and one shape predicate.  A
+# kernel's agent / level / anchor limit is a HEAL_*_MAX_* define of the header and reaches Python through ops' constants.
+_BARE_4_OR_8 = {
+    ("heal_amd/ops.py", "DISCO_WIDTHS = (128, 32, 8)        # PixelWeightLayer: 2C -> 128 -> 32 -> 8 -> 1"),
+    ("heal_amd/ops.py", "wm[mt*16 + (lane & 15)][ks*4 + (lane >> 4)].\"\"\""),
+    ("heal_amd/ops.py", "if cout != 64 or tuple(w.shape[2:]) != (7, 7) or not 1 <= cin <= 4:"),          # heal_stem7x7's shape predicate
+    ("heal_amd/ops.py", "U[xi = 9 (wave & 3) + xi_i][co = 32 mb + 16 (wave >> 2) + (lane & 15)][ci = 16 chunk + 4 ks + (lane >> 4)], "
+                        "zero-padded.\"\"\""),
+    ("heal_amd/opencood/models/fuse_modules/disco_fuse.py",
+     "cat(warped neighbour, ego), 2C -> 128 -> 32 -> 8 -> 1.  Plain torch layers: this is the CPU, gradient and training arithmetic;"),
+}
+
+
+def test_kernel_limits_come_from_the_header():
+    import re
+    from heal_amd import _capi, ops
+    from heal_amd.opencood.models.fuse_modules import fusion_in_one
+    want = {"HEAL_WARP_MAX_AGENTS": 8, "HEAL_WARP_MAX_LEVELS": 4, "HEAL_DECODE_MAX_AGENTS": 8, "HEAL_V2V_MAX_AGENTS": 8,
+            "HEAL_AGENT_WINDOW_MAX_AGENTS": 8, "HEAL_AGENT_ATTENTION_MAX_AGENTS": 8, "HEAL_LOSS_MAX_ANCHORS": 4,
+            "HEAL_OCC_LOSS_MAX_LEVELS": 4, "HEAL_EVAL_MAX_DET": 1024, "HEAL_EVAL_MAX_GT": 256, "HEAL_EVAL_MAX_THR": 8}
+    header = open(_capi.HEADER).read()
+    assert sorted(re.findall(r"^#define\s+(HEAL_\w+_MAX_\w+)", header, re.M)) == sorted(want)
+    assert {k: _capi.header_define(k) for k in want} == want              # the values this ABI version was reviewed with
+    assert _capi.header_define("HEAL_AMD_ABI_VERSION") == _capi.abi_version_of_header() == 13
+    with pytest.raises(_capi.HealAmdError, match="HEAL_NO_SUCH_LIMIT"):
+        _capi.header_define("HEAL_NO_SUCH_LIMIT")
+    d = _capi.header_define
+    for names, define in ((("WARP_MAX_AGENTS", "WARP_ATT_MAX_AGENTS", "DISCO_MAX_AGENTS"), "HEAL_WARP_MAX_AGENTS"),
+                          (("WARP_MAX_LEVELS", "WARP_ATT_MAX_LEVELS"), "HEAL_WARP_MAX_LEVELS"),
+                          (("DECODE_MAX_AGENTS",), "HEAL_DECODE_MAX_AGENTS"), (("V2V_MAX_AGENTS",), "HEAL_V2V_MAX_AGENTS"),
+                          (("AGENT_WINDOW_MAX_AGENTS",), "HEAL_AGENT_WINDOW_MAX_AGENTS"),
+                          (("AGENT_ATTENTION_MAX_AGENTS",), "HEAL_AGENT_ATTENTION_MAX_AGENTS"),
+                          (("LOSS_MAX_ANCHORS",), "HEAL_LOSS_MAX_ANCHORS"), (("OCC_LOSS_MAX_LEVELS",), "HEAL_OCC_LOSS_MAX_LEVELS"),
+                          (("EVAL_MAX_DET",), "HEAL_EVAL_MAX_DET"), (("EVAL_MAX_GT",), "HEAL_EVAL_MAX_GT"),
+                          (("EVAL_MAX_THR",), "HEAL_EVAL_MAX_THR")):
+        for name in names:
+            assert getattr(ops, name) == d(define), (name, define)
+    assert fusion_in_one.MS_MAX_AGENTS == d("HEAL_WARP_MAX_AGENTS")
+    # ... and every .hip / .h constant is spelled with its define, never with the number again
+    csrc = os.path.join(ROOT, "heal_amd", "csrc")
+    used = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")))
+    for define in want:
+        assert len(re.findall(rf"constexpr int \w+ = {define};", used)) == 1, define
+    # no bare limit is left in the Python tree (the leading \b of a pattern like r"\b(<=|>) ?8\b" would need a word character
+    # right before the operator and so miss every `x <= 8` written with a space: left out, which only matches more)
+    hits = set()
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "heal_amd")):
+        for f in sorted(files):
+            if f.endswith(".py"):
+                path = os.path.join(dirpath, f)
+                for line in open(path):
+                    if re.search(r"(<=|>) ?8\b", line) or re.search(r"(<=|>) ?4\b", line):
+                        hits.add((os.path.relpath(path, ROOT).replace(os.sep, "/"), line.strip()))
+    assert hits == _BARE_4_OR_8, (sorted(hits - _BARE_4_OR_8), sorted(_BARE_4_OR_8 - hits))
 
 
 # ------------------------------------------------------------------------------------- host mirror

@@ -16,7 +16,7 @@ def test_abi_12_declares_and_exports_the_agents_entry_points():
     declared = _capi.declared_symbols()
     for name in NEW_SYMBOLS:
         assert name in declared, f"{name} is not declared in include/heal_amd.h"
-        assert name in _capi._SIGNATURES, f"{name} has no ctypes signature"
+        assert name in _capi.signatures(), f"{name} has no ctypes signature"
     assert _capi.abi_version_of_header() == 13
     from heal_amd import build
     build.build()
