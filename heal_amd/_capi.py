@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HEAL_AMD_LIB") or os.path.join(HERE, "lib", "libheal_amd.so")  # env: A/B a rebuilt library
 HEADER = os.path.join(os.path.dirname(HERE), "include", "heal_amd.h")
 HEADER_EXPERIMENTAL = os.path.join(os.path.dirname(HERE), "include", "heal_amd_experimental.h")
+HEADER_TRAIN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train.h")
 
 _lib = None
 
@@ -71,6 +72,14 @@ def signatures(experimental=None):
         return parse_prototypes(f.read())
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_train():
+    """{name: (restype, argtypes)} of include/heal_amd_train.h: the training-side entry points (the dense convolutions' weight
+    gradient).  Every build exports them; they are not part of the versioned inference ABI that signatures() describes."""
+    with open(HEADER_TRAIN) as f:
+        return parse_prototypes(f.read())
+
+
 def declared_symbols(experimental=False):
     """Function names declared in include/heal_amd.h (the shipped C ABI), or with experimental=True in
     include/heal_amd_experimental.h."""
@@ -103,7 +112,7 @@ def lib():
         # process do not share devices, streams or allocations).
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in signatures().items():
+        for name, (res, args) in {**signatures(), **signatures_train()}.items():
             if not hasattr(L, name):
                 continue  # declared but not built yet -> surfaces in call() / the symbol test
             f = getattr(L, name)

@@ -66,6 +66,7 @@ def _deps():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     inc = os.path.join(os.path.dirname(HERE), "include")
     hdrs.append(os.path.join(inc, "heal_amd.h"))
+    hdrs.append(os.path.join(inc, "heal_amd_train.h"))      # the training-side entry points: part of every build
     if EXPERIMENTAL:
         hdrs.append(os.path.join(inc, "heal_amd_experimental.h"))
     return hdrs

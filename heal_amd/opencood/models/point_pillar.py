@@ -9,13 +9,13 @@ import torch.nn as nn
 from heal_amd.opencood.models.heter_encoders import PointPillar as _PillarEncoder
 from heal_amd.opencood.models.sub_modules.base_bev_backbone import BaseBEVBackbone
 from heal_amd.opencood.models.sub_modules.base_bev_backbone_resnet import ResNetBEVBackbone
-from heal_amd.opencood.models.sub_modules.bev_blocks import conv_bias_act
+from heal_amd.opencood.models.sub_modules.bev_blocks import conv_bias_act, grad_conv
 from heal_amd.opencood.models.sub_modules.downsample_conv import DownsampleConv
 
 
 def head(conv, x):
     if torch.is_grad_enabled() and (x.requires_grad or conv.training or conv.weight.requires_grad):   # gradient path
-        return conv(x)
+        return grad_conv(conv, x)
     return conv_bias_act(x, conv.weight, conv.bias, conv.stride, conv.padding, 1, 1, False)
 
 

@@ -7,7 +7,8 @@ downsample_conv.py:7-49, feature_alignnet.py:12-39, feature_alignnet_modules.py:
 naive_compress.py:5-31.
 
 Training / fine-tuning (gradients enabled, see `grad_path`): the blocks run conv -> BatchNorm -> ReLU as torch modules with
-autograd.  Inference design (eval mode): every Conv+BatchNorm pair is folded into one convolution with bias
+autograd; under HEAL_CONV_GRAD=kernel the dense 3x3 / 1x1 convolutions among them run as ops.ConvGrad (`grad_conv`).
+Inference design (eval mode): every Conv+BatchNorm pair is folded into one convolution with bias
 (heal_amd.derived: re-folded when a parameter changes), ReLU and the residual add run in place -- one pass
 over each BEV map instead of three.  Pointwise, dense 3x3 (padding 1, stride 1 | 2) and 32-group 3x3 convolutions run on
 the hand-written fp32-MFMA / stencil kernels of libheal_amd with that epilogue fused; what is left to the library
@@ -110,6 +111,26 @@ def grad_path(x, *modules):
     return False
 
 
+def grad_conv(conv, x, padding=None):
+    """conv(x) on the gradient path.  Under HEAL_CONV_GRAD=kernel (ops.conv_grad_enabled) a dense fp32 convolution on the device --
+    groups 1, dilation 1, 3x3 with padding 1 or 1x1 with padding 0, stride 1 | 2 -- runs as ops.ConvGrad: forward, data gradient and
+    weight gradient on this library's kernels.  Everything else (grouped, depthwise, 7x7, transposed, CPU tensors, other dtypes, the
+    switch unset) calls the module exactly as before.  padding: the padding of an explicit ZeroPad2d in front of a padding-0
+    convolution (BaseBEVBackbone's stage openers); the caller has NOT applied it."""
+    from heal_amd import ops
+    if (ops.conv_grad_enabled() and type(conv) is nn.Conv2d and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
+            and conv.weight.dtype == torch.float32 and not torch.is_autocast_enabled()
+            and conv.groups == 1 and conv.dilation == (1, 1) and conv.padding_mode == "zeros"
+            and conv.kernel_size in ((1, 1), (3, 3)) and conv.stride in ((1, 1), (2, 2))
+            and (conv.padding if padding is None else (padding, padding)) == (conv.kernel_size[0] // 2,) * 2
+            and (padding is None or conv.padding == (0, 0))
+            and ops.conv_grad_supported(x, conv.weight, conv.stride[0])):
+        return ops.ConvGrad.apply(x, conv.weight, conv.bias, conv.stride[0])
+    if padding is not None:
+        x = F.pad(x, (padding,) * 4)
+    return conv(x)
+
+
 def _require_eval(module):
     """For the operators that still have no gradient path (the sparse 3-D encoder K3)."""
     if module.training and torch.is_grad_enabled():
@@ -133,7 +154,7 @@ class ConvBN(nn.Module):
         if out is not None:      # gradient path with a destination (CPU tests of the stage walks): compute, then copy
             return out.copy_(ConvBN.run(x, conv, bn, relu, residual))
         if grad_path(x, bn, conv):   # training / fine-tuning: conv -> BatchNorm (batch statistics when training) -> + -> ReLU
-            y = bn(conv(x))
+            y = bn(grad_conv(conv, x))
             if residual is not None:
                 y = y + residual
             return F.relu(y) if relu else y
@@ -479,7 +500,9 @@ class DoubleConv(nn.Module):
 
     def forward(self, x):
         if grad_path(x, self):
-            return self.double_conv(x)
+            for m in self.double_conv:
+                x = grad_conv(m, x) if isinstance(m, nn.Conv2d) else m(x)
+            return x
         c0, c1 = self.double_conv[0], self.double_conv[2]
         x = conv_bias_act(x, c0.weight, c0.bias, c0.stride, c0.padding, 1, 1, True)
         return conv_bias_act(x, c1.weight, c1.bias, c1.stride, c1.padding, 1, 1, True)

@@ -3032,6 +3032,125 @@ def conv3x3(x, w, bias=None, residual=None, relu=False, stride=1):
     return y
 
 
+# ------------------------------------------------------------------------------------------------ dense convolution backward
+def conv_grad_enabled():
+    """HEAL_CONV_GRAD=kernel: the dense 3x3 / 1x1 convolutions of the gradient path run forward, data gradient and weight gradient
+    on this library's kernels (ConvGrad).  Opt-in: until scripts/conv_grad_bench.py says otherwise the library composition stays
+    the default, as with HEAL_WATTN_GRAD."""
+    return os.environ.get("HEAL_CONV_GRAD", "") == "kernel"
+
+
+# what ConvGrad ran since the process started (tests and scripts/conv_grad_bench.py read it): forward calls, heal_conv_wgrad calls,
+# data gradients on heal_conv3x3 / heal_conv1x1 and data gradients left to the library (stride 2, maps the pointwise kernel refuses)
+CONV_GRAD_CALLS = {"forward": 0, "wgrad": 0, "dx_kernel": 0, "dx_library": 0}
+
+
+def _conv_wgrad_shape(x, g, k, stride):
+    """(n, cin, cout, H, W) if x [n, cin, H, W] and g [n, cout, Ho, Wo] belong to one k x k convolution of that stride, else None."""
+    if not (isinstance(x, torch.Tensor) and isinstance(g, torch.Tensor) and x.dim() == 4 and g.dim() == 4
+            and k in (1, 3) and stride in (1, 2)):
+        return None
+    n, cin, H, W = (int(v) for v in x.shape)
+    if min(n, cin, H, W) < 1 or int(g.shape[1]) < 1:
+        return None
+    if (int(g.shape[0]), int(g.shape[2]), int(g.shape[3])) != (n, (H - 1) // stride + 1, (W - 1) // stride + 1):
+        return None
+    return n, cin, int(g.shape[1]), H, W
+
+
+def conv_wgrad_supported(x, g, k, stride):
+    """True if heal_conv_wgrad takes the pair: f32 device tensors x [n, Cin, H, W], g [n, Cout, Ho, Wo], k 1 | 3 (padding k // 2),
+    stride 1 | 2.  No alignment or divisibility requirement."""
+    shape = _conv_wgrad_shape(x, g, k, stride)
+    return (shape is not None and x.is_cuda and g.is_cuda and x.dtype == torch.float32 and g.dtype == torch.float32
+            and bool(_capi.query("heal_conv_wgrad_supported", *shape, int(k), int(stride))))
+
+
+def conv_wgrad(x, g, k, stride):
+    """Weight gradient of a dense convolution (what torch.nn.grad.conv2d_weight returns): x [n, Cin, H, W], g [n, Cout, Ho, Wo]
+    f32 cuda, k 1 | 3 with padding k // 2, stride 1 | 2 -> dW [Cout, Cin, k, k].  fp32 MFMA over the pixels; the reduction is
+    split over blocks and summed in a fixed order (bit-equal across calls)."""
+    x = _need(x, torch.float32, "x")
+    g = _need(g, torch.float32, "g")
+    shape = _conv_wgrad_shape(x, g, k, stride)
+    if shape is None or not _capi.query("heal_conv_wgrad_supported", *shape, int(k), int(stride)):
+        raise _capi.HealAmdError(f"conv_wgrad: x {tuple(x.shape)} and g {tuple(g.shape)} do not belong to a supported "
+                                 f"convolution (k={k}, stride={stride}; k 1 | 3, stride 1 | 2)")
+    n, cin, cout, H, W = shape
+    dw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=x.device)
+    nbytes = _capi.query("heal_conv_wgrad_workspace", n, cin, cout, H, W, int(k), int(stride))
+    ws = _workspace("conv_wgrad", nbytes, x.device) if nbytes else None
+    with _Timed(f"conv_wgrad{k}_{cin}_{cout}" + ("_s2" if stride == 2 else ""), 2.0 * g.numel() * cin * k * k,
+                4.0 * (x.numel() + g.numel() + dw.numel())):
+        _capi.call("heal_conv_wgrad", _ptr(x), _ptr(g), n, cin, cout, H, W, int(k), int(stride), _ptr(dw), _ptr(ws),
+                   ws.numel() if ws is not None else 0, _stream())
+    CONV_GRAD_CALLS["wgrad"] += 1
+    return dw
+
+
+def conv_grad_supported(x, weight, stride):
+    """True if ConvGrad takes the convolution: x f32 on the device, weight [Cout, Cin, k, k] with k 1 | 3 (padding k // 2, no groups,
+    no dilation), stride 1 | 2, and a map the forward kernel takes (heal_conv1x1 wants 16-byte pixel rows)."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and weight.is_cuda
+            and weight.dtype == torch.float32 and weight.dim() == 4 and stride in (1, 2)):
+        return False
+    n, cin, H, W = (int(v) for v in x.shape)
+    cout, k = int(weight.shape[0]), int(weight.shape[2])
+    if tuple(weight.shape[1:]) != (cin, k, k) or k not in (1, 3) or min(n, cin, cout, H, W) < 1:
+        return False
+    if not _capi.query("heal_conv_wgrad_supported", n, cin, cout, H, W, k, int(stride)):
+        return False
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    return k == 3 or conv1x1_supported(cin, cout, Ho * Wo, stride, Wo)
+
+
+def _conv_grad_wt(weight):
+    """The weight of the data-gradient convolution: [Cin, Cout, k, k], taps flipped (3x3) -- dx = conv(g, flip(W)^T)."""
+    k = int(weight.shape[2])
+    return _derived("conv_grad_wt", (weight,),
+                    lambda: (weight.flip(2, 3) if k == 3 else weight).transpose(0, 1).contiguous())
+
+
+class ConvGrad(torch.autograd.Function):
+    """A dense convolution (3x3 padding 1 | 1x1, stride 1 | 2) under autograd on this library's kernels:
+    apply(x, weight, bias | None, stride) -> conv2d(x, weight, bias, stride, k // 2).  Forward: heal_conv3x3 / heal_conv1x1 on the
+    raw weight.  Backward: dW = heal_conv_wgrad, db = sum of g, dx = the forward kernels on the flipped, channel-transposed weight at
+    stride 1; at stride 2 (and for maps the pointwise kernel refuses) dx = torch.nn.grad.conv2d_input on the library."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride):
+        x = x.contiguous()
+        k = int(weight.shape[2])
+        y = conv3x3(x, weight, bias, None, False, stride) if k == 3 else conv1x1(x, weight, bias, None, 0, stride=stride)
+        ctx.save_for_backward(x, weight)
+        ctx.cfg = (k, int(stride), bias is not None)
+        CONV_GRAD_CALLS["forward"] += 1
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        k, stride, has_bias = ctx.cfg
+        g = g.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            cin, cout = int(weight.shape[1]), int(weight.shape[0])
+            if stride == 1 and k == 3:
+                dx = conv3x3(g, _conv_grad_wt(weight), None, None, False, 1)
+            elif stride == 1 and conv1x1_supported(cout, cin, int(g.shape[2] * g.shape[3])):
+                dx = conv1x1(g, _conv_grad_wt(weight), None, None, 0)
+            if dx is not None:
+                CONV_GRAD_CALLS["dx_kernel"] += 1
+            else:
+                dx = torch.nn.grad.conv2d_input(x.shape, weight, g, stride=stride, padding=k // 2)
+                CONV_GRAD_CALLS["dx_library"] += 1
+        if ctx.needs_input_grad[1]:
+            dw = conv_wgrad(x, g, k, stride)
+        if has_bias and ctx.needs_input_grad[2]:
+            db = g.sum((0, 2, 3))
+        return dx, dw, db, None
+
+
 def channel_dot_supported(x):
     return x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and int(x.shape[2] * x.shape[3]) % 4 == 0
 
