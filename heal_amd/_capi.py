@@ -8,8 +8,10 @@ import functools
 import os
 import re
 
+from heal_amd import switches
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("HEAL_AMD_LIB") or os.path.join(HERE, "lib", "libheal_amd.so")  # env: A/B a rebuilt library
+LIB_PATH = switches.get("HEAL_AMD_LIB") or os.path.join(HERE, "lib", "libheal_amd.so")  # env: A/B a rebuilt library
 HEADER = os.path.join(os.path.dirname(HERE), "include", "heal_amd.h")
 HEADER_EXPERIMENTAL = os.path.join(os.path.dirname(HERE), "include", "heal_amd_experimental.h")
 HEADER_TRAIN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train.h")
@@ -132,7 +134,7 @@ def lib():
 # HEAL_TRACE_CALLS=1: debugging aid for GPU memory faults (a fault kills the process without a Python traceback).  Every C-ABI call
 # is announced on stderr BEFORE it is issued and the device is synchronised AFTER it (outside stream captures), so the last line
 # printed names the faulting operator.  =2 also prints the pointer / integer arguments.
-_TRACE = int(os.environ.get("HEAL_TRACE_CALLS", "0") or 0)
+_TRACE = switches.number("HEAL_TRACE_CALLS")
 
 
 def _trace_call(name, args):
@@ -160,7 +162,7 @@ def _trace_done(name):
 # DURING a capture is logged; whoever owns the graph takes the log (guard_take) and has it verified before replays (guard_check): each
 # address must still lie in memory the caching allocator has handed out -- an active block of the ordinary pool, or any block of a
 # graph-private pool that is still mapped (tensors allocated and released inside a capture live there for the life of their graph).
-_GUARD = os.environ.get("HEAL_GRAPH_GUARD", "0") == "1"
+_GUARD = switches.on("HEAL_GRAPH_GUARD")
 _guard_log = []
 
 

@@ -19,6 +19,8 @@ import shutil
 import subprocess
 import sys
 
+from heal_amd import switches
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
@@ -37,7 +39,7 @@ def _hipcc():
     raise RuntimeError("hipcc not found (set HIPCC)")
 
 
-EXPERIMENTAL = os.environ.get("HEAL_BUILD_EXPERIMENTAL", "0") == "1"
+EXPERIMENTAL = switches.on("HEAL_BUILD_EXPERIMENTAL")
 EXP_DIR = os.path.join(CSRC, "experimental")
 
 

@@ -14,6 +14,8 @@ head, detection heads, decode + NMS).
 import torch
 import torch.distributed as dist
 
+from heal_amd import switches
+
 
 def agent_owner(a, world):
     """Rank that encodes scene agent a (slot a // world of that rank's buffer)."""
@@ -176,8 +178,7 @@ class _Sharded:
         self.rank = rank
         self.world = world
         self.wire_dtype = wire_dtype if wire_dtype is not None else torch.float32
-        import os
-        self.collective = collective or os.environ.get("HEAL_COLLECTIVE", "gather")
+        self.collective = collective or switches.get("HEAL_COLLECTIVE")
         if self.collective not in ("gather", "all_gather", "p2p"):
             raise ValueError(f"collective must be 'gather', 'all_gather' or 'p2p', got {self.collective!r}")
         self._g_local = self._g_tail = None
@@ -377,8 +378,7 @@ class ShardedCollab(_Sharded):
     scores, warped to the ego frame by the owning rank."""
 
     def __new__(cls, model, rank, world, wire_dtype=None, collective=None, split=None):
-        import os
-        split = split or os.environ.get("HEAL_SPLIT", "levels")
+        split = split or switches.get("HEAL_SPLIT")
         if split == "compressed" and cls is ShardedCollab:
             return super().__new__(ShardedCollabCompressed)
         return super().__new__(cls)
@@ -876,7 +876,6 @@ class ShardedBaselineStriped(ShardedBaseline):
 def make_sharded(model, rank, world, wire_dtype=None, collective=None, split=None):
     """The agent-sharded runner that matches the model class.  split: "levels" (default: warped pyramid levels travel) |
     "compressed" (HeterPyramidCollab with a compressor: the compressor's encoder output travels)."""
-    import os
     name = type(model).__name__
     if name == "HeterPyramidCollab":
         return ShardedCollab(model, rank, world, wire_dtype, collective, split)
@@ -888,7 +887,7 @@ def make_sharded(model, rank, world, wire_dtype=None, collective=None, split=Non
             raise NotImplementedError("no agent-sharded split for DiscoFusion: its pixel weights need the ego's unwarped map next to "
                                       "every gathered agent (fusion_in_one.py:188-192), which the warp-then-gather exchange does not carry")
         if (world > 1 and type(model.fusion_net).__name__ == "V2XViTFusion"
-                and os.environ.get("HEAL_V2XVIT_STRIPES", "1") != "0"):
+                and switches.on("HEAL_V2XVIT_STRIPES")):
             return ShardedBaselineStriped(model, rank, world, wire_dtype, collective)
         return ShardedBaseline(model, rank, world, wire_dtype, collective)
     raise NotImplementedError(f"no agent-sharded split for {name}")

@@ -3,13 +3,12 @@ generate_anchor_box (:30-83) on the host, post_process (:245-405) on the gfx950 
 kernel K8 (heal_decode_nms), generate_label (:85-207) on heal_label_assign, collate_batch (:210-243) and the
 inherited generate_gt_bbx (base_postprocessor.py:47-107) on the host."""
 import math
-import os
 import sys
 
 import numpy as np
 import torch
 
-from heal_amd import ops
+from heal_amd import ops, switches
 
 
 _DEFERRED_ANCHORS = None
@@ -45,10 +44,10 @@ class VoxelPostprocessor:
         # created.  train=False: the labels are unused, zeros are returned.  train=True: it only packs its inputs and
         # the assignment happens on the device when a loss first reads the labels (resolve_deferred_labels); datasets
         # whose collate reads the label tensors by key (the heter datasets) need num_workers=0 and no deferral instead.
-        self.defer = bool(self.params.get('defer_to_device', False)) or os.environ.get("HEAL_DEFER_VOXELIZE", "0") == "1"
+        self.defer = bool(self.params.get('defer_to_device', False)) or switches.on("HEAL_DEFER_VOXELIZE")
         # labels are never read (tools/inference.py): `postprocess.inference_only: true` or HEAL_INFERENCE_ONLY=1
         self.inference_only = (bool(self.params.get('inference_only', False))
-                               or os.environ.get("HEAL_INFERENCE_ONLY", "0") == "1")
+                               or switches.on("HEAL_INFERENCE_ONLY"))
 
     def generate_anchor_box(self):
         a = self.params['anchor_args']
@@ -260,7 +259,7 @@ class VoxelPostprocessor:
     def _late_fused_ok(self, output_dict):
         """Several cavs go to the pooled decode + NMS kernel (ops.decode_nms_agents) when every cav's maps are CUDA fp32 with
         batch size 1 on ONE device, there is no iou_preds head and at most 8 cavs; HEAL_LATE_FUSED=0 keeps the per-cav tensor path."""
-        if os.environ.get("HEAL_LATE_FUSED", "1") == "0" or len(output_dict) > ops.DECODE_MAX_AGENTS:
+        if not switches.on("HEAL_LATE_FUSED") or len(output_dict) > ops.DECODE_MAX_AGENTS:
             return False
         with_dir = device = None
         for out in output_dict.values():

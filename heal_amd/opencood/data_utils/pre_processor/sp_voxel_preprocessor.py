@@ -10,13 +10,12 @@ touch the GPU -- it runs inside the datasets' forked DataLoader workers, where a
 returns the cloud itself; `collate_batch` turns the clouds into a list of tensors, `train_utils.to_device` moves them
 (0.9 MB per agent instead of the 4-16 MB of padded voxels), and the encoder voxelises every agent of the modality in
 one launch chain on the device (K1, heter_encoders 'points' path) with the caps carried along in the dictionary."""
-import os
 import sys
 
 import numpy as np
 import torch
 
-from heal_amd import ops
+from heal_amd import ops, switches
 
 
 class SpVoxelPreprocessor:
@@ -31,7 +30,7 @@ class SpVoxelPreprocessor:
         grid_size = (np.array(self.lidar_range[3:6]) - np.array(self.lidar_range[0:3])) / np.array(self.voxel_size)
         self.grid_size = np.round(grid_size).astype(np.int64)
         self.defer = bool(self.params['args'].get('defer_to_device', False)) or \
-            os.environ.get("HEAL_DEFER_VOXELIZE", "0") == "1"
+            switches.on("HEAL_DEFER_VOXELIZE")
 
     def preprocess_device(self, points, batch_idx=0):
         """points: [N,4] f32 device tensor -> device tensors (voxels, coords (b,z,y,x), num_points)."""

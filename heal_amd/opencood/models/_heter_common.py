@@ -6,6 +6,7 @@ from collections import OrderedDict
 import torch
 import torch.nn.functional as F
 
+from heal_amd import switches
 from heal_amd.derived import derived
 
 
@@ -137,7 +138,6 @@ def encode_modalities(model, data_dict, present, encode):
     where the fork / join become parallel branches.  Allocator discipline: a stem's tensors are allocated on its side stream
     and only its OUTPUT crosses to the caller's stream after the join; every forward starts with the fork's wait, so a block
     the side stream reuses is never still read by the caller's previous work.  `HEAL_PARALLEL_MODALITIES=0` serialises."""
-    import os
     from heal_amd import ops
     mods = [m for m in model.modality_name_list if m in present]
     dev = next(model.parameters()).device
@@ -145,7 +145,7 @@ def encode_modalities(model, data_dict, present, encode):
     # PendingPool), then ops.bev_pool_pm_multi, then each modality's backbone / aligner (encode_modality_tail).  HEAL_K4_MULTI=0: off.
     # MEASURED NEGATIVE at the scene level (profiles/r06_k4_shared_launch.json): the streams have to meet for the launch, and the extra
     # branches stop the two frames in flight from overlapping (6.15 -> 7.4 ms per step) -- opt-in, and only in an experimental build.
-    two = (dev.type == "cuda" and not torch.is_grad_enabled() and os.environ.get("HEAL_K4_MULTI", "0") == "1" and ops.experimental_build()
+    two = (dev.type == "cuda" and not torch.is_grad_enabled() and switches.on("HEAL_K4_MULTI") and ops.experimental_build()
            and hasattr(model, "encode_modality_tail") and getattr(encode, "__func__", None) is getattr(model.encode_modality, "__func__", 0))
     cams = [m for m in mods if two and hasattr(getattr(model, f"encoder_{m}"), "forward_head")]
     if len(cams) < 2:
@@ -164,7 +164,7 @@ def encode_modalities(model, data_dict, present, encode):
         pooled = iter(ops.bev_pool_pm_multi([p.args for p in deferred]) if len(deferred) >= 2 else [p.finish() for p in deferred])
         return [next(pooled) if hasattr(p, "finish") else p for p in items]
 
-    if (len(mods) < 2 or dev.type != "cuda" or os.environ.get("HEAL_PARALLEL_MODALITIES", "1") != "1"
+    if (len(mods) < 2 or dev.type != "cuda" or not switches.on("HEAL_PARALLEL_MODALITIES")
             or torch.is_grad_enabled()):   # (a gradient path stays on one stream)
         feats = {m: first_half(m) for m in mods}
         if cams:

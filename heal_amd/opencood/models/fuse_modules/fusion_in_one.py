@@ -3,13 +3,12 @@ fusion_in_one.py): MaxFusion (:87-124), AttFusion (:126-151, :14-45), DiscoFusio
 V2XViTFusion (:320-372), CoBEVT (:374-430).  Warping to the ego frame is K5's heal_warp_agent; the per-pixel attention is K6; CoBEVT's
 agent-window attention is heal_agent_window_attention (swap_fusion_modules.py); V2VNet's masked message aggregation is
 heal_v2v_message; DiscoNet's warp + pixel-weight MLP + softmax is heal_disco_fuse."""
-import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from heal_amd import ops
+from heal_amd import ops, switches
 from heal_amd.opencood.models._heter_common import record_len_to_list
 
 
@@ -71,7 +70,7 @@ class AttFusion(_WarpThenFuse):
         if torch.is_grad_enabled() and ego.requires_grad:
             # gradient path (fusion_in_one.py:14-45,126-151): softmax(x x^T / sqrt(C)) x per pixel, the ego row
             if (n <= ops.AGENT_ATTENTION_MAX_AGENTS and ops.agent_attention_train_supported(x, 1)
-                    and os.environ.get("HEAL_ATTN_GRAD", "kernel") != "torch"):
+                    and switches.get("HEAL_ATTN_GRAD") != "torch"):
                 # K6 forward (ego row) + heal_agent_attention_backward; x enters as q, k and v: autograd sums the three gradients
                 return ops.AgentAttention.apply(x, x, x, 1, 1.0 / self.sqrt_dim, 1, False)[:, 0, :].t().reshape(C, H, W)
             attn = torch.softmax(torch.bmm(x, x.transpose(1, 2)) / self.sqrt_dim, dim=-1)
@@ -245,7 +244,7 @@ class DiscoFusion(nn.Module):
         return (x.is_cuda and x.dtype == torch.float32 and not self.training
                 and not (torch.is_grad_enabled() and x.requires_grad) and max(lens) <= ops.DISCO_MAX_AGENTS
                 and C % 4 == 0 and C == self.pixel_weight_layer.conv1_1.in_channels // 2 and ego_ok
-                and os.environ.get("HEAL_DISCO_FUSED", "1") != "0")
+                and switches.on("HEAL_DISCO_FUSED"))
 
     def _weights(self):
         """(W1n in A-fragment order, W1e [128, C, 1, 1], b1, W2, b2, W3, b3, w4, b4) with the BatchNorms folded, from the parameters
@@ -381,7 +380,7 @@ class V2VNetFusion(nn.Module):
         ks_ok = all(tuple(k) == (3, 3) for k in (c.conv_gates.kernel_size for c in self.conv_gru.cell_list))
         mlp_ok = (H * W) % 4 == 0 or ops.linear_supported(H * W, C, C)
         return (x.is_cuda and x.dtype == torch.float32 and not (torch.is_grad_enabled() and x.requires_grad) and ks_ok and mlp_ok
-                and max(lens) <= ops.V2V_MAX_AGENTS and os.environ.get("HEAL_V2VNET_FUSED", "1") != "0")
+                and max(lens) <= ops.V2V_MAX_AGENTS and switches.on("HEAL_V2VNET_FUSED"))
 
     def _weights(self):
         """(W_n, stacked x_i weight, stacked bias, agg weight | None, [(layer weight, layer bias)] for GRU layers >= 1), from the
@@ -493,7 +492,7 @@ def ms_fused_ok(fusion_net, feature_list, lens):
     return (all(f.is_cuda and f.dtype == torch.float32 for f in feature_list)
             and not (torch.is_grad_enabled() and any(f.requires_grad for f in feature_list))
             and max(lens) <= MS_MAX_AGENTS and 1 <= len(feature_list) <= ops.WARP_ATT_MAX_LEVELS
-            and os.environ.get("HEAL_MSATT_FUSED", "1") != "0")
+            and switches.on("HEAL_MSATT_FUSED"))
 
 
 def fuse_level_torch(module, x, lens, aff):

@@ -3,7 +3,7 @@ fused warp + occupancy-softmax kernel K5 (heal_warp_fuse)."""
 import torch
 import torch.nn as nn
 
-from heal_amd import derived, ops
+from heal_amd import derived, ops, switches
 from heal_amd.opencood.models.sub_modules.bev_blocks import (Bottleneck, ResNetBEVBackbone, ResNetModified)
 
 
@@ -67,9 +67,8 @@ def weighted_fuse(x, occ, record_len, affine_matrix, grid_f64=True, crops=None):
 
     x [sum(n),C,H,W]; occ [sum(n),1,H,W] occupancy LOGITS; record_len: list of ints;
     affine_matrix: host numpy [B,L,L,2,3]; crops: per-agent (h0,h1,w0,w1) or None."""
-    import os
     grad = torch.is_grad_enabled() and (x.requires_grad or occ.requires_grad)
-    if grad and not (x.is_cuda and os.environ.get("HEAL_K5_BACKWARD", "1") == "1"):
+    if grad and not (x.is_cuda and switches.on("HEAL_K5_BACKWARD")):
         return weighted_fuse_autograd(x, occ, record_len, affine_matrix, crops)   # any device: torch operators
     out = []
     start = 0
@@ -215,9 +214,8 @@ class PyramidFusion(ResNetBEVBackbone):
     def _camcrop_args(self, spatial_features, agent_modality_list, cam_boxes):
         """(cam_slice, box) when the camera-crop walk applies: inference on a HIP device, ResNeXt stages, the camera agents form one
         contiguous range at an end of the scene and share one valid box."""
-        import os
         if (not cam_boxes or agent_modality_list is None or torch.is_grad_enabled() or not spatial_features.is_cuda
-                or os.environ.get("HEAL_PYRAMID_CAMCROP", "1") != "1"):
+                or not switches.on("HEAL_PYRAMID_CAMCROP")):
             return None
         cams = [k for k, m in enumerate(agent_modality_list) if m in cam_boxes]
         n = len(agent_modality_list)
@@ -265,9 +263,8 @@ class PyramidFusion(ResNetBEVBackbone):
         conditions of the camera-crop walk (_camcrop_args), a crop window for every camera agent, a cropped stage 0, the other agents
         of ONE modality (their encoder's output is then the LiDAR tensor in scene order), cached responses ready under capture.
         like: a [k, C, H, W] tensor of the full map size on the model's device (k may be 0)."""
-        import os
         if (len(record_len) != 1 or not 1 <= self.num_levels <= ops.WARP_MAX_LEVELS or int(record_len[0]) > ops.WARP_MAX_AGENTS
-                or self.training or os.environ.get("HEAL_K5_LEVELS", "1") != "1" or os.environ.get("HEAL_PYRAMID_LEAN", "1") != "1"):
+                or self.training or not switches.on("HEAL_K5_LEVELS") or not switches.on("HEAL_PYRAMID_LEAN")):
             return None
         cc = self._camcrop_args(like, agent_modality_list, cam_boxes)
         if cc is None:
@@ -384,9 +381,8 @@ class PyramidFusion(ResNetBEVBackbone):
         feature_list = self.multiscale(spatial_features, agent_modality_list, cam_boxes if len(record_len) == 1 else None)
         use_crop = bool(cam_crop_info) and not self.training
         fused_feature_list, occ_map_list = [], []
-        import os
         if (len(record_len) == 1 and not torch.is_grad_enabled() and feature_list[0].is_cuda
-                and 1 <= self.num_levels <= ops.WARP_MAX_LEVELS and int(record_len[0]) <= ops.WARP_MAX_AGENTS and os.environ.get("HEAL_K5_LEVELS", "1") == "1"):
+                and 1 <= self.num_levels <= ops.WARP_MAX_LEVELS and int(record_len[0]) <= ops.WARP_MAX_AGENTS and switches.on("HEAL_K5_LEVELS")):
             # inference, one scene: the three levels are independent once the stages ran -> ONE K5 launch for all of them
             # (heal_warp_fuse_levels; HEAL_K5_LEVELS=0 keeps one heal_warp_fuse launch per level for A/B)
             n = int(record_len[0])

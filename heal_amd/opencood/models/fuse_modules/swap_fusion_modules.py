@@ -10,12 +10,11 @@ included).  CoBEVT itself (Regroup, warp, blocks, mlp_head) is in fusion_in_one.
     position bias, keys of padded agents skipped) -> heal_linear (to_out + x); each feed-forward is two heal_linear launches
     (v2xvit_basic.FeedForward.fused_residual); mlp_head is heal_agent_mean -> heal_ln_stats -> heal_linear.
 """
-import os
 
 import torch
 import torch.nn as nn
 
-from heal_amd import ops
+from heal_amd import ops, switches
 from heal_amd.derived import derived
 from heal_amd.opencood.models.sub_modules.v2xvit_basic import FeedForward, _fold_ln
 
@@ -27,7 +26,7 @@ def _grad_path(x, module):
 def fused_ok(x, module, L, H, W, C):
     """Inference on the device of x with a scene of L agents, H x W maps and C channels, shapes the HIP kernels take.
     HEAL_COBEVT_FUSED=0 keeps the torch composition on the device (A/B)."""
-    if not x.is_cuda or x.dtype != torch.float32 or _grad_path(x, module) or os.environ.get("HEAL_COBEVT_FUSED", "1") == "0":
+    if not x.is_cuda or x.dtype != torch.float32 or _grad_path(x, module) or not switches.on("HEAL_COBEVT_FUSED"):
         return False
     return all(ops.agent_window_attention_supported(L, b.window_size, b.window_attention.fn.dim_head, H, W)
                and b.window_attention.fn.heads * b.window_attention.fn.dim_head == C for b in module.layers) \

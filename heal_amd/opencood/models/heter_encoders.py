@@ -2,13 +2,12 @@
 PointPillar (:22-50), SECOND (:52-81), LiftSplatShoot (:83-241), LiftSplatShootVoxel (:244-301).
 Classes are discovered by name exactly as the reference does (heter_pyramid_collab.py:41-48).
 """
-import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from heal_amd import ops
+from heal_amd import ops, switches
 from heal_amd.derived import derived
 from heal_amd.opencood.models.sub_modules.bev_blocks import grad_path
 from heal_amd.opencood.models.sub_modules.pillar_vfe import PillarVFE
@@ -42,7 +41,7 @@ class PointPillar(nn.Module):
 
     def _scatter_op(self, v, c, n, weight, scale, shift, n_agents, n_voxels_dev=None):
         ny, nx = self.scatter.ny, self.scatter.nx
-        if self.emit_pooled and os.environ.get("HEAL_K2_POOLED", "1") == "1" and int(weight.shape[0]) == 64:
+        if self.emit_pooled and switches.on("HEAL_K2_POOLED") and int(weight.shape[0]) == 64:
             return ops.pfn_pillars(v, c, n, weight, scale, shift, self.voxel_size, self.lidar_range, n_agents, ny, nx,
                                    n_voxels_dev=n_voxels_dev)
         return ops.pfn_scatter(v, c, n, weight, scale, shift, self.voxel_size, self.lidar_range, n_agents, ny, nx,
@@ -84,12 +83,11 @@ class PointPillar(nn.Module):
             n_agents = int(inp["n_agents"]) if "n_agents" in inp else int(coords[:, 0].max().item()) + 1
         if grad:   # gradient path: the scatter as a torch index operation; the PFN on its forward / backward kernels on the
             # device (HEAL_K2_BACKWARD=0, the CPU and max_points > 32: Linear / BatchNorm1d / max as torch operators)
-            import os
             pfn0 = self.pillar_vfe.pfn_layers[0]
             if (voxels.is_cuda and ops.pfn_train_supported(voxels) and getattr(pfn0, "use_norm", True)
                     and len(self.pillar_vfe.pfn_layers) == 1 and pfn0.linear.bias is None
                     and pfn0.linear.out_features == 64 and pfn0.linear.in_features == 10   # the kernels hard-code Linear(10 -> 64)
-                    and os.environ.get("HEAL_K2_BACKWARD", "1") == "1"):
+                    and switches.on("HEAL_K2_BACKWARD")):
                 feats = self.pillar_vfe.pillar_features_kernels(voxels, coords, num)
             else:
                 feats = self.pillar_vfe.pillar_features(voxels, coords, num)
@@ -254,7 +252,7 @@ class LiftSplatShoot(nn.Module):
                             self.bx_host, self.nx_host)
 
     def pool_pixel_major(self, head, cam_mats, B, N, fH, fW, defer=False):
-        pooled = self.emit_pooled and self.nx_host[2] == 1 and os.environ.get("HEAL_K4_POOLED", "1") == "1"
+        pooled = self.emit_pooled and self.nx_host[2] == 1 and switches.on("HEAL_K4_POOLED")
         pend = PendingPool(head=head, C=self.camC, D=self.D, fH=fH, fW=fW, frustum=self.frustum(head.device), cam_mats=cam_mats,
                            n_agents=B, n_cams=N, dx=self.dx_host, bx=self.bx_host, nx=self.nx_host, pooled=pooled)
         return pend if defer else pend.finish()
@@ -295,7 +293,7 @@ class LiftSplatShoot(nn.Module):
             items, depth_logit, x_img = self.camencode(x.view(B * N, C, imH, imW), pixel_major=False)
             if self.depth_supervision:
                 self.depth_items = items
-            if x.is_cuda and self.D <= 64 and self.camC <= 256 and os.environ.get("HEAL_K4_BACKWARD", "1") == "1":
+            if x.is_cuda and self.D <= 64 and self.camC <= 256 and switches.on("HEAL_K4_BACKWARD"):
                 with torch.no_grad():
                     cam = self.camera_matrices(inp["rots"], inp["trans"], inp["intrins"], inp["post_rots"], inp["post_trans"])
                 out = _LiftPool.apply(depth_logit, x_img, self.frustum(x.device), cam, B, N, self.dx_host, self.bx_host,

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from heal_amd import switches
 from heal_amd.derived import derived
 
 
@@ -36,9 +37,14 @@ def fold_bn(conv, bn, transposed=False):
     return derived("fold_bn", (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var), build, (transposed,))
 
 
-import os
-_CONV1X1 = os.environ.get("HEAL_CONV1X1", "1") == "1"  # hand-written pointwise conv with fused epilogue (K7c)
-_CONV3X3 = os.environ.get("HEAL_CONV3X3", "1") == "1"  # hand-written dense 3x3 conv on fp32 MFMA (0: MIOpen + heal_bias_act, A/B)
+def conv1x1_enabled():
+    """HEAL_CONV1X1=0: pointwise convolutions on the library instead of heal_conv1x1 with its fused epilogue (K7c; A/B)."""
+    return switches.on("HEAL_CONV1X1")
+
+
+def conv3x3_enabled():
+    """HEAL_CONV3X3=0: dense 3x3 convolutions on MIOpen + heal_bias_act instead of heal_conv3x3 on the fp32 MFMA (A/B)."""
+    return switches.on("HEAL_CONV3X3")
 
 
 def conv_bias_act(x, w, b, stride, padding, dilation=1, groups=1, relu=True, residual=None, out=None):
@@ -59,13 +65,13 @@ def conv_bias_act(x, w, b, stride, padding, dilation=1, groups=1, relu=True, res
     if (groups > 1 and w.shape[2:] == (3, 3) and pd == 1 and dl == 1 and st in (1, 2) and residual is None
             and w.shape[1] in (4, 8, 16) and w.shape[0] == x.shape[1]):
         return ops.grouped_conv3x3(x, w, b, groups, st, relu)
-    if _CONV1X1 and groups == 1 and w.shape[2:] == (1, 1) and st in (1, 2) and pd == 0:
+    if groups == 1 and w.shape[2:] == (1, 1) and st in (1, 2) and pd == 0 and conv1x1_enabled():
         Ho, Wo = (int(x.shape[2]) - 1) // st + 1, (int(x.shape[3]) - 1) // st + 1
         if ops.conv1x1_supported(int(w.shape[1]), int(w.shape[0]), Ho * Wo, st, Wo):
             return ops.conv1x1(x, w, b, residual, 1 if relu else 0, stride=st, out=out)
-    if (_CONV3X3 and x.is_cuda and groups == 1 and tuple(w.shape[2:]) == (3, 3) and pd == 1 and dl == 1 and st in (1, 2)
+    if (x.is_cuda and groups == 1 and tuple(w.shape[2:]) == (3, 3) and pd == 1 and dl == 1 and st in (1, 2)
             and (padding if isinstance(padding, int) else padding[1]) == 1
-            and (stride if isinstance(stride, int) else stride[1]) == st):
+            and (stride if isinstance(stride, int) else stride[1]) == st and conv3x3_enabled()):
         return ops.conv3x3(x, w, b, residual, relu, st)
     if (x.is_cuda and groups == 1 and tuple(w.shape[2:]) == (7, 7) and st == 2 and pd == 3 and dl == 1 and residual is None
             and ops.conv7x7_s2_supported(int(w.shape[1]), int(w.shape[0]), int(x.shape[3]))):
@@ -255,8 +261,7 @@ class Bottleneck(nn.Module):
     def _fusable(self, x):
         # The fused kernel (heal_resnext_bottleneck) is correct but, at one workgroup per CU, still slower
         # than the un-fused sequence ("K7b"): opt-in until it wins.
-        import os
-        if os.environ.get("HEAL_FUSED_BOTTLENECK", "0") != "1":
+        if not switches.on("HEAL_FUSED_BOTTLENECK"):
             return False
         from heal_amd import ops
         if not ops.experimental_build():      # the kernel ships only in a HEAL_BUILD_EXPERIMENTAL=1 library
@@ -322,7 +327,7 @@ class ResNetModified(nn.Module):
         Cache), although one agent's whole block (16.8 + 33.5 + 33.5 + 16.8 MB) fits the cache.  Walking the stage agent chunk by
         agent chunk -- every block of the stage on chunk 0, then chunk 1, ... -- keeps a chunk's intermediates on the die between
         the producing and the consuming launch.  HEAL_STAGE_CHUNK_MB: the working-set budget per chunk (0: off)."""
-        mb = float(os.environ.get("HEAL_STAGE_CHUNK_MB", "0"))
+        mb = switches.number("HEAL_STAGE_CHUNK_MB")
         if mb <= 0 or not x.is_cuda or torch.is_grad_enabled() or not all(isinstance(b, Bottleneck) for b in layer):
             return 0
         n = int(x.shape[0])
@@ -389,7 +394,7 @@ class _Deblock(nn.Sequential):
         if isinstance(conv, nn.ConvTranspose2d):
             w, b = fold_bn(conv, bn, transposed=True)
             k = conv.kernel_size[0]
-            if (_CONV1X1 and x.is_cuda and conv.kernel_size == conv.stride and conv.kernel_size[0] == conv.kernel_size[1]
+            if (conv1x1_enabled() and x.is_cuda and conv.kernel_size == conv.stride and conv.kernel_size[0] == conv.kernel_size[1]
                     and conv.padding == (0, 0) and conv.output_padding == (0, 0) and conv.groups == 1
                     and ops.conv1x1_supported(int(w.shape[0]), int(w.shape[1]) * k * k, int(x.shape[2] * x.shape[3]))):
                 # kernel == stride: the transposed convolution is a pointwise convolution to Cout*k*k channels followed

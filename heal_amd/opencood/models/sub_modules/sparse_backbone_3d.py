@@ -14,11 +14,11 @@ cells per agent) fits.  Off the device (and with HEAL_SP_GRAD=dense): spconv's a
 grid, masked by the active-site rules -- plain torch, differentiable, only for small grids; it is what pins the sparse path
 (tests/test_gpu_train.py) and the CPU oracle comparison.
 """
-import os
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from heal_amd import switches
 from heal_amd.derived import derived
 
 
@@ -70,7 +70,7 @@ class _SparseConvFn(torch.autograd.Function):
             gf = ops.sp_conv_raw(g, nbr_t, weight.detach().transpose(1, 2).contiguous())
         if ctx.needs_input_grad[1]:   # d W[tap] = X_pairs^T G_pairs
             x = feats.detach().contiguous()
-            if ops.sp_wgrad_supported(int(weight.shape[1]), int(weight.shape[2])) and os.environ.get("HEAL_SP_WGRAD", "1") == "1":
+            if ops.sp_wgrad_supported(int(weight.shape[1]), int(weight.shape[2])) and switches.on("HEAL_SP_WGRAD"):
                 gw = ops.sp_wgrad(x, g, nbr)          # heal_sp_wgrad: pair-compacted gather + MFMA over the pair index
             else:   # gather the paired rows, one matrix product per tap
                 gw = torch.zeros_like(weight)
@@ -199,7 +199,7 @@ class VoxelBackBone8x(nn.Module):
     def forward_autograd(self, batch_dict):
         """Gradient path: sparse on the device (forward_autograd_sparse), dense masked evaluation otherwise (module docstring)."""
         feats = batch_dict["voxel_features"]
-        if feats.is_cuda and os.environ.get("HEAL_SP_GRAD", "sparse") != "dense":
+        if feats.is_cuda and switches.get("HEAL_SP_GRAD") != "dense":
             return self.forward_autograd_sparse(batch_dict)
         coords = batch_dict["voxel_coords"].long()
         B = int(batch_dict["batch_size"])

@@ -23,9 +23,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-import os
-
-from heal_amd import ops
+from heal_amd import ops, switches
 from heal_amd.derived import derived
 
 
@@ -35,7 +33,7 @@ def _grad_path(x, module):
 
 def _fused_ok(x, module):
     """Inference on the device with shapes heal_linear takes (channels % 128 == 0, H W % 128 == 0): the fused path."""
-    if not x.is_cuda or _grad_path(x, module) or os.environ.get("HEAL_V2XVIT_FUSED", "1") == "0":
+    if not x.is_cuda or _grad_path(x, module) or not switches.on("HEAL_V2XVIT_FUSED"):
         return False
     L, H, W, C = x.shape
     return C % 128 == 0 and (H * W) % 128 == 0 and x.dtype == torch.float32
@@ -142,7 +140,7 @@ class HGTCavAttention(nn.Module):
             qa = torch.einsum("lphd,hde->lphe", q, self.relation_att[0])
             vm = torch.einsum("lphd,hde->lphe", v, self.relation_msg[0])
             if (L <= ops.AGENT_ATTENTION_MAX_AGENTS and m * d == 256 and ops.agent_attention_train_supported(flat, m)
-                    and os.environ.get("HEAL_ATTN_GRAD", "kernel") != "torch"):
+                    and switches.get("HEAL_ATTN_GRAD") != "torch"):
                 # on the device: K6 forward + heal_agent_attention_backward (no [HW, m, L, L] score / [L, HW, m, d] message tensors
                 # kept for the backward: q, k, v are saved and the probabilities recomputed per pixel)
                 out = ops.AgentAttention.apply(qa.reshape(L, H * W, m * d), k.reshape(L, H * W, m * d),
@@ -235,7 +233,7 @@ class BaseWindowAttention(nn.Module):
             # the [windows, T, T] score tensor (heal_window_attention): 16x (ws 4), 4x (ws 8) and 1.7x (ws 16) faster
             # than the library sequence at 8 agents x 128 x 128
             return self.to_out[0](ops.window_attention(qkv, bias, m, d, ws, self.scale))
-        if (x.is_cuda and _grad_path(x, self) and os.environ.get("HEAL_WATTN_GRAD", "torch") == "kernel"
+        if (x.is_cuda and _grad_path(x, self) and switches.get("HEAL_WATTN_GRAD") == "kernel"
                 and ops.window_attention_supported(ws, d, H, W) and qkv.dtype == torch.float32):
             # opt-in (unmeasured): K6b forward + heal_window_attention_backward instead of the library composition below
             return self.to_out(ops.WindowAttention.apply(qkv, bias, m, d, ws, self.scale))
@@ -428,7 +426,7 @@ class V2XTEncoder(nn.Module):
         if self.use_RTE:
             x = self.rte(x)
         for li, (attn, ff) in enumerate(self.layers):
-            if li == len(self.layers) - 1 and x.shape[0] > 1 and _fused_ok(x, self) and os.environ.get("HEAL_V2XVIT_EGO_TAIL", "1") == "1":
+            if li == len(self.layers) - 1 and x.shape[0] > 1 and _fused_ok(x, self) and switches.on("HEAL_V2XVIT_EGO_TAIL"):
                 ego = self._ego_tail(attn, ff, x)
                 if ego is not None:
                     return ego

@@ -17,7 +17,7 @@ import os
 import numpy as np
 import torch
 
-from heal_amd import ops
+from heal_amd import ops, switches
 from heal_amd.opencood.hypes_yaml import yaml_utils
 
 DEFAULT_THRESHOLDS = (0.3, 0.5, 0.7)
@@ -67,7 +67,7 @@ def _greedy_match(iou, thresholds, score=None):
 
 
 def fused_enabled():
-    return os.environ.get("HEAL_EVAL_FUSED", "1") != "0"
+    return switches.on("HEAL_EVAL_FUSED")
 
 
 def _on_device(t, dtype=torch.float32):

@@ -5,12 +5,11 @@ libheal_amd.so.  Every function requires CUDA(HIP) tensors and raises otherwise 
 path in the product.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
 
-from . import _capi, derived
+from . import _capi, derived, switches
 from .derived import derived as _derived
 
 _WS = {}
@@ -449,7 +448,7 @@ class PillarBEV:
         return (self.channels == 64 and cout_main == 64 and cout_down == 64 and ((self.nx_ - 1) // 2 + 1) % 4 == 0)
 
     # weight layout of stem_block: "lanes" (pillar_stem_fragments, the pixel-compacted kernel) | "tiles" (stem_fragments, v1: A/B)
-    weight_layout = "tiles" if os.environ.get("HEAL_PILLAR_STEM", "2") == "1" else "lanes"
+    weight_layout = "tiles" if switches.get("HEAL_PILLAR_STEM") == "1" else "lanes"
 
     def fragments(self, w_main, w_down):
         return pillar_stem_fragments(w_main, w_down) if self.weight_layout == "lanes" else stem_fragments(w_main, w_down)
@@ -1252,18 +1251,16 @@ V2V_MAX_AGENTS = _limit("HEAL_V2V_MAX_AGENTS")
 def v2v_message_tile_h(n_ego, cout, H, W, mode):
     """Output rows per heal_v2v_message block: 8 for the mean (2 waves per SIMD at 138 VGPRs), 4 for the max (its fold keeps E
     and a running maximum: 8 rows would leave one wave per SIMD); HEAL_V2V_TH overrides (4 | 8 | 16)."""
-    e = os.environ.get("HEAL_V2V_TH", "")
-    if e in ("4", "8", "16"):
-        return int(e)
-    return 4 if mode == 1 else 8
+    return switches.number("HEAL_V2V_TH") or (4 if mode == 1 else 8)
 
 
 def v2v_message_nsplit(n_ego, n_agents, cout, H, W, tile_h):
     """Agent-loop splits: 1 unless one launch has fewer blocks than two per CU (256 CUs): then enough splits for ~512 blocks, at
     most one per agent, none empty.  HEAL_V2V_SPLIT forces a value (clamped to [1, n_agents])."""
     blocks = n_ego * -(-cout // 64) * -(-W // 16) * -(-H // tile_h)
-    env = os.environ.get("HEAL_V2V_SPLIT")
-    want = int(env) if env is not None else (-(-512 // blocks) if blocks < 512 else 1)
+    want = switches.number("HEAL_V2V_SPLIT")
+    if want is None:
+        want = -(-512 // blocks) if blocks < 512 else 1
     want = max(1, min(want, n_agents))
     return -(-n_agents // -(-n_agents // want))       # no empty split
 
@@ -1428,7 +1425,7 @@ def bev_pool_pm_supported(D, fH, C):
     mtot = (D + 15) // 16 * 16
     fh4 = (fH + 3) // 4 * 4
     lds = (fh4 * (C + 16) + 2 * mtot * 66) * 4   # LssLds, bev_pool.hip
-    return (os.environ.get("HEAL_LSS_PATH", "") != "sorted" and fH <= 64 and D <= 64 and D % 4 == 0 and C % 16 == 0
+    return (switches.get("HEAL_LSS_PATH") != "sorted" and fH <= 64 and D <= 64 and D % 4 == 0 and C % 16 == 0
             and 16 <= C <= 256 and lds <= 150 * 1024)
 
 
@@ -1689,9 +1686,19 @@ class PairTiles:
         return self.to_neighbors()[key]
 
 
+def sp_rank_enabled():
+    """HEAL_SP_RULEBOOK=hash: sort + hash-grid rulebooks instead of the rank structures, for the voxel set and every layer."""
+    return switches.get("HEAL_SP_RULEBOOK") == "rank"
+
+
+def sp_root_rank_enabled():
+    """HEAL_SP_ROOT=sort: radix sort + hash grid for the voxel set alone; the layers behind it keep their rank structures."""
+    return sp_rank_enabled() and switches.get("HEAL_SP_ROOT") == "rank"
+
+
 def sp_tiles_enabled():
     """HEAL_SP_TILES=0: every sparse layer through the [n_out, K] neighbour table (A/B, and what training uses)."""
-    return os.environ.get("HEAL_SP_TILES", "1") != "0"
+    return switches.on("HEAL_SP_TILES")
 
 
 class SparseTensor:
@@ -1735,7 +1742,7 @@ class SparseTensor:
         rank = None
         C = int(features.shape[1])
         feats = torch.zeros((n, C), dtype=torch.float32, device=dev) if n_dev is not None else torch.empty((n, C), dtype=torch.float32, device=dev)
-        if os.environ.get("HEAL_SP_RULEBOOK", "rank") == "rank" and os.environ.get("HEAL_SP_ROOT", "rank") == "rank":
+        if sp_root_rank_enabled():
             # rank(linear coordinate) IS the sorted position: one scatter (sites, permutation and feature rows) instead of a radix
             # sort + gather, and the structure answers the neighbour queries of the layers that read the voxel set (no hash grid)
             nbytes = _capi.query("heal_sp_root_rank_bytes", _i3(spatial_shape), int(batch_size))
@@ -1794,7 +1801,7 @@ class SparseTensor:
         # sites per slot: 64.  128 fill the 16-pair tiles of a strided layer better (2.5 live taps of 27 per site on conv2's
         # SparseConv3d: -5 us on that convolution) but the rulebook kernel then has half the waves for the same lookups (+22 us):
         # HEAL_SP_SLOT_SITES=128 is the A/B switch of a HEAL_BUILD_EXPERIMENTAL=1 library (profiles/r06_k3_thin.json)
-        sites = int(os.environ.get("HEAL_SP_SLOT_SITES", 0)) or 64
+        sites = switches.number("HEAL_SP_SLOT_SITES")
         buf = torch.empty((_capi.query("heal_sp_pair_tiles_words", n_out, sites),), dtype=torch.int32, device=self.indices.device)
         with _Timed("sp_rulebook"):
             _capi.call("heal_sp_neighbor_tiles", _ptr(out_indices), n_out, _i3(ksize), _i3(stride), _i3(padding),
@@ -1826,7 +1833,7 @@ class SparseTensor:
         out_idx = torch.empty((out_cap, 4), dtype=torch.int32, device=dev)
         n_out = torch.zeros((1,), dtype=torch.int32, device=dev)
         rank = None
-        if os.environ.get("HEAL_SP_RULEBOOK", "rank") != "hash":
+        if sp_rank_enabled():
             nbytes = _capi.query("heal_sp_rank_bytes", _i3(out_shape), self.batch_size)
             rank = torch.empty((nbytes,), dtype=torch.uint8, device=dev)   # lives as long as the site set it describes
             with _Timed("sp_rulebook"):
@@ -2035,7 +2042,7 @@ def kd_kl_supported(student, teacher):
                 and student.dtype == torch.float32 and teacher.dtype == torch.float32 and student.dim() == 4
                 and student.shape == teacher.shape and student.numel() > 0 and student.device == teacher.device
                 and not (teacher.requires_grad and torch.is_grad_enabled())
-                and os.environ.get("HEAL_KD_FUSED", "1") != "0")
+                and switches.on("HEAL_KD_FUSED"))
 
 
 def kd_kl_loss(student, teacher, need_grad=True, grad_out=None):
@@ -2096,7 +2103,7 @@ LOSS_MAX_ANCHORS, OCC_LOSS_MAX_LEVELS = _limit("HEAL_LOSS_MAX_ANCHORS"), _limit(
 
 
 def loss_fused_enabled():
-    return os.environ.get("HEAL_LOSS_FUSED", "1") != "0"
+    return switches.on("HEAL_LOSS_FUSED")
 
 
 def _loss_map_ok(t):
@@ -2521,7 +2528,7 @@ def grouped_conv3x3(x, weight, bias, groups, stride=1, relu=True):
     Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
     y = torch.empty((n, C, Ho, Wo), dtype=torch.float32, device=x.device)
     cg = C // groups
-    mode = os.environ.get("HEAL_GCONV_MFMA", "1")
+    mode = switches.get("HEAL_GCONV_MFMA")
     if C % 16 == 0 and W % 4 == 0 and Wo % 4 == 0 and mode in ("1", "s") and cg in (4, 8, 16):
         frag = grouped_small_fragments(weight, cg)
         with _Timed(f"grouped_conv3x3_c{C}" + ("_s2" if stride == 2 else ""), 2.0 * 9 * n * C * cg * Ho * Wo,
@@ -2609,8 +2616,9 @@ def conv1x1_ksplit(n, cin, cout, hw):
     HEAL_C1_KSPLIT forces a value (0 / 1: off)."""
     chunks = (cin + 31) // 32
     blocks = -(-cout // 64) * -(-hw // 64) * n
-    env = os.environ.get("HEAL_C1_KSPLIT")
-    want = int(env) if env is not None else (min(chunks // 2, max(2, 256 // blocks)) if blocks < 128 and chunks >= 8 else 1)
+    want = switches.number("HEAL_C1_KSPLIT")
+    if want is None:
+        want = min(chunks // 2, max(2, 256 // blocks)) if blocks < 128 and chunks >= 8 else 1
     if want < 2 or chunks < 2 or hw % 4:
         return 1
     want = min(want, chunks, 65535 // n)
@@ -2655,7 +2663,7 @@ def conv1x1_tiled_ok(n, cin, cout, hw):
     OPT-IN (HEAL_C1_TILED=1, =force for every shape it can take): measured at the scenes' shapes (scripts/c1t_bench.py,
     profiles/r04_c1t_bench.json) it is at parity with the 64 x 64 kernel -- 0.70-1.07x, ahead only on 256 -> 2048 and single-image
     256 -> 128; neither tile shape of either kernel moves the 85-105 TFLOP/s these 5-GFLOP launches reach in isolation."""
-    mode = os.environ.get("HEAL_C1_TILED", "0")
+    mode = switches.get("HEAL_C1_TILED")
     if mode == "0" or not experimental_build() or cin % 32 or cout % 64 or hw % 4 or hw < 128:
         return False
     bm = 128 if cout % 128 == 0 else 64
@@ -2668,8 +2676,7 @@ def conv1x1_tiled_ok(n, cin, cout, hw):
 def arith_products():
     """HEAL_ARITH: "" / "f32" (default: exact-fp32 MFMA everywhere) | "bf16x6" | "bf16x9" -- the OPT-IN split-bf16 evaluation of the
     pointwise convolutions (heal_conv1x1_split; fp32 in / out / accumulate, 6 or 9 bf16 partial products per fp32 product)."""
-    a = os.environ.get("HEAL_ARITH", "")
-    return {"bf16x6": 6, "bf16x9": 9}.get(a, 0)
+    return {"bf16x6": 6, "bf16x9": 9}.get(switches.get("HEAL_ARITH"), 0)
 
 
 def conv1x1_split_fragments(w):
@@ -2838,9 +2845,9 @@ def conv3x3_winograd_waves(n=1, cout=64, H=256, W=256):
     """Waves per Winograd block: 8 (16x16-pixel tiles, one block per CU: best operand reuse) when that still gives every CU two
     or more blocks, else 4 (8x16-pixel tiles, two independent blocks per CU whose transform / MFMA phases overlap; measured
     crossover, scripts/conv3x3_bench.py); HEAL_WG_WAVES overrides."""
-    e = os.environ.get("HEAL_WG_WAVES", "")
-    if e in ("4", "8"):
-        return int(e)
+    waves = switches.number("HEAL_WG_WAVES")
+    if waves is not None:
+        return waves
     blocks8 = n * ((cout + 63) // 64) * ((H + 15) // 16) * ((W + 15) // 16)
     return 8 if blocks8 >= 512 else 4
 
@@ -2849,8 +2856,7 @@ def conv3x3_winograd_kc(cin, waves, H=1, W=1):
     """Input channels per chunk of the Winograd K loop: 16 where the kernel has it (an experimental build, 8-wave blocks,
     cin % 16 == 0, a map whose 16-channel chunk stays below 2^31 bytes) and HEAL_WG_KC asks for it, else 8.  Measured in round 5
     (profiles/r05_wino_kc16.txt): 4-13 % slower, hence experimental."""
-    want = os.environ.get("HEAL_WG_KC", _WG_KC_DEFAULT)
-    ok16 = (want == "16" and waves == 8 and cin % 16 == 0 and 16 * H * W * 4 < 2 ** 31 and experimental_build())
+    ok16 = (switches.number("HEAL_WG_KC") == 16 and waves == 8 and cin % 16 == 0 and 16 * H * W * 4 < 2 ** 31 and experimental_build())
     return 16 if ok16 else 8
 
 
@@ -2858,9 +2864,6 @@ def experimental_build():
     """True if libheal_amd.so was built with HEAL_BUILD_EXPERIMENTAL=1 (the measured-negative kernels of
     include/heal_amd_experimental.h are present)."""
     return hasattr(_capi.lib(), "heal_gconv_conv3")
-
-
-_WG_KC_DEFAULT = "8"
 
 
 def conv3x3_winograd_fragments(w, waves=8, kc=8):
@@ -2900,14 +2903,14 @@ def conv3x3_winograd4_ok(n, cout, H, W):
     """F(4x4,3x3) (heal_conv3x3_winograd4) is OPT-IN: HEAL_C3_ALGO=winograd4.  Measured 0.80 - 1.03x of F(2x2,3x3) at the scenes'
     shapes (profiles/r03_wino_f44_vs_f22.json): a quarter of the multiplications instead of 4/9, but twice the transform work per
     output at 32 output channels per block."""
-    return os.environ.get("HEAL_C3_ALGO", "") == "winograd4" and experimental_build()
+    return switches.get("HEAL_C3_ALGO") == "winograd4" and experimental_build()
 
 
 def conv3x3_algo(stride, n=1, cout=64, H=256, W=256):
     """'winograd' | 'direct' for a shape; HEAL_C3_ALGO overrides for A/B.  Winograd F(2x2,3x3) is the stride-1 formulation
     and runs one 8-wave block per CU on a 16x16-pixel x 64-channel tile: below ~one block per CU the implicit GEMM with its
     smaller tiles fills the chip better (measured crossover ~100 blocks, scripts/conv3x3_bench.py)."""
-    a = os.environ.get("HEAL_C3_ALGO", "")
+    a = switches.get("HEAL_C3_ALGO")
     if stride != 1 or a == "direct":
         return "direct"
     if a in ("winograd", "winograd4"):
@@ -2917,7 +2920,7 @@ def conv3x3_algo(stride, n=1, cout=64, H=256, W=256):
 
 
 def conv_gemm_supported(cin, cout, Wo):
-    return cout % 128 == 0 and cin % 32 == 0 and Wo % 4 == 0 and os.environ.get("HEAL_CONV_GEMM", "1") == "1"
+    return cout % 128 == 0 and cin % 32 == 0 and Wo % 4 == 0 and switches.on("HEAL_CONV_GEMM")
 
 
 def conv_gemm(x, w, bias=None, residual=None, relu=False, stride=1):
@@ -2942,7 +2945,7 @@ def conv_gemm(x, w, bias=None, residual=None, relu=False, stride=1):
 
 
 def conv7x7_s2_supported(cin, cout, W):
-    return cin % 32 == 0 and cout <= 128 and ((W - 1) // 2 + 1) % 4 == 0 and os.environ.get("HEAL_CONV_GEMM", "1") == "1"
+    return cin % 32 == 0 and cout <= 128 and ((W - 1) // 2 + 1) % 4 == 0 and switches.on("HEAL_CONV_GEMM")
 
 
 def conv7x7_s2(x, w, bias=None, relu=False):
@@ -2972,8 +2975,9 @@ def conv3x3_winograd_ksplit(n, cin, cout, H, W, waves):
     4 x 24 x 32 pixels = 192 blocks of 54 / 64 chunks) is what this is for.  HEAL_C3_KSPLIT forces a value (0 / 1: off)."""
     chunks = (cin + 7) // 8
     blocks = -(-W // 16) * -(-H // (2 * waves)) * n * -(-cout // 64)
-    env = os.environ.get("HEAL_C3_KSPLIT")
-    want = int(env) if env is not None else (min(chunks // 8, max(2, -(-768 // blocks))) if blocks < 256 and chunks >= 32 else 1)
+    want = switches.number("HEAL_C3_KSPLIT")
+    if want is None:
+        want = min(chunks // 8, max(2, -(-768 // blocks))) if blocks < 256 and chunks >= 32 else 1
     if want < 2 or chunks < 2 or (H * W) % 4 or n * want > 65535:
         return 1
     want = min(want, chunks)
@@ -3037,7 +3041,7 @@ def conv_grad_enabled():
     """HEAL_CONV_GRAD=kernel: the dense 3x3 / 1x1 convolutions of the gradient path run forward, data gradient and weight gradient
     on this library's kernels (ConvGrad).  Opt-in: until scripts/conv_grad_bench.py says otherwise the library composition stays
     the default, as with HEAL_WATTN_GRAD."""
-    return os.environ.get("HEAL_CONV_GRAD", "") == "kernel"
+    return switches.get("HEAL_CONV_GRAD") == "kernel"
 
 
 # what ConvGrad ran since the process started (tests and scripts/conv_grad_bench.py read it): forward calls, heal_conv_wgrad calls,
