@@ -624,16 +624,21 @@ int heal_upsample2x_bilinear(const float* x, int n, int channels, int H, int W, 
  *   feature_alignnet_modules.py:314) with explicit top/left zero padding, bias and
  *   activation (0 none, 1 ReLU, 2 SiLU): the MBConv depthwise stage of the EfficientNet-b0 trunk
  *   (lss_submodule.py:93-105); x [n,C,H,W], weight [C,1,k,k] -> y [n,C,Ho,Wo].
- *   channel_sums (NULL or [n,C,T] f32, T = ceil(Wo/32) * ceil(Ho/8) output tiles): every block stores the sum of its tile's
- *   activated outputs -- the squeeze of the squeeze-excite stage that follows in an MBConv block, folded into this launch
- *   (plain stores, every word written); heal_se_gate(scale = 1/(Ho*Wo), tiles = T) adds the tiles up in a fixed order.  */
+ *   channel_sums (NULL or [n,C,T] f32, T = ceil(Wo/32) * ceil(Ho/8) output tiles, tile (ty, tx) at index ty * ceil(Wo/32) + tx):
+ *   the sum of each 32 x 8 tile's activated outputs -- the squeeze of the squeeze-excite stage that follows in an MBConv block,
+ *   folded into this launch (plain stores, every word written, a fixed reduction tree of depth 8 per tile);
+ *   heal_se_gate(scale = 1/(Ho*Wo), tiles = T) adds the tiles up in a fixed order.
+ *   One wave per tile, four tiles to a block: n * C * T < 2^31 is the only size limit.  Rows are staged with 16-B loads when
+ *   W % 4 == 0 and x is 16-B aligned, dword loads otherwise; y is bit for bit acc = bias, then fmaf over ky, kx ascending.  */
 int heal_depthwise_conv(const float* x, const float* weight, const float* bias, int n, int channels, int H, int W,
                         int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo, int act, float* y,
                         float* channel_sums, void* stream);
 
 /* heal_layernorm_nchw: LayerNorm over the channel axis of an NCHW map, y = (x - mean_c) / sqrt(var_c + eps) * gamma + beta
  *   (biased variance) -- the `norm` of the ConvNeXt aligner block (feature_alignnet_modules.py:12-31,318-321), which the
- *   reference evaluates as permute -> F.layer_norm -> ... -> permute.  x,y [n,C,H,W].                               */
+ *   reference evaluates as permute -> F.layer_norm -> ... -> permute.  x,y [n,C,H,W].  Two passes (mean, then the variance
+ *   of x - mean).  C <= 128 with C % 4 == 0 reads x once: the four waves of a block hold a quarter of a pixel's channels each
+ *   in registers and combine their partial sums in a fixed order; other C loop over the planes, one thread per pixel.   */
 int heal_layernorm_nchw(const float* x, const float* gamma, const float* beta, int n, int channels, int HW, float eps,
                         float* y, void* stream);
 
@@ -647,7 +652,9 @@ int heal_channel_dot(const float* x, const float* weight, const float* bias, int
  *   lss_submodule.py:93-105): gate [n,C] = sigmoid(W_expand silu(W_reduce mean + b_reduce) + b_expand) from the spatial
  *   squeezed input = scale * sum_t mean[n][c][t]; W_reduce [S,C]; w_expand_t = W_expand^T laid out [S,C] (coalesced
  *   columns); S <= 64.  tiles = 1, scale = 1: `mean` is the spatial mean [n,C]; tiles = T, scale = 1/(Ho*Wo): `mean` holds the
- *   per-tile sums [n,C,T] heal_depthwise_conv leaves.  Feeds heal_conv1x1's in_scale.                                 */
+ *   per-tile sums [n,C,T] heal_depthwise_conv leaves, added by a power-of-two group of lanes per channel (up to a wave,
+ *   lane i taking tiles i, i + lanes, ...; then a shuffle tree) -- a fixed order, so the gate is bit-reproducible; a few tiles
+ *   and tiles = 1 are added by one thread in tile order.  Feeds heal_conv1x1's in_scale.                              */
 int heal_se_gate(const float* mean, const float* w_reduce, const float* b_reduce, const float* w_expand_t,
                  const float* b_expand, int n, int channels, int squeezed, float scale, int tiles, float* gate,
                  void* stream);
