@@ -15,6 +15,7 @@ LIB_PATH = switches.get("HEAL_AMD_LIB") or os.path.join(HERE, "lib", "libheal_am
 HEADER = os.path.join(os.path.dirname(HERE), "include", "heal_amd.h")
 HEADER_EXPERIMENTAL = os.path.join(os.path.dirname(HERE), "include", "heal_amd_experimental.h")
 HEADER_TRAIN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train.h")
+HEADER_EXT = os.path.join(os.path.dirname(HERE), "include", "heal_amd_ext.h")
 
 _lib = None
 
@@ -82,6 +83,14 @@ def signatures_train():
         return parse_prototypes(f.read())
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_ext():
+    """{name: (restype, argtypes)} of include/heal_amd_ext.h: inference entry points added outside the versioned table of
+    signatures() (heal_warp_mha_fuse).  Every build exports them."""
+    with open(HEADER_EXT) as f:
+        return parse_prototypes(f.read())
+
+
 def declared_symbols(experimental=False):
     """Function names declared in include/heal_amd.h (the shipped C ABI), or with experimental=True in
     include/heal_amd_experimental.h."""
@@ -114,7 +123,7 @@ def lib():
         # process do not share devices, streams or allocations).
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**signatures(), **signatures_train()}.items():
+        for name, (res, args) in {**signatures(), **signatures_train(), **signatures_ext()}.items():
             if not hasattr(L, name):
                 continue  # declared but not built yet -> surfaces in call() / the symbol test
             f = getattr(L, name)

@@ -69,6 +69,7 @@ def _deps():
     inc = os.path.join(os.path.dirname(HERE), "include")
     hdrs.append(os.path.join(inc, "heal_amd.h"))
     hdrs.append(os.path.join(inc, "heal_amd_train.h"))      # the training-side entry points: part of every build
+    hdrs.append(os.path.join(inc, "heal_amd_ext.h"))        # inference entry points outside the versioned table: part of every build
     if EXPERIMENTAL:
         hdrs.append(os.path.join(inc, "heal_amd_experimental.h"))
     return hdrs

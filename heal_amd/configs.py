@@ -197,7 +197,7 @@ def _baseline_modality(base, strides, inplanes=None):
 
 def lidar_baseline(fusion_method="v2xvit", lidar_range=FULL_RANGE, max_cav=5, modality="m1"):
     """HeterModelBaseline (LiDAROnly/lidar_v2xvit.yaml; BASELINE config 5 with modality='m3'):
-    encoder -> plain BEV backbone -> shrinker -> single-scale fusion (v2xvit | att | max | cobevt | v2vnet | disconet) -> heads."""
+    encoder -> plain BEV backbone -> shrinker -> single-scale fusion (v2xvit | att | max | cobevt | v2vnet | disconet | where2comm | who2com) -> heads."""
     h = _common(lidar_range, max_cav)
     h["name"] = f"heal_amd_opv2v_{modality}_{fusion_method}"
     if modality == "m1":
@@ -222,6 +222,8 @@ def lidar_baseline(fusion_method="v2xvit", lidar_range=FULL_RANGE, max_cav=5, mo
                           "conv_gru": {"H": H, "W": W, "num_layers": 1, "kernel_size": [[3, 3]]}}
     elif fusion_method == "disconet":   # LiDAROnly/lidar_disco.yaml
         args["disconet"] = {"feat_dim": 256}
+    elif fusion_method in ("where2comm", "who2com"):    # heter_model_baseline.py:108-111: the entry is the feature width itself
+        args[fusion_method] = 256
     h["model"] = {"core_method": "heter_model_baseline", "args": args}
     # encoder + backbone + stride-2 shrinker leave the map at 1/4 of the 0.4 m anchor grid (lidar_v2xvit.yaml: feature_stride 4)
     h["postprocess"]["anchor_args"]["feature_stride"] = 4

@@ -886,6 +886,12 @@ def make_sharded(model, rank, world, wire_dtype=None, collective=None, split=Non
         if type(model.fusion_net).__name__ == "DiscoFusion":
             raise NotImplementedError("no agent-sharded split for DiscoFusion: its pixel weights need the ego's unwarped map next to "
                                       "every gathered agent (fusion_in_one.py:188-192), which the warp-then-gather exchange does not carry")
+        if type(model.fusion_net).__name__ == "Who2comFusion":
+            raise NotImplementedError("no agent-sharded split for Who2comFusion: its decode layer needs the ego's unwarped map next to "
+                                      "the fused one (fusion_in_one.py:526-533), which the warp-then-gather exchange does not carry")
+        if type(model.fusion_net).__name__ == "Where2commFusion":
+            raise NotImplementedError("no agent-sharded split for Where2commFusion: its projections run before the warp "
+                                      "(heal_warp_mha_fuse samples projected maps), not on the gathered ego-frame stack")
         if (world > 1 and type(model.fusion_net).__name__ == "V2XViTFusion"
                 and switches.on("HEAL_V2XVIT_STRIPES")):
             return ShardedBaselineStriped(model, rank, world, wire_dtype, collective)

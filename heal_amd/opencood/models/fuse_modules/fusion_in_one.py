@@ -1,8 +1,9 @@
 """Single-scale fusion operators used by HeterModelBaseline (reference: opencood/models/fuse_modules/
 fusion_in_one.py): MaxFusion (:87-124), AttFusion (:126-151, :14-45), DiscoFusion (:153-201), V2VNetFusion (:203-318),
-V2XViTFusion (:320-372), CoBEVT (:374-430).  Warping to the ego frame is K5's heal_warp_agent; the per-pixel attention is K6; CoBEVT's
-agent-window attention is heal_agent_window_attention (swap_fusion_modules.py); V2VNet's masked message aggregation is
-heal_v2v_message; DiscoNet's warp + pixel-weight MLP + softmax is heal_disco_fuse."""
+V2XViTFusion (:320-372), CoBEVT (:374-430), Where2commFusion (:431-484), Who2comFusion (:486-539).  Warping to the ego frame is K5's
+heal_warp_agent; the per-pixel attention is K6; CoBEVT's agent-window attention is heal_agent_window_attention
+(swap_fusion_modules.py); V2VNet's masked message aggregation is heal_v2v_message; DiscoNet's warp + pixel-weight MLP + softmax is
+heal_disco_fuse; Where2comm's warp + multi-head attention over agents is heal_warp_mha_fuse."""
 
 import numpy as np
 import torch
@@ -297,6 +298,152 @@ class DiscoFusion(nn.Module):
         return torch.stack(out)
 
 
+class Where2commFusion(nn.Module):
+    """fusion_in_one.py:431-484 (with where2comm_attn.py:64-103).  Per scene: every agent warped into the ego frame (the ego too),
+    then per pixel an nn.MultiheadAttention of the ego over the agents (no key mask: an agent that misses the pixel is a zero vector
+    and keeps its share), out-projection + residual (the WARPED ego) + LayerNorm, feed-forward + residual + LayerNorm.  One agent
+    is not the identity: the projections, both LayerNorms and the feed-forward still run.
+
+    On the CPU, under autograd, for more agents than the kernel takes and for shapes the kernels refuse, the reference's torch
+    arithmetic runs (`forward_torch`).  Inference on the device (Where2comm) rests on W warp(x) = warp(W x): the K | V
+    projection of all agents and the Q projection of the egos are two heal_conv1x1 launches on the UNWARPED maps without bias,
+    heal_warp_mha_fuse samples them, adds the biases and attends (one launch per scene), and the tail runs once on the stacked
+    batch in NCHW (heal_conv1x1 with fused residual / ReLU, heal_layernorm_nchw).
+    `fused` (class attribute; set it on an instance for an A/B, scripts/where2comm_bench.py) = False keeps the torch arithmetic on
+    the device too."""
+    fused = True
+
+    def __init__(self, feature_dims):
+        super().__init__()
+        from heal_amd.opencood.models.fuse_modules.where2comm_attn import EncodeLayer
+        self.mha_fusion = EncodeLayer(feature_dims)
+
+    # ---- the reference's arithmetic ----------------------------------------------------------------------------------------
+    def forward_torch(self, x, record_len, affine_matrix):
+        """fusion_in_one.py:442-484 as written (the CPU, gradient and unsupported-shape path)."""
+        _, C, H, W = x.shape
+        lens = record_len_to_list(record_len)
+        aff = affine_matrix if isinstance(affine_matrix, torch.Tensor) else torch.from_numpy(np.asarray(affine_matrix))
+        aff = aff.to(x.device)
+        out = []
+        for b, feats in enumerate(regroup(x, lens)):
+            N = lens[b]
+            t_matrix = aff[b][:N, :N, :, :]
+            neighbor = _warp_affine_simple(feats, t_matrix[0, :, :, :], (H, W))
+            tokens = neighbor.permute(0, 2, 3, 1).flatten(1, 2)                     # [N, HW, C]
+            fused = self.mha_fusion(tokens[0:1], tokens, tokens)                    # [1, HW, C]
+            out.append(fused.permute(0, 2, 1).reshape(C, H, W))
+        return torch.stack(out)
+
+    # ---- inference on the device -------------------------------------------------------------------------------------------
+    def fused_ok(self, x, lens):
+        C, H, W = (int(v) for v in x.shape[1:])
+        attn = self.mha_fusion.attn
+        return (self.fused and x.is_cuda and x.dtype == torch.float32 and not (torch.is_grad_enabled() and x.requires_grad)
+                and C == attn.embed_dim and C % attn.num_heads == 0 and ops.conv1x1_supported(C, 2 * C, H * W)
+                and max(lens) <= ops.W2C_MAX_AGENTS)
+
+    def _weights(self):
+        """(Wq [C,C,1,1], Wkv [2C,C,1,1], bq, bk, bv, Wo, W1, W2 as [C,C,1,1]) split and reshaped from the parameters (derived store:
+        rebuilt when one of them changes in place, capture-safe)."""
+        from heal_amd.derived import derived
+        e = self.mha_fusion
+        srcs = (e.attn.in_proj_weight, e.attn.in_proj_bias, e.attn.out_proj.weight, e.linear1.weight, e.linear2.weight)
+
+        def build():
+            C = e.attn.embed_dim
+            w, b = e.attn.in_proj_weight, e.attn.in_proj_bias
+            as_conv = lambda m: m.reshape(-1, C, 1, 1).contiguous()      # noqa: E731
+            return (as_conv(w[:C]), as_conv(w[C:]), b[:C].contiguous(), b[C:2 * C].contiguous(), b[2 * C:].contiguous(),
+                    as_conv(e.attn.out_proj.weight), as_conv(e.linear1.weight), as_conv(e.linear2.weight))
+        return derived("where2comm_split", srcs, build)
+
+    def forward(self, x, record_len, affine_matrix):
+        lens = record_len_to_list(record_len)
+        if not self.fused_ok(x, lens):
+            return self.forward_torch(x, record_len, affine_matrix)
+        aff, f64 = _host_affine(affine_matrix)
+        e = self.mha_fusion
+        wq, wkv, bq, bk, bv, wo, w1, w2 = self._weights()
+        x = x.contiguous()
+        starts = [sum(lens[:b]) for b in range(len(lens))]
+        egos = x[:1] if len(lens) == 1 else torch.stack([x[s] for s in starts])
+        kv = ops.conv1x1(x, wkv)                          # [sum n, 2C, H, W]: K over V of every agent, unwarped, no bias
+        q = ops.conv1x1(egos, wq)                         # [B, C, H, W]: the egos only
+        ctx, ego_w = [], []
+        for b, (s, n) in enumerate(zip(starts, lens)):
+            c, w = ops.warp_mha_fuse(q[b], kv[s:s + n], egos[b], bq, bk, bv, e.attn.num_heads, aff[b][0, :n], f64)
+            ctx.append(c)
+            ego_w.append(w)
+        ctx = ctx[0].unsqueeze(0) if len(lens) == 1 else torch.stack(ctx)
+        ego_w = ego_w[0].unsqueeze(0) if len(lens) == 1 else torch.stack(ego_w)
+        o1 = ops.layernorm_nchw(ops.conv1x1(ctx, wo, e.attn.out_proj.bias, residual=ego_w), e.norm1.weight, e.norm1.bias, e.norm1.eps)
+        h = ops.conv1x1(o1, w1, e.linear1.bias, act=1)
+        return ops.layernorm_nchw(ops.conv1x1(h, w2, e.linear2.bias, residual=o1), e.norm2.weight, e.norm2.bias, e.norm2.eps)
+
+
+class ScaledDotProductAttention(nn.Module):
+    """fusion_in_one.py:14-45: softmax(q k^T / sqrt(dim)) v.  No parameters."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.sqrt_dim = float(np.sqrt(dim))
+
+    def forward(self, query, key, value):
+        score = torch.bmm(query, key.transpose(1, 2)) / self.sqrt_dim
+        return torch.bmm(torch.softmax(score, -1), value)
+
+
+class Who2comFusion(nn.Module):
+    """fusion_in_one.py:486-539.  Per scene: AttFusion's ego row (every agent warped into the ego frame, softmax(x_0 . x_j /
+    sqrt(feature_dims)) weights), concatenated BEHIND the ego's UNWARPED map, then a 3x3 convolution 2C to C.
+
+    Inference on the device: heal_warp_att_fuse_levels (one level) per scene, the concatenation, and ONE heal_conv3x3 on the stacked
+    batch; otherwise the reference's torch arithmetic (`forward_torch`).  `fused` as on Where2commFusion."""
+    fused = True
+
+    def __init__(self, feature_dims):
+        super().__init__()
+        self.att = ScaledDotProductAttention(feature_dims)
+        self.decode_layer = nn.Conv2d(feature_dims * 2, feature_dims, kernel_size=3, stride=1, padding=1)
+
+    def forward_torch(self, x, record_len, affine_matrix):
+        """fusion_in_one.py:493-539 as written (the CPU, gradient and unsupported-shape path)."""
+        _, C, H, W = x.shape
+        lens = record_len_to_list(record_len)
+        aff = affine_matrix if isinstance(affine_matrix, torch.Tensor) else torch.from_numpy(np.asarray(affine_matrix))
+        aff = aff.to(x.device)
+        out = []
+        for b, feats in enumerate(regroup(x, lens)):
+            N = lens[b]
+            t_matrix = aff[b][:N, :N, :, :]
+            neighbor = _warp_affine_simple(feats, t_matrix[0, :, :, :], (H, W))
+            ego = feats[0]
+            neighbor = neighbor.view(N, C, -1).permute(2, 0, 1)
+            neighbor = self.att(neighbor, neighbor, neighbor)
+            neighbor = neighbor.permute(1, 2, 0).view(N, C, H, W)[0, ...]
+            out.append(self.decode_layer(torch.cat((ego, neighbor), dim=0).unsqueeze(0)))
+        return torch.cat(out, dim=0)
+
+    def fused_ok(self, x, lens):
+        return (self.fused and x.is_cuda and x.dtype == torch.float32 and not (torch.is_grad_enabled() and x.requires_grad)
+                and int(x.shape[1]) == self.decode_layer.out_channels and max(lens) <= ops.WARP_ATT_MAX_AGENTS)
+
+    def forward(self, x, record_len, affine_matrix):
+        lens = record_len_to_list(record_len)
+        if not self.fused_ok(x, lens):
+            return self.forward_torch(x, record_len, affine_matrix)
+        aff, f64 = _host_affine(affine_matrix)
+        x = x.contiguous()
+        cat, start = [], 0
+        for b, n in enumerate(lens):
+            fused = ops.warp_att_fuse_levels([x[start:start + n]], aff[b][0, :n], f64, "att", [self.att.sqrt_dim])[0]
+            cat.append(torch.cat((x[start], fused), dim=0))
+            start += n
+        cat = cat[0].unsqueeze(0) if len(lens) == 1 else torch.stack(cat)
+        return ops.conv3x3(cat, self.decode_layer.weight, self.decode_layer.bias)
+
+
 class V2VNetFusion(nn.Module):
     """fusion_in_one.py:203-318 (with sub_modules/convgru.py).  num_iteration Jacobi rounds of message passing: every node i
     warps every node j into its frame, msg_ij = msg_cnn(cat(nbr_ij, x_i)) * roi_mask_ij, agg_i = mean_j | max_j msg_ij, then
@@ -539,8 +686,9 @@ def fuse_levels(fusion_net, feature_list, record_len, affine_matrix):
 
 
 def build_fusion(args):
-    """The single-scale fusion operator a model YAML names (`fusion_method`: max | att | v2xvit | cobevt | v2vnet | disconet; where2comm and
-    who2com, which no YAML file selects, are outside the hot-path scope)."""
+    """The single-scale fusion operator a model YAML names (`fusion_method`: max | att | v2xvit | cobevt | v2vnet | disconet | where2comm
+    | who2com -- the eight of heter_model_baseline.py:96-111).  A method named without its argument entry (args[method]) is answered
+    like an unknown one, with the NotImplementedError that lists the built methods (the reference raises KeyError there)."""
     method = args["fusion_method"]
     if method == "max":
         return MaxFusion()
@@ -554,5 +702,9 @@ def build_fusion(args):
         return V2VNetFusion(args["v2vnet"])
     if method == "disconet":
         return DiscoFusion(args["disconet"]["feat_dim"])
-    raise NotImplementedError(f"fusion_method '{method}' is outside the hot-path scope (SURVEY 2, row 2): max, att, v2xvit, cobevt, "
-                              "v2vnet and disconet are built")
+    if method == "where2comm" and "where2comm" in args:
+        return Where2commFusion(args["where2comm"])
+    if method == "who2com" and "who2com" in args:
+        return Who2comFusion(args["who2com"])
+    raise NotImplementedError(f"fusion_method '{method}' is not built, or its argument entry args['{method}'] is missing (SURVEY 2, row 2): "
+                              "max, att, v2xvit, cobevt, v2vnet, disconet, where2comm and who2com are built")

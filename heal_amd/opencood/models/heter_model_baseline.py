@@ -1,6 +1,6 @@
 """HeterModelBaseline -- single-scale heterogeneous collaboration with a pluggable fusion operator
-(reference: opencood/models/heter_model_baseline.py:26-236).  In scope: fusion_method max / att / v2xvit / cobevt / v2vnet / disconet
-(BASELINE config 5 uses v2xvit)."""
+(reference: opencood/models/heter_model_baseline.py:26-236).  In scope: fusion_method max / att / v2xvit / cobevt / v2vnet / disconet /
+where2comm / who2com (BASELINE config 5 uses v2xvit)."""
 from collections import Counter
 
 import torch

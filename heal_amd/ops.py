@@ -804,6 +804,52 @@ def disco_fuse(feats, affine_rows, grid_f64, e0, w1n_frag, w2, b2, w3, b3, w4, b
     return (out, scores) if return_scores else out
 
 
+W2C_MAX_AGENTS = _limit("HEAL_WARP_MAX_AGENTS")       # heal_warp_mha_fuse (include/heal_amd_ext.h)
+
+
+def warp_mha_fuse(q_map, kv_map, x_ego, bq, bk, bv, heads, affine_rows, grid_f64=True, scale=None, return_logits=False):
+    """Where2comm's fusion of one scene between its projections and its out-projection in ONE launch (heal_warp_mha_fuse;
+    fusion_in_one.py:431-484): the projected maps of every agent sampled in the ego frame, the projection biases added after
+    sampling, multi-head attention of the ego pixel over ALL agents (no key mask), and the warped ego map (the residual).
+    q_map [C,H,W] = Wq x_0 and kv_map [n,2C,H,W] = [Wk; Wv] x_j: projections of the UNWARPED maps without bias; x_ego [C,H,W] the
+    ego's unwarped map; bq, bk, bv [C]; 1..W2C_MAX_AGENTS agents, C % heads == 0; affine_rows [n,2,3] (host array or CUDA tensor
+    read at run time); scale: the factor on q (None: 1 / sqrt(C / heads))
+    -> (ctx [C,H,W], ego_warped [C,H,W]), and the scaled logits [n,heads,H,W] with return_logits."""
+    who = "warp_mha_fuse"
+    q_map = _need(q_map, torch.float32, "q_map")
+    kv_map = _need(kv_map, torch.float32, "kv_map")
+    x_ego = _need(x_ego, torch.float32, "x_ego")
+    if q_map.dim() != 3:
+        raise _capi.HealAmdError(f"{who}: q_map must be [C, H, W], got {tuple(q_map.shape)}")
+    C, H, W = (int(v) for v in q_map.shape)
+    heads = int(heads)
+    if heads < 1 or C % heads:
+        raise _capi.HealAmdError(f"{who}: C = {C} is not a multiple of heads = {heads}")
+    if kv_map.dim() != 4 or tuple(kv_map.shape[1:]) != (2 * C, H, W):
+        raise _capi.HealAmdError(f"{who}: kv_map has shape {tuple(kv_map.shape)}, want [n, {2 * C}, {H}, {W}] (K over V)")
+    n = int(kv_map.shape[0])
+    if not 1 <= n <= W2C_MAX_AGENTS:
+        raise _capi.HealAmdError(f"{who}: 1..{W2C_MAX_AGENTS} agents per scene (got {n})")
+    if tuple(x_ego.shape) != (C, H, W):
+        raise _capi.HealAmdError(f"{who}: x_ego has shape {tuple(x_ego.shape)}, want {(C, H, W)}")
+    bq = _need_channels(bq, C, "bq", who)
+    bk = _need_channels(bk, C, "bk", who)
+    bv = _need_channels(bv, C, "bv", who)
+    a, ap, adev = _affine_args(affine_rows, n)
+    scale = float((C // heads) ** -0.5 if scale is None else scale)
+    dev = q_map.device
+    ctx = torch.empty((C, H, W), dtype=torch.float32, device=dev)
+    ego_warped = torch.empty((C, H, W), dtype=torch.float32, device=dev)
+    logits = torch.empty((n, heads, H, W), dtype=torch.float32, device=dev) if return_logits else None
+    flops = 2.0 * H * W * C * (2 * n + 1) + 8.0 * H * W * C * (2 * n + 2)      # the dot products and sums; 4 taps per sample
+    # compulsory traffic: Q, the ego map and every agent's K and V once, the context and the warped ego (and the logits when asked)
+    nbytes = 4.0 * H * W * ((2 * n + 2) * C + 2 * C + (n * heads if return_logits else 0))
+    with _Timed(f"warp_mha_fuse_c{C}", flops, nbytes, kernel_events=True):
+        _capi.call("heal_warp_mha_fuse", _ptr(q_map), _ptr(kv_map), _ptr(x_ego), _ptr(bq), _ptr(bk), _ptr(bv), n, C, heads, H, W,
+                   scale, ap, adev, int(bool(grid_f64)), _ptr(ctx), _ptr(ego_warped), _optr(logits), _stream())
+    return (ctx, ego_warped, logits) if return_logits else (ctx, ego_warped)
+
+
 def warp_fuse_backward(feats, occ, affine_rows, grad_out, grid_f64=True, crop=None):
     """Gradient of warp_fuse with respect to (feats, occ): grad_out [C,H,W] -> ([n,C,H,W], [n,1,H,W])."""
     feats = _need(feats, torch.float32, "feats")

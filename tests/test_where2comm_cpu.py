@@ -1,0 +1,263 @@
+"""Where2comm and Who2com fusion (fusion_method: where2comm | who2com) on the CPU: the mirrors' torch arithmetic against the reference's
+outputs (tests/golden/where2comm_small.npz, who2com_small.npz), their parameter layout against the reference's
+(tests/golden/where2comm_state_dict_keys.json), the wiring (build_fusion, configs.lidar_baseline, dist.make_sharded) and the
+header of the entry point outside the versioned table (include/heal_amd_ext.h).  No GPU."""
+import ctypes
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from heal_amd import configs
+from tests.golden.w2c_fill import fill_w2c
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+E2E_RANGE = [-12.8, -12.8, -3, 12.8, 12.8, 1]        # the end-to-end cases (a 32 x 32 fusion map)
+TOL = 1e-3                                           # the project's tolerance against the goldens
+# prefix -> channels; as tests/golden/gen_golden_where2comm.py
+CASES = {"n5_": 128, "n3_": 128, "n1_": 128, "b2_": 128, "odd_": 128, "c64_": 64, "far_": 128}
+MULTI = ["n5_", "n3_", "b2_", "odd_", "c64_", "far_"]        # cases with a scene of more than one agent
+WHO_CASES = {"n3_": 128, "n1_": 128, "b2_": 128, "odd_": 128}
+
+
+def rel_err(a, b):
+    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-12))
+
+
+def make_w2c(prefix):
+    from heal_amd.opencood.models.fuse_modules.fusion_in_one import Where2commFusion
+    return fill_w2c(Where2commFusion(CASES[prefix])).eval()
+
+
+def make_who(prefix):
+    from heal_amd.opencood.models.fuse_modules.fusion_in_one import Who2comFusion
+    return fill_w2c(Who2comFusion(WHO_CASES[prefix])).eval()
+
+
+def case_inputs(g, prefix):
+    """(x, record_len, affine) of a module case: int8-coded maps, the affines normalised as HeterModelBaseline does."""
+    from oracle import oracle_np as O
+    x = torch.from_numpy(g[f"{prefix}x_code"].astype(np.float32) / np.float32(g["x_scale"]))
+    return x, torch.from_numpy(g[f"{prefix}record_len"]), O.normalize_pairwise_tfm(g[f"{prefix}pairwise"], *g["HW_m"], 1)
+
+
+def e2e_hypes(method):
+    """v2xset/LiDAROnly/lidar_attfuse.yaml on the small range with the fusion substituted: lidar_baseline(method) with the YAML's
+    stride-1 shrinker."""
+    hy = configs.lidar_baseline(method, E2E_RANGE)
+    hy["model"]["args"]["m1"]["shrink_header"]["stride"] = [1]
+    return hy
+
+
+def e2e_data(g):
+    return {"inputs_m1": {"voxel_features": torch.from_numpy(g["e2e_voxel_features"]),
+                          "voxel_coords": torch.from_numpy(g["e2e_voxel_coords"]).to(torch.int32),
+                          "voxel_num_points": torch.from_numpy(g["e2e_voxel_num_points"]).to(torch.int32)},
+            "agent_modality_list": ["m1"] * 3, "record_len": torch.tensor([3]),
+            "pairwise_t_matrix": torch.from_numpy(g["e2e_pairwise"])}
+
+
+def scene_probs(model, x, record_len, aff):
+    """Per scene: (probabilities [n, heads, H, W] recomputed from the module's own weights by the restatement of the issue --
+    project, per-head softmax over the agents --, covered [n, H, W]: whether the agent has a tap inside its map at the pixel)."""
+    from heal_amd.opencood.models.fuse_modules.fusion_in_one import _warp_affine_simple, regroup
+    aff = torch.as_tensor(aff)
+    attn = model.mha_fusion.attn
+    C, heads = attn.embed_dim, attn.num_heads
+    d = C // heads
+    wq, wk, _ = attn.in_proj_weight.chunk(3)
+    bq, bk, _ = attn.in_proj_bias.chunk(3)
+    out = []
+    with torch.no_grad():
+        for b, feats in enumerate(regroup(x, record_len)):
+            n, _, H, W = feats.shape
+            nbr = _warp_affine_simple(feats, aff[b][0, :n], (H, W))
+            cover = _warp_affine_simple(torch.ones((n, 1, H, W)), aff[b][0, :n].float(), (H, W))[:, 0] > 0
+            q = torch.einsum("oc,chw->ohw", wq, nbr[0]) + bq[:, None, None]
+            k = torch.einsum("oc,nchw->nohw", wk, nbr) + bk[None, :, None, None]
+            logit = (q.view(1, heads, d, H, W) * d ** -0.5 * k.view(n, heads, d, H, W)).sum(2)
+            out.append((torch.softmax(logit, dim=0), cover))
+    return out
+
+
+@pytest.fixture(scope="module")
+def g():
+    return np.load(os.path.join(GOLD, "where2comm_small.npz"))
+
+
+@pytest.fixture(scope="module")
+def gw():
+    return np.load(os.path.join(GOLD, "who2com_small.npz"))
+
+
+@pytest.mark.parametrize("prefix", sorted(CASES))
+def test_where2comm_module_matches_reference(g, prefix):
+    model = make_w2c(prefix)
+    with torch.no_grad():
+        got = model(*case_inputs(g, prefix)).numpy()
+    want = g[f"{prefix}out"]
+    assert got.shape == want.shape
+    assert rel_err(got, want) <= TOL, rel_err(got, want)
+
+
+@pytest.mark.parametrize("prefix", sorted(WHO_CASES))
+def test_who2com_module_matches_reference(gw, prefix):
+    model = make_who(prefix)
+    with torch.no_grad():
+        got = model(*case_inputs(gw, prefix)).numpy()
+    want = gw[f"{prefix}out"]
+    assert got.shape == want.shape
+    assert rel_err(got, want) <= TOL, rel_err(got, want)
+
+
+@pytest.mark.parametrize("prefix", MULTI)
+def test_where2comm_fixture_is_not_degenerate(g, prefix):
+    """A uniform softmax makes the attention a plain mean of the values and a one-hot softmax a selection: neither can tell a
+    wrong scale or a wrong head split from a right one.  In every scene of more than one agent at least half of the (pixel, head)
+    pairs have max probability - 1 / n above 0.05 and fewer than 5 % have a max probability above 0.99.  In far_ at least 10 % of the
+    pixels have an agent with no tap inside its map."""
+    model = make_w2c(prefix)
+    x, rl, aff = case_inputs(g, prefix)
+    for b, (p, cover) in enumerate(scene_probs(model, x, rl, aff)):
+        n = p.shape[0]
+        if n < 2:
+            continue
+        pmax = p.max(0)[0]
+        spread = float((pmax - 1.0 / n > 0.05).float().mean())
+        onehot = float((pmax > 0.99).float().mean())
+        missed = float((~cover).any(0).float().mean())
+        print(f"{prefix} scene {b}: n={n}, median max p {float(pmax.median()):.3f} (uniform {1.0 / n:.3f}), spread>0.05 on {spread:.3f}, "
+              f"p>0.99 on {onehot:.3f}, pixels with an agent off its map {missed:.3f}")
+        assert spread >= 0.5, spread
+        assert onehot < 0.05, onehot
+        if prefix == "far_":
+            assert missed >= 0.10, missed
+
+
+def test_where2comm_single_agent_is_not_the_warped_map(g):
+    """One agent: the context is v_0, and the out-projection, both LayerNorms and the feed-forward still run."""
+    from heal_amd.opencood.models.fuse_modules.fusion_in_one import _warp_affine_simple
+    model = make_w2c("n1_")
+    x, rl, aff = case_inputs(g, "n1_")
+    with torch.no_grad():
+        got = model(x, rl, aff)
+    warped = _warp_affine_simple(x, torch.as_tensor(aff)[0][0, :1], x.shape[2:])
+    assert rel_err(got.numpy(), g["n1_out"]) <= TOL
+    assert rel_err(got.numpy(), warped.numpy()) > 0.1
+
+
+@pytest.mark.grad
+@pytest.mark.parametrize("method", ["where2comm", "who2com"])
+def test_heter_model_baseline_matches_reference(g, gw, method):
+    from heal_amd.opencood.tools.train_utils import create_model
+    gold = g if method == "where2comm" else gw
+    model = fill_w2c(create_model(e2e_hypes(method))).eval()
+    out = model(e2e_data(gold))      # autograd records: the encoders run their (CPU) gradient path
+    for key, name in (("cls_preds", "cls"), ("reg_preds", "reg"), ("dir_preds", "dir")):
+        e = rel_err(out[key].detach().numpy(), gold[f"e2e_{name}"])
+        assert e <= TOL, (key, e)
+
+
+def test_lidar_baseline_configs_build():
+    from heal_amd.opencood.models.fuse_modules.fusion_in_one import Where2commFusion, Who2comFusion
+    from heal_amd.opencood.models.fuse_modules.where2comm_attn import EncodeLayer
+    from heal_amd.opencood.tools.train_utils import create_model
+    for method, cls in (("where2comm", Where2commFusion), ("who2com", Who2comFusion)):
+        hy = configs.lidar_baseline(method)
+        assert hy["model"]["args"]["fusion_method"] == method and hy["model"]["args"][method] == 256
+        model = create_model(hy)
+        assert isinstance(model.fusion_net, cls)
+    w2c = create_model(configs.lidar_baseline("where2comm")).fusion_net
+    assert isinstance(w2c.mha_fusion, EncodeLayer) and w2c.mha_fusion.attn.num_heads == 8
+    assert w2c.mha_fusion.attn.dropout == 0 and w2c.mha_fusion.norm1.eps == 1e-5
+    assert sum(p.numel() for p in w2c.parameters()) == 6 * 256 * 256 + 10 * 256
+    who = create_model(configs.lidar_baseline("who2com")).fusion_net
+    assert who.att.sqrt_dim == 16.0 and not list(who.att.parameters())
+    assert sum(p.numel() for p in who.parameters()) == 256 * 512 * 9 + 256
+
+
+def test_build_fusion_builds_both_and_names_the_built_methods_otherwise():
+    from heal_amd.opencood.models.fuse_modules.fusion_in_one import Where2commFusion, Who2comFusion, build_fusion
+    assert isinstance(build_fusion({"fusion_method": "where2comm", "where2comm": 64}), Where2commFusion)
+    assert isinstance(build_fusion({"fusion_method": "who2com", "who2com": 64}), Who2comFusion)
+    for method in ("where2comm", "who2com", "no_such_fusion"):
+        with pytest.raises(NotImplementedError, match="disconet") as e:
+            build_fusion({"fusion_method": method})
+        assert all(m in str(e.value) for m in ("max", "att", "v2xvit", "cobevt", "v2vnet", "disconet", "where2comm", "who2com"))
+
+
+@pytest.mark.parametrize("method,name", [("where2comm", "Where2commFusion"), ("who2com", "Who2comFusion")])
+def test_sharded_split_is_refused(method, name):
+    from heal_amd import dist
+    from heal_amd.opencood.tools.train_utils import create_model
+    model = create_model(configs.lidar_baseline(method, E2E_RANGE))
+    with pytest.raises(NotImplementedError, match=name):
+        dist.make_sharded(model, 0, 2)
+
+
+def test_state_dict_matches_reference():
+    """Keys and shapes equal the reference's two modules at 256 channels (needs no reference tree); a dict keyed like the
+    reference's loads strictly."""
+    from heal_amd.opencood.tools.train_utils import create_model
+    with open(os.path.join(GOLD, "where2comm_state_dict_keys.json")) as fh:
+        table = json.load(fh)
+    assert sorted(table) == ["where2comm", "who2com"]
+    for method, keys in table.items():
+        model = create_model(configs.lidar_baseline(method, E2E_RANGE))
+        mine = {k: list(v.shape) for k, v in model.state_dict().items() if k.startswith("fusion_net.")}
+        assert mine == keys, method
+        model.fusion_net.load_state_dict({k[len("fusion_net."):]: torch.randn(shape) for k, shape in keys.items()}, strict=True)
+    pre = "fusion_net.mha_fusion."
+    assert table["where2comm"][pre + "attn.in_proj_weight"] == [768, 256] and table["where2comm"][pre + "attn.in_proj_bias"] == [768]
+    assert table["where2comm"][pre + "attn.out_proj.weight"] == [256, 256] and table["where2comm"][pre + "norm2.bias"] == [256]
+    assert table["who2com"] == {"fusion_net.decode_layer.weight": [256, 512, 3, 3], "fusion_net.decode_layer.bias": [256]}
+
+
+@pytest.mark.grad
+def test_gradient_path_reaches_every_parameter(g, gw):
+    for model, gold in ((make_w2c("n3_"), g), (make_who("n3_"), gw)):
+        x, rl, aff = case_inputs(gold, "n3_")
+        x = x.clone().requires_grad_(True)
+        out = model(x, rl, aff)
+        assert rel_err(out.detach().numpy(), gold["n3_out"]) <= TOL
+        out.square().mean().backward()
+        assert x.grad is not None and bool(torch.isfinite(x.grad).all()) and float(x.grad.abs().max()) > 0
+        for name, p in model.named_parameters():
+            assert p.grad is not None and bool(torch.isfinite(p.grad).all()) and float(p.grad.abs().max()) > 0, name
+
+
+def test_where2comm_more_agents_than_the_kernel_takes_run_on_the_torch_path():
+    from heal_amd import ops
+    from heal_amd.opencood.models.fuse_modules.fusion_in_one import Where2commFusion
+    n = ops.W2C_MAX_AGENTS + 1
+    model = fill_w2c(Where2commFusion(32)).eval()
+    x = torch.randn((n, 32, 8, 8), generator=torch.Generator().manual_seed(1))
+    aff = np.tile(np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), (1, n, n, 1, 1))
+    with torch.no_grad():
+        out = model(x, torch.tensor([n]), aff)
+    assert out.shape == (1, 32, 8, 8) and bool(torch.isfinite(out).all())
+
+
+def test_ext_header_is_parsed_bound_and_exported():
+    """include/heal_amd_ext.h: its prototype as written out here, bound by _capi.lib(), exported by the library; the versioned
+    table, the experimental header and the training header keep their entry points."""
+    from heal_amd import _capi, build, ops
+    P, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    assert _capi.signatures_ext() == {"heal_warp_mha_fuse": (I, [P] * 6 + [I] * 5 + [F, P, P, I, P, P, P, P])}
+    assert (len(_capi.signatures(False)), len(_capi.signatures(True)), len(_capi.signatures_train())) == (126, 7, 4)
+    assert not set(_capi.signatures_ext()) & (set(_capi.signatures()) | set(_capi.signatures_train()))
+    assert _capi.HEADER_EXT in build._deps()                    # an edit of the header rebuilds the objects
+    build.build()
+    L = _capi.lib()
+    assert hasattr(L, "heal_warp_mha_fuse")
+    assert L.heal_warp_mha_fuse.argtypes == _capi.signatures_ext()["heal_warp_mha_fuse"][1] and L.heal_warp_mha_fuse.restype is I
+    assert ops.W2C_MAX_AGENTS == _capi.header_define("HEAL_WARP_MAX_AGENTS")
+
+
+def test_warp_mha_fuse_has_no_cpu_path():
+    from heal_amd import _capi, ops
+    z = torch.zeros(8, 4, 4)
+    with pytest.raises(_capi.HealAmdError, match="CUDA/HIP"):
+        ops.warp_mha_fuse(z, torch.zeros(1, 16, 4, 4), z, torch.zeros(8), torch.zeros(8), torch.zeros(8), 2, np.zeros((1, 2, 3)))
