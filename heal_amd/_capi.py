@@ -16,6 +16,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "heal_amd.h")
 HEADER_EXPERIMENTAL = os.path.join(os.path.dirname(HERE), "include", "heal_amd_experimental.h")
 HEADER_TRAIN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train.h")
 HEADER_EXT = os.path.join(os.path.dirname(HERE), "include", "heal_amd_ext.h")
+HEADER_TRAIN_ATTN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train_attn.h")
 
 _lib = None
 
@@ -91,6 +92,14 @@ def signatures_ext():
         return parse_prototypes(f.read())
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_train_attn():
+    """{name: (restype, argtypes)} of include/heal_amd_train_attn.h: the training side of CoBEVT's agent-window attention (its
+    backward kernel).  Every build exports them; like signatures_train() they are outside the versioned inference ABI."""
+    with open(HEADER_TRAIN_ATTN) as f:
+        return parse_prototypes(f.read())
+
+
 def declared_symbols(experimental=False):
     """Function names declared in include/heal_amd.h (the shipped C ABI), or with experimental=True in
     include/heal_amd_experimental.h."""
@@ -123,7 +132,7 @@ def lib():
         # process do not share devices, streams or allocations).
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**signatures(), **signatures_train(), **signatures_ext()}.items():
+        for name, (res, args) in {**signatures(), **signatures_train(), **signatures_ext(), **signatures_train_attn()}.items():
             if not hasattr(L, name):
                 continue  # declared but not built yet -> surfaces in call() / the symbol test
             f = getattr(L, name)

@@ -2,8 +2,8 @@
 fusion_in_one.py): MaxFusion (:87-124), AttFusion (:126-151, :14-45), DiscoFusion (:153-201), V2VNetFusion (:203-318),
 V2XViTFusion (:320-372), CoBEVT (:374-430), Where2commFusion (:431-484), Who2comFusion (:486-539).  Warping to the ego frame is K5's
 heal_warp_agent; the per-pixel attention is K6; CoBEVT's agent-window attention is heal_agent_window_attention
-(swap_fusion_modules.py); V2VNet's masked message aggregation is heal_v2v_message; DiscoNet's warp + pixel-weight MLP + softmax is
-heal_disco_fuse; Where2comm's warp + multi-head attention over agents is heal_warp_mha_fuse."""
+(swap_fusion_modules.py; with `grad_kernel` its backward is heal_agent_window_attention_backward); V2VNet's masked message
+aggregation is heal_v2v_message; DiscoNet's warp + pixel-weight MLP + softmax is heal_disco_fuse; Where2comm's warp + multi-head attention over agents is heal_warp_mha_fuse."""
 
 import numpy as np
 import torch
@@ -118,6 +118,11 @@ class CoBEVT(_WarpThenFuse):
         input_dim = args["input_dim"]
         self.layers = nn.ModuleList([SwapFusionBlockMask(input_dim, args["mlp_dim"], args["dim_head"], args["window_size"],
                                                          args["agent_size"], args["drop_out"]) for _ in range(self.depth)])
+        # opt-in: under autograd on the device the blocks run ops.AgentWindowAttention (forward + backward kernels) instead of the
+        # library's composition
+        self.grad_kernel = bool(args.get("grad_kernel", False))
+        for stage in self.layers:
+            stage.window_attention.fn.grad_kernel = stage.grid_attention.fn.grad_kernel = self.grad_kernel
         self.mlp_head = nn.Sequential(_NoParams("Reduce('b m d h w -> b d h w', 'mean')"),
                                       _NoParams("Rearrange('b d h w -> b h w d')"),
                                       nn.LayerNorm(input_dim), nn.Linear(input_dim, input_dim),

@@ -2,9 +2,12 @@
 sub_modules/base_transformer.py:17-39 PreNormResidual / FeedForward, fusion_in_one.py:374-430 CoBEVT).
 
 Module / parameter layout mirrors the reference so that checkpoints load (the persistent `relative_position_index` buffer
-included).  CoBEVT itself (Regroup, warp, blocks, mlp_head) is in fusion_in_one.py.  Two execution paths:
+included).  CoBEVT itself (Regroup, warp, blocks, mlp_head) is in fusion_in_one.py.  Three execution paths:
   * the reference's torch arithmetic on x [B, L, C, H, W] with einops' rearranges restated as view / permute -- on the CPU and
-    whenever autograd records (the gradient path; no HIP backward);
+    whenever autograd records (the default gradient path: the library's composition, no HIP kernel);
+  * opt-in (Attention.grad_kernel, CoBEVT's `grad_kernel` argument), when autograd records on the device: the block token-major
+    [B, L, H, W, C] with the torch LayerNorm / Linear / FeedForward modules around ops.AgentWindowAttention (the forward kernel +
+    heal_agent_window_attention_backward per scene; no [groups, heads, T, T] tensor is kept for the backward);
   * inference on the device: one scene token-major [L, H, W, C] through all blocks.  Each attention half-block is heal_ln_stats ->
     heal_linear (LayerNorm folded, 256 -> 768) -> heal_agent_window_attention (window or grid grouping, per-head 3-D relative
     position bias, keys of padded agents skipped) -> heal_linear (to_out + x); each feed-forward is two heal_linear launches
@@ -58,6 +61,8 @@ def _relative_position_index(agent_size, window_size):
 
 
 class Attention(nn.Module):
+    grad_kernel = False     # True: under autograd on the device the attention core is ops.AgentWindowAttention (SwapFusionBlockMask)
+
     def __init__(self, dim, dim_head=32, dropout=0.0, agent_size=6, window_size=7):
         super().__init__()
         assert dim % dim_head == 0, "dimension should be divisible by dimension per head"
@@ -97,6 +102,24 @@ class Attention(nn.Module):
         return derived("agent_window_position_bias", (tab, self.relative_position_index),
                        lambda: tab.detach()[self.relative_position_index].permute(2, 0, 1).contiguous().float())
 
+    def grad_kernel_ok(self, x):
+        """The opt-in device gradient path takes x [b, L, C, H, W]: grad_kernel set, autograd recording, CUDA fp32 and a shape
+        heal_agent_window_attention_backward takes."""
+        if not (self.grad_kernel and x.is_cuda and x.dtype == torch.float32 and _grad_path(x, self) and x.dim() == 5):
+            return False
+        b, L, C, H, W = x.shape
+        return C == self.heads * self.dim_head and ops.agent_window_attention_train_supported(L, self.window_size[1], self.dim_head,
+                                                                                              H, W)
+
+    def kernel_residual(self, x, norm, n_valid, mode):
+        """x token-major [b, L, H, W, C] -> to_out(attention(to_qkv(norm(x)))) + x under autograd: the torch modules around
+        ops.AgentWindowAttention per scene.  The bias is looked up from the table through autograd: its gradient reaches the table."""
+        qkv = self.to_qkv(norm(x))
+        bias = self.relative_position_bias_table(self.relative_position_index).permute(2, 0, 1).contiguous()
+        att = torch.stack([ops.AgentWindowAttention.apply(qkv[i], bias, n_valid[i], mode, self.heads, self.dim_head,
+                                                          self.window_size[1], self.scale) for i in range(x.shape[0])])
+        return self.to_out(att) + x
+
     def fused_residual(self, x, norm, n_valid, mode):
         """x token-major [L, H, W, C] -> x + to_out(attention(norm(x))): LayerNorm folded into the 256 -> 768 heal_linear, the
         agent-window kernel writing [L, H, W, C], to_out + x in the epilogue of the second heal_linear."""
@@ -111,6 +134,18 @@ class Attention(nn.Module):
         return derived("fold_ln", (self.to_qkv.weight, None, norm.weight, norm.bias), lambda: _fold_ln(self.to_qkv.weight, None, norm))
 
 
+def _prefix_counts(key_mask, b, m):
+    """key_mask [b, m] (nonzero = real agent) -> the number of real agents of every scene, or None when a mask is not a non-empty
+    prefix of the agents (the kernels mask the trailing agents; Regroup pads at the end).  Reads the mask on the host."""
+    if key_mask is None:
+        return [m] * b
+    rows = (key_mask != 0).tolist()
+    counts = [sum(r) for r in rows]
+    if any(n < 1 or r != [True] * n + [False] * (m - n) for r, n in zip(rows, counts)):
+        return None
+    return counts
+
+
 class SwapFusionBlockMask(nn.Module):
     def __init__(self, input_dim, mlp_dim, dim_head, window_size, agent_size, drop_out):
         super().__init__()
@@ -123,6 +158,10 @@ class SwapFusionBlockMask(nn.Module):
     def forward(self, x, key_mask):
         """x [b, m, d, H, W], key_mask [b, m] -> [b, m, d, H, W] (swap_fusion_modules.py:135-152)."""
         b, m, d, H, W = x.shape
+        if self.window_attention.fn.grad_kernel_ok(x) and self.grid_attention.fn.grad_kernel_ok(x):
+            n_valid = _prefix_counts(key_mask, b, m)
+            if n_valid is not None:
+                return self.grad_kernel_forward(x, n_valid)
         ws = self.window_size
         X, Y = H // ws, W // ws
         # 'b m d (x w1) (y w2) -> b m x y w1 w2 d'
@@ -135,6 +174,16 @@ class SwapFusionBlockMask(nn.Module):
         x = self.grid_attention(x, key_mask=key_mask)
         x = self.grid_ffd(x)
         return x.permute(0, 1, 6, 4, 2, 5, 3).reshape(b, m, d, H, W)
+
+    def grad_kernel_forward(self, x, n_valid):
+        """The same block under autograd with the attention kernels: token-major [b, m, H, W, d] through both half-blocks and
+        both feed-forwards, permuted back so that the caller sees [b, m, d, H, W]."""
+        x = x.permute(0, 1, 3, 4, 2).contiguous()
+        x = self.window_attention.fn.kernel_residual(x, self.window_attention.norm, n_valid, "window")
+        x = self.window_ffd(x)
+        x = self.grid_attention.fn.kernel_residual(x, self.grid_attention.norm, n_valid, "grid")
+        x = self.grid_ffd(x)
+        return x.permute(0, 1, 4, 2, 3)
 
     def fused(self, x, n_valid):
         """The same block on one scene token-major [L, H, W, C] (inference on the device)."""

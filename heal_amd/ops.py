@@ -1278,6 +1278,81 @@ def agent_window_attention(qkv, bias, n_valid, mode, heads, dim_head, window, sc
     return out
 
 
+def agent_window_attention_train_supported(n_agents, window, dim_head, H, W):
+    """The shapes heal_agent_window_attention_backward takes (the forward's): the device gradient path of agent_window_attention
+    (ops.AgentWindowAttention) for fp32 CUDA tensors."""
+    return bool(agent_window_attention_supported(n_agents, window, dim_head, H, W)
+                and _capi.lib().heal_agent_window_attention_backward_supported(int(n_agents), int(window), int(dim_head), int(H), int(W)))
+
+
+def agent_window_attention_backward(qkv, bias, grad_out, n_valid, mode, heads, dim_head, window, scale, parts=None):
+    """Backward of agent_window_attention (heal_agent_window_attention_backward): qkv / bias / n_valid / mode as in the forward,
+    grad_out like the forward's result -> (grad_qkv like qkv, grad_bias [heads,T,T] | None).  The forward's result itself is not
+    needed: the kernel recomputes the probabilities and forms the softmax gradient's row term from them.  Masked agents' dK / dV
+    rows and grad_bias columns are exact zeros.  parts: into how many ranges the groups are cut for the deterministic grad_bias sum
+    (None: the library's policy)."""
+    who = "agent_window_attention_backward"
+    qkv = _need(qkv, torch.float32, "qkv"); grad_out = _need(grad_out, torch.float32, "grad_out")
+    if qkv.dim() != 4:
+        raise _capi.HealAmdError(f"{who}: qkv must be [L,H,W,3*heads*dim_head]")
+    L, H, W, C3 = (int(v) for v in qkv.shape)
+    if mode not in _AGENT_WINDOW_MODES:
+        raise _capi.HealAmdError(f"{who}: mode must be 'window' or 'grid', got {mode!r}")
+    if C3 != 3 * heads * dim_head or not agent_window_attention_train_supported(L, window, dim_head, H, W):
+        raise _capi.HealAmdError(f"{who}: unsupported shape ({L} agents, window {window}, dim_head {dim_head}, map {H}x{W})")
+    inner = heads * dim_head
+    if tuple(grad_out.shape) != (L, H, W, inner):
+        raise _capi.HealAmdError(f"{who}: grad_out must be [L,H,W,heads*dim_head] = [{L}, {H}, {W}, {inner}]")
+    if grad_out.device != qkv.device:
+        raise _capi.HealAmdError(f"{who}: qkv and grad_out must be on one device")
+    n_valid = int(n_valid)
+    if not 1 <= n_valid <= L:
+        raise _capi.HealAmdError(f"{who}: n_valid {n_valid} outside 1..{L}")
+    T = L * window * window
+    G = (H // window) * (W // window)
+    parts = 0 if parts is None else int(parts)
+    if parts and not 1 <= parts <= G:
+        raise _capi.HealAmdError(f"{who}: parts {parts} outside 1..{G} (the groups)")
+    grad_bias, ws, need = None, None, 0
+    if bias is not None:
+        bias = _need(bias, torch.float32, "bias")
+        if tuple(bias.shape) != (heads, T, T) or bias.device != qkv.device:
+            raise _capi.HealAmdError(f"{who}: bias must be [heads, T, T] = [{heads}, {T}, {T}] on the device of qkv")
+        grad_bias = torch.empty_like(bias)
+        need = _capi.query("heal_agent_window_attention_backward_workspace", L, H, W, int(heads), parts)
+        ws = _workspace("agent_window_attention_bwd", need, qkv.device) if need else None
+    grad_qkv = torch.empty_like(qkv)
+    # per query token: 7 products over the n_valid * window^2 unmasked keys (S and dP in both phases, dQ, dK, dV) = 14 n_valid
+    # window^2 inner FLOPs; q | k | v and grad_out read + grad_qkv written = 28 inner bytes
+    with _Timed(f"agent_window_attention_backward_{mode}", flops=14.0 * L * H * W * n_valid * window * window * inner,
+                nbytes=28.0 * L * H * W * inner):
+        _capi.call("heal_agent_window_attention_backward", _ptr(qkv), _optr(bias), _ptr(grad_out), L, n_valid, H, W,
+                   int(heads), int(dim_head), int(window), _AGENT_WINDOW_MODES[mode], float(scale), parts, _ptr(grad_qkv),
+                   _optr(grad_bias), _optr(ws), need, _stream())
+    return grad_qkv, grad_bias
+
+
+class AgentWindowAttention(torch.autograd.Function):
+    """agent_window_attention under autograd: forward = heal_agent_window_attention, backward =
+    heal_agent_window_attention_backward (saves qkv and the bias; the T x T probabilities are recomputed per group and the
+    output is not needed again)."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias, n_valid, mode, heads, dim_head, window, scale):
+        qkv = qkv.contiguous()
+        bias = bias.contiguous() if bias is not None else None
+        out = agent_window_attention(qkv, bias, n_valid, mode, heads, dim_head, window, scale)
+        ctx.save_for_backward(qkv, bias)
+        ctx.cfg = (int(n_valid), mode, int(heads), int(dim_head), int(window), float(scale))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        qkv, bias = ctx.saved_tensors
+        gq, gb = agent_window_attention_backward(qkv, bias, grad_out.contiguous(), *ctx.cfg)
+        return gq, gb, None, None, None, None, None, None
+
+
 def agent_mean(x):
     """x [L, ...] f32 -> mean over the first dimension [...] (heal_agent_mean; sums in agent order)."""
     x = _need(x, torch.float32, "x")
