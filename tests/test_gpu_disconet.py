@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from heal_amd import _capi, ops
+from tests.backward_refs import shift_rows          # noqa: F401  (tests/test_gpu_where2comm.py imports it from here)
 from tests.golden.disco_fill import fill_disco
 from tests.test_disconet_cpu import CASES, E2E_RANGE, TOL, case_inputs, e2e_data, e2e_hypes, make_disco, rel_err
 
@@ -21,13 +22,6 @@ W4_SCALE = 2.0 ** -6          # conv1_4's weights are +-2^-6: a power of two kee
 
 def _ints(gen, shape, lo, hi):
     return torch.randint(lo, hi + 1, shape, generator=gen).float()
-
-
-def shift_rows(shifts, H, W):
-    """Normalised affine rows (fp64) of pure translations by (sx, sy) pixels: the sample of ego pixel (y, x) is taken at
-    (y + sy, x + sx).  With H and W powers of two and shifts that are multiples of 1/2, the sampling coordinates and the bilinear
-    weights (0, 1/4, 1/2, 1) are exact in the kernel's arithmetic."""
-    return np.array([[[1.0, 0.0, 2.0 * sx / W], [0.0, 1.0, 2.0 * sy / H]] for sx, sy in shifts], dtype=np.float64)
 
 
 def disco_fixture(n, C, H, W, seed, equal=False):
