@@ -1197,17 +1197,26 @@ def window_attention(qkv, pos_bias, heads, dim_head, window, scale, out=None):
     return out
 
 
-def window_attention_backward(qkv, pos_bias, out, grad_out, heads, dim_head, window, scale):
-    """Backward of window_attention -> (grad_qkv like qkv, grad_bias [T,T] | None).  Unmeasured so far: the modules use it only
-    under HEAL_WATTN_GRAD=kernel."""
+def window_attention_backward(qkv, pos_bias, out, grad_out, heads, dim_head, window, scale, grad_qkv=None):
+    """Backward of window_attention -> (grad_qkv like qkv, grad_bias [T,T] | None); `out` is the forward's result.  grad_qkv is
+    written into the caller's buffer when given.  Unmeasured so far: the modules use it only under HEAL_WATTN_GRAD=kernel."""
+    who = "window_attention_backward"
     qkv = _need(qkv, torch.float32, "qkv"); out = _need(out, torch.float32, "out"); grad_out = _need(grad_out, torch.float32, "grad_out")
+    if qkv.dim() != 4:
+        raise _capi.HealAmdError(f"{who}: qkv must be [L,H,W,3*heads*dim_head], got {tuple(qkv.shape)}")
     L, H, W, C3 = (int(v) for v in qkv.shape)
     if C3 != 3 * heads * dim_head or not window_attention_supported(window, dim_head, H, W):
-        raise _capi.HealAmdError(f"window_attention_backward: unsupported shape (window {window}, dim_head {dim_head}, map {H}x{W})")
-    grad_qkv = torch.empty_like(qkv)
+        raise _capi.HealAmdError(f"{who}: unsupported shape (window {window}, dim_head {dim_head}, map {H}x{W})")
+    # the kernels read a [L,H,W,heads*dim_head] row per token of `out` and `grad_out`, and window^4 bias words, from bare pointers
+    for name, t in (("out", out), ("grad_out", grad_out)):
+        if tuple(t.shape) != (L, H, W, heads * dim_head):
+            raise _capi.HealAmdError(f"{who}: {name} has shape {tuple(t.shape)}, want {(L, H, W, heads * dim_head)}")
+    grad_qkv = _out_or_empty(grad_qkv, tuple(qkv.shape), qkv.device, who)
     grad_bias = None
     if pos_bias is not None:
         pos_bias = _need(pos_bias, torch.float32, "pos_bias")
+        if tuple(pos_bias.shape) != (window * window, window * window):
+            raise _capi.HealAmdError(f"{who}: pos_bias must be [window^2, window^2], got {tuple(pos_bias.shape)}")
         grad_bias = torch.zeros_like(pos_bias)
     need = _capi.query("heal_window_attention_backward_workspace", L, H, W, int(heads))
     ws = _workspace("window_attention_bwd", need, qkv.device)
@@ -2075,40 +2084,60 @@ def sp_transpose_neighbors(nbr, n_in):
 
 
 # ------------------------------------------------------------------------------------------------ K6
-def agent_attention(q, k, v, heads, scale, key_mask=None, out_rows=None, agent_major=False):
-    """K6.  q,k,v [n_pix, L, 256] f32 cuda -> [n_pix, out_rows, 256] (softmax over the L agents per
-    pixel and head; key_mask [L] int32 cuda marks real agents).  agent_major: q, k, v [L, n_pix, 256] -> [out_rows, n_pix, 256]."""
+def _agent_attention_args(who, q, k, v, key_mask, agent_major):
+    """q, k, v [n_pix, L, 256] (or [L, n_pix, 256]) f32 cuda of ONE shape and key_mask [L] int32 cuda, made contiguous: the kernels
+    read L rows of 256 floats per pixel from each of the three and L mask words from bare pointers, so a `v` with fewer pixels
+    or a short mask would be read out of bounds without an error.  -> (q, k, v, key_mask, n_pix, L)"""
     q = _need(q, torch.float32, "q"); k = _need(k, torch.float32, "k"); v = _need(v, torch.float32, "v")
-    if agent_major:
-        L, n_pix, C = (int(x) for x in q.shape)
-    else:
-        n_pix, L, C = (int(x) for x in q.shape)
-    rows = L if out_rows is None else int(out_rows)
-    out = torch.empty((rows, n_pix, C) if agent_major else (n_pix, rows, C), dtype=torch.float32, device=q.device)
+    if q.dim() != 3 or int(q.shape[2]) != 256:
+        raise _capi.HealAmdError(f"{who}: q has shape {tuple(q.shape)}, want [n_pix, L, 256] ([L, n_pix, 256] agent-major): "
+                                 "the last dimension must be 256")
+    for name, t in (("k", k), ("v", v)):
+        if tuple(t.shape) != tuple(q.shape):
+            raise _capi.HealAmdError(f"{who}: {name} has shape {tuple(t.shape)}, q has {tuple(q.shape)}")
+    L, n_pix = (int(q.shape[0]), int(q.shape[1])) if agent_major else (int(q.shape[1]), int(q.shape[0]))
+    if not 1 <= L <= AGENT_ATTENTION_MAX_AGENTS:
+        raise _capi.HealAmdError(f"{who}: {L} agents, the kernel takes 1..{AGENT_ATTENTION_MAX_AGENTS}")
     if key_mask is not None:
         key_mask = _need(key_mask, torch.int32, "key_mask")
+        if key_mask.numel() != L:
+            raise _capi.HealAmdError(f"{who}: key_mask has {key_mask.numel()} entries for {L} agents")
+    return q, k, v, key_mask, n_pix, L
+
+
+def agent_attention(q, k, v, heads, scale, key_mask=None, out_rows=None, agent_major=False, out=None):
+    """K6.  q,k,v [n_pix, L, 256] f32 cuda -> [n_pix, out_rows, 256] (softmax over the L agents per
+    pixel and head; key_mask [L] int32 cuda marks real agents).  agent_major: q, k, v [L, n_pix, 256] -> [out_rows, n_pix, 256].
+    The result is written into `out` when given."""
+    who = "agent_attention"
+    q, k, v, key_mask, n_pix, L = _agent_attention_args(who, q, k, v, key_mask, agent_major)
+    rows = L if out_rows is None else int(out_rows)
+    if not 1 <= rows <= L:
+        raise _capi.HealAmdError(f"{who}: out_rows {rows} outside 1..{L}")
+    out = _out_or_empty(out, (rows, n_pix, 256) if agent_major else (n_pix, rows, 256), q.device, who)
     with _Timed(f"agent_attention_h{heads}"):
-        _capi.call("heal_agent_attention", _ptr(q), _ptr(k), _ptr(v), _optr(key_mask), n_pix, L, C, int(heads),
+        _capi.call("heal_agent_attention", _ptr(q), _ptr(k), _ptr(v), _optr(key_mask), n_pix, L, 256, int(heads),
                    float(scale), rows, _ptr(out), int(bool(agent_major)), _stream())
     return out
 
 
-def agent_attention_backward(q, k, v, grad_out, heads, scale, key_mask=None, agent_major=False):
+def agent_attention_backward(q, k, v, grad_out, heads, scale, key_mask=None, agent_major=False, grads=None):
     """Backward of agent_attention: grad_out [n_pix, out_rows, 256] (or [out_rows, n_pix, 256]) -> (grad_q, grad_k, grad_v), each
-    shaped like q.  Rows >= out_rows of the forward output were not produced and carry no gradient."""
-    q = _need(q, torch.float32, "q"); k = _need(k, torch.float32, "k"); v = _need(v, torch.float32, "v")
+    shaped like q (written into the three buffers of `grads` when given).  Rows >= out_rows of the forward output were not
+    produced and carry no gradient."""
+    who = "agent_attention_backward"
+    q, k, v, key_mask, n_pix, L = _agent_attention_args(who, q, k, v, key_mask, agent_major)
     grad_out = _need(grad_out, torch.float32, "grad_out")
-    if agent_major:
-        L, n_pix, C = (int(x) for x in q.shape)
-        rows = int(grad_out.shape[0])
-    else:
-        n_pix, L, C = (int(x) for x in q.shape)
-        rows = int(grad_out.shape[1])
-    if key_mask is not None:
-        key_mask = _need(key_mask, torch.int32, "key_mask")
-    gq, gk, gv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+    rows = int(grad_out.shape[0 if agent_major else 1]) if grad_out.dim() == 3 else 0
+    if not 1 <= rows <= L:
+        raise _capi.HealAmdError(f"{who}: grad_out has shape {tuple(grad_out.shape)}: its out_rows must be in 1..{L}")
+    if tuple(grad_out.shape) != ((rows, n_pix, 256) if agent_major else (n_pix, rows, 256)):
+        raise _capi.HealAmdError(f"{who}: grad_out has shape {tuple(grad_out.shape)} for q of shape {tuple(q.shape)}")
+    if grads is None:
+        grads = (None, None, None)
+    gq, gk, gv = (_out_or_empty(g, tuple(q.shape), q.device, who) for g in grads)
     with _Timed(f"agent_attention_bwd_h{heads}"):
-        _capi.call("heal_agent_attention_backward", _ptr(q), _ptr(k), _ptr(v), _optr(key_mask), _ptr(grad_out), n_pix, L, C,
+        _capi.call("heal_agent_attention_backward", _ptr(q), _ptr(k), _ptr(v), _optr(key_mask), _ptr(grad_out), n_pix, L, 256,
                    int(heads), float(scale), rows, _ptr(gq), _ptr(gk), _ptr(gv), int(bool(agent_major)), _stream())
     return gq, gk, gv
 
