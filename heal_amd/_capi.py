@@ -17,6 +17,7 @@ HEADER_EXPERIMENTAL = os.path.join(os.path.dirname(HERE), "include", "heal_amd_e
 HEADER_TRAIN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train.h")
 HEADER_EXT = os.path.join(os.path.dirname(HERE), "include", "heal_amd_ext.h")
 HEADER_TRAIN_ATTN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train_attn.h")
+HEADER_TRAIN_BN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train_bn.h")
 
 _lib = None
 
@@ -100,6 +101,15 @@ def signatures_train_attn():
         return parse_prototypes(f.read())
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_train_bn():
+    """{name: (restype, argtypes)} of include/heal_amd_train_bn.h: the gradient path's fused BatchNorm (+ residual) (+ ReLU) --
+    batch statistics, apply and backward.  Every build exports them; like signatures_train() they are outside the versioned
+    inference ABI."""
+    with open(HEADER_TRAIN_BN) as f:
+        return parse_prototypes(f.read())
+
+
 def declared_symbols(experimental=False):
     """Function names declared in include/heal_amd.h (the shipped C ABI), or with experimental=True in
     include/heal_amd_experimental.h."""
@@ -132,7 +142,8 @@ def lib():
         # process do not share devices, streams or allocations).
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**signatures(), **signatures_train(), **signatures_ext(), **signatures_train_attn()}.items():
+        for name, (res, args) in {**signatures(), **signatures_train(), **signatures_ext(), **signatures_train_attn(),
+                                  **signatures_train_bn()}.items():
             if not hasattr(L, name):
                 continue  # declared but not built yet -> surfaces in call() / the symbol test
             f = getattr(L, name)

@@ -71,6 +71,7 @@ def _deps():
     hdrs.append(os.path.join(inc, "heal_amd_train.h"))      # the training-side entry points: part of every build
     hdrs.append(os.path.join(inc, "heal_amd_ext.h"))        # inference entry points outside the versioned table: part of every build
     hdrs.append(os.path.join(inc, "heal_amd_train_attn.h"))  # the agent-window attention backward: part of every build
+    hdrs.append(os.path.join(inc, "heal_amd_train_bn.h"))   # the gradient path's BatchNorm + residual + ReLU: part of every build
     if EXPERIMENTAL:
         hdrs.append(os.path.join(inc, "heal_amd_experimental.h"))
     return hdrs

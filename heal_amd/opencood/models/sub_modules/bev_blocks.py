@@ -7,7 +7,8 @@ downsample_conv.py:7-49, feature_alignnet.py:12-39, feature_alignnet_modules.py:
 naive_compress.py:5-31.
 
 Training / fine-tuning (gradients enabled, see `grad_path`): the blocks run conv -> BatchNorm -> ReLU as torch modules with
-autograd; under HEAL_CONV_GRAD=kernel the dense 3x3 / 1x1 convolutions among them run as ops.ConvGrad (`grad_conv`).
+autograd; under HEAL_CONV_GRAD=kernel the dense 3x3 / 1x1 convolutions among them run as ops.ConvGrad (`grad_conv`), and in
+ops.bn_grad("kernel") mode BatchNorm (+ residual) (+ ReLU) runs as ops.BatchNormAct (`grad_bn_act`).
 Inference design (eval mode): every Conv+BatchNorm pair is folded into one convolution with bias
 (heal_amd.derived: re-folded when a parameter changes), ReLU and the residual add run in place -- one pass
 over each BEV map instead of three.  Pointwise, dense 3x3 (padding 1, stride 1 | 2) and 32-group 3x3 convolutions run on
@@ -137,6 +138,31 @@ def grad_conv(conv, x, padding=None):
     return conv(x)
 
 
+def grad_bn_act(bn, x, relu, residual=None):
+    """[relu](bn(x) (+ residual)) on the gradient path.  In ops.bn_grad("kernel") mode a plain affine nn.BatchNorm2d that tracks
+    running statistics with a fixed momentum, on a contiguous fp32 device map outside autocast, runs as ops.BatchNormAct: batch
+    statistics (when training), apply and backward on this library's kernels, one autograd node instead of three.  Everything else
+    (the default mode, CPU tensors, other dtypes, SyncBatchNorm and other subclasses, no affine / no running statistics / cumulative
+    momentum, a single-element channel in training) evaluates the modules' expressions exactly as before."""
+    from heal_amd import ops
+    if (ops.bn_grad_enabled() and type(bn) is nn.BatchNorm2d and bn.affine and bn.track_running_stats and bn.momentum is not None
+            and torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous()
+            and bn.weight.dtype == torch.float32 and not torch.is_autocast_enabled()
+            and (not bn.training or x.shape[0] * x.shape[2] * x.shape[3] >= 2)
+            and (residual is None or (torch.is_tensor(residual) and residual.shape == x.shape and residual.device == x.device
+                                      and residual.dtype == torch.float32 and residual.is_contiguous()))
+            and ops.bn_train_supported(x)):
+        if bn.training:
+            bn.num_batches_tracked.add_(1)
+        return ops.BatchNormAct.apply(x, residual, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training,
+                                      bn.momentum, bn.eps, relu)
+    ops.BN_GRAD_CALLS["module"] += 1
+    y = bn(x)
+    if residual is not None:
+        y = y + residual
+    return F.relu(y) if relu else y
+
+
 def _require_eval(module):
     """For the operators that still have no gradient path (the sparse 3-D encoder K3)."""
     if module.training and torch.is_grad_enabled():
@@ -160,10 +186,7 @@ class ConvBN(nn.Module):
         if out is not None:      # gradient path with a destination (CPU tests of the stage walks): compute, then copy
             return out.copy_(ConvBN.run(x, conv, bn, relu, residual))
         if grad_path(x, bn, conv):   # training / fine-tuning: conv -> BatchNorm (batch statistics when training) -> + -> ReLU
-            y = bn(grad_conv(conv, x))
-            if residual is not None:
-                y = y + residual
-            return F.relu(y) if relu else y
+            return grad_bn_act(bn, grad_conv(conv, x), relu, residual)
         w, b = fold_bn(conv, bn)
         return conv_bias_act(x, w, b, conv.stride, conv.padding, conv.dilation, conv.groups, relu, residual)
 
@@ -388,7 +411,7 @@ class _Deblock(nn.Sequential):
 
     def _forward(self, x, into=None):
         if grad_path(x, self):
-            return super().forward(x)   # (transposed) conv -> BatchNorm -> ReLU as torch modules
+            return grad_bn_act(self[1], self[0](x), True)   # (transposed) conv as a torch module -> BatchNorm -> ReLU
         conv, bn = self[0], self[1]
         from heal_amd import ops
         if isinstance(conv, nn.ConvTranspose2d):

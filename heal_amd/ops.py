@@ -3305,6 +3305,211 @@ class ConvGrad(torch.autograd.Function):
         return dx, dw, db, None
 
 
+# ------------------------------------------------------------------------------- BatchNorm + residual + ReLU of the gradient path
+_BN_GRAD_MODES = ("torch", "kernel")
+_BN_GRAD_MODE = "torch"
+
+
+class bn_grad:
+    """ops.bn_grad("kernel"): the BatchNorm2d (+ residual) (+ ReLU) sites of the gradient path (bev_blocks.grad_bn_act) run as
+    ops.BatchNormAct on this library's kernels; ops.bn_grad("torch") (the default): the library composition.  A plain setter --
+    the mode is set when the object is made -- and a context manager, which puts the previous mode back on exit:
+        ops.bn_grad("kernel")                 # from here on
+        with ops.bn_grad("kernel"): ...       # for the block
+    A process-wide Python setting, deliberately not an environment switch."""
+
+    def __init__(self, mode):
+        global _BN_GRAD_MODE
+        if mode not in _BN_GRAD_MODES:
+            raise ValueError(f"bn_grad: mode must be one of {_BN_GRAD_MODES}, got {mode!r}")
+        self.previous = _BN_GRAD_MODE
+        _BN_GRAD_MODE = mode
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        global _BN_GRAD_MODE
+        _BN_GRAD_MODE = self.previous
+        return False
+
+
+def bn_grad_enabled():
+    """True in ops.bn_grad("kernel") mode."""
+    return _BN_GRAD_MODE == "kernel"
+
+
+# what bev_blocks.grad_bn_act ran since the process started (tests and scripts/bn_grad_bench.py read it): BatchNormAct forwards and
+# backwards, and sites left to the torch modules (the default mode, CPU tensors, other dtypes, BatchNorms the kernels do not take)
+BN_GRAD_CALLS = {"forward": 0, "backward": 0, "module": 0}
+
+
+def _bn_shape(x):
+    """(n, C, HW) of a 4-D map, else None."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        return None
+    n, C, H, W = (int(v) for v in x.shape)
+    return (n, C, H * W) if H * W < 2 ** 31 else None
+
+
+def bn_train_supported(x):
+    """True if the BatchNorm training kernels take the map: a contiguous f32 device tensor [n, C, H, W] within the index ranges of
+    heal_bn_train_supported.  No alignment or divisibility requirement."""
+    shape = _bn_shape(x)
+    return (shape is not None and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and min(shape) >= 1
+            and bool(_capi.lib().heal_bn_train_supported(*shape)))
+
+
+def _bn_map(t, name, who, like=None):
+    """A contiguous f32 device map; `like`: the map whose shape and device it must share.  Nothing is copied or converted."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _capi.HealAmdError(f"{who}: {name} must be a CUDA/HIP tensor (heal_amd has no CPU path)")
+    if t.dtype != torch.float32:
+        raise _capi.HealAmdError(f"{who}: {name} must have dtype torch.float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise _capi.HealAmdError(f"{who}: {name} must be contiguous")
+    if like is None:
+        if not bn_train_supported(t):
+            raise _capi.HealAmdError(f"{who}: {name} of shape {tuple(t.shape)} is not a supported [n, C, H, W] map")
+    elif t.shape != like.shape or t.device != like.device:
+        raise _capi.HealAmdError(f"{who}: {name} has shape {tuple(t.shape)} on {t.device}, want {tuple(like.shape)} on {like.device}")
+    return t
+
+
+def _bn_vec(t, C, name, who, like):
+    """A contiguous f32 vector of C values on the device of `like`."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != like.device:
+        raise _capi.HealAmdError(f"{who}: {name} must be a CUDA/HIP tensor on the device of the map")
+    if t.dtype != torch.float32:
+        raise _capi.HealAmdError(f"{who}: {name} must have dtype torch.float32, got {t.dtype}")
+    if tuple(t.shape) != (C,) or not t.is_contiguous():
+        raise _capi.HealAmdError(f"{who}: {name} has shape {tuple(t.shape)}, want a contiguous [{C}]")
+    return t
+
+
+def _bn_workspace(x, shape):
+    need = _capi.query("heal_bn_train_workspace", *shape)
+    return _workspace("bn_train", need, x.device), need
+
+
+def bn_stats(x, eps, momentum=0.0, running_mean=None, running_var=None, out=None):
+    """Batch statistics of x [n, C, H, W] (heal_bn_stats) -> (mean [C], rstd [C]) with rstd = 1 / sqrt(biased variance + eps), from
+    fp64 sums, each rounded once.  running_mean / running_var (both or neither) are updated in place as nn.BatchNorm2d does
+    (momentum; the unbiased variance).  out: optional (mean, rstd) destinations."""
+    who = "bn_stats"
+    x = _bn_map(x, "x", who)
+    n, C, HW = shape = _bn_shape(x)
+    if (running_mean is None) != (running_var is None):
+        raise _capi.HealAmdError(f"{who}: running_mean and running_var go together")
+    if running_mean is not None:
+        _bn_vec(running_mean, C, "running_mean", who, x)
+        _bn_vec(running_var, C, "running_var", who, x)
+        if n * HW < 2:
+            raise _capi.HealAmdError(f"{who}: the unbiased variance of the running statistics needs n * H * W >= 2, got {n * HW}")
+    if not float(eps) >= 0.0:
+        raise _capi.HealAmdError(f"{who}: eps must not be negative, got {eps}")
+    mean, rstd = out if out is not None else (torch.empty(C, dtype=torch.float32, device=x.device) for _ in range(2))
+    _bn_vec(mean, C, "out[0]", who, x)
+    _bn_vec(rstd, C, "out[1]", who, x)
+    ws, need = _bn_workspace(x, shape)
+    with _Timed("bn_stats", 3.0 * x.numel(), 4.0 * x.numel()):
+        _capi.call("heal_bn_stats", _ptr(x), n, C, HW, float(eps), float(momentum), _ptr(mean), _ptr(rstd), _optr(running_mean),
+                   _optr(running_var), _ptr(ws), need, _stream())
+    return mean, rstd
+
+
+def bn_act_forward(x, residual, mean, rstd, gamma, beta, relu, out=None):
+    """y = [relu]((x - mean) * rstd * gamma + beta (+ residual)) per channel of x [n, C, H, W] (heal_bn_act_forward).  mean / rstd:
+    bn_stats' or a frozen BatchNorm's running mean and 1 / sqrt(running_var + eps).  out: optional destination like x."""
+    who = "bn_act_forward"
+    x = _bn_map(x, "x", who)
+    n, C, HW = _bn_shape(x)
+    if residual is not None:
+        _bn_map(residual, "residual", who, x)
+    for t, name in ((mean, "mean"), (rstd, "rstd"), (gamma, "gamma"), (beta, "beta")):
+        _bn_vec(t, C, name, who, x)
+    y = _bn_map(out, "out", who, x) if out is not None else torch.empty_like(x)
+    maps = 2 + (residual is not None)
+    with _Timed("bn_act_forward", 4.0 * x.numel(), 4.0 * maps * x.numel(), kernel_events=True):
+        _capi.call("heal_bn_act_forward", _ptr(x), _optr(residual), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), n, C, HW,
+                   int(bool(relu)), _ptr(y), _stream())
+    return y
+
+
+def bn_act_backward(dy, x, y, mean, rstd, gamma, relu, batch_stats, want=(True, True, True, True), out=None):
+    """Backward of bn_act_forward (heal_bn_act_backward) -> (dx, dresidual, dgamma, dbeta), None where `want` (four flags in that
+    order) does not ask for one.  y: the forward's result, needed exactly when relu (the mask is y > 0).  batch_stats: the
+    statistics were the batch's own (the gradient flows through them) | frozen.  out: optional destinations, a 4-tuple with None
+    where the wrapper shall allocate."""
+    who = "bn_act_backward"
+    x = _bn_map(x, "x", who)
+    n, C, HW = shape = _bn_shape(x)
+    _bn_map(dy, "dy", who, x)
+    if bool(relu) != (y is not None):
+        raise _capi.HealAmdError(f"{who}: y (the forward's result) is required exactly when relu is set")
+    if y is not None:
+        _bn_map(y, "y", who, x)
+    for t, name in ((mean, "mean"), (rstd, "rstd"), (gamma, "gamma")):
+        _bn_vec(t, C, name, who, x)
+    want = tuple(bool(w) for w in want)
+    if len(want) != 4:
+        raise _capi.HealAmdError(f"{who}: want must hold four flags (dx, dresidual, dgamma, dbeta)")
+    out = tuple(out) if out is not None else (None,) * 4
+    res = []
+    for i, name in enumerate(("dx", "dresidual", "dgamma", "dbeta")):
+        t = out[i] if want[i] else None
+        if want[i] and t is None:
+            t = torch.empty_like(x) if i < 2 else torch.empty(C, dtype=torch.float32, device=x.device)
+        elif t is not None:
+            t = _bn_map(t, f"out[{name}]", who, x) if i < 2 else _bn_vec(t, C, f"out[{name}]", who, x)
+        res.append(t)
+    if not any(want):
+        return tuple(res)
+    ws, need = _bn_workspace(x, shape)
+    reads = (2 + bool(relu)) * ((want[2] or want[3] or (batch_stats and want[0])) + (want[0] or want[1]))
+    with _Timed("bn_act_backward", 8.0 * x.numel(), 4.0 * (reads + want[0] + want[1]) * x.numel()):
+        _capi.call("heal_bn_act_backward", _ptr(dy), _ptr(x), _optr(y), _ptr(mean), _ptr(rstd), _ptr(gamma), n, C, HW,
+                   int(bool(relu)), int(bool(batch_stats)), _optr(res[0]), _optr(res[1]), _optr(res[2]), _optr(res[3]), _ptr(ws), need,
+                   _stream())
+    return tuple(res)
+
+
+class BatchNormAct(torch.autograd.Function):
+    """BatchNorm2d (+ residual) (+ ReLU) under autograd on this library's kernels:
+    apply(x, residual | None, bn_weight, bn_bias, running_mean, running_var, training, momentum, eps, relu)
+        -> [relu](batch_norm(x) (+ residual)).
+    training: heal_bn_stats (the running buffers are updated in place) then heal_bn_act_forward; otherwise heal_bn_act_forward from
+    the running statistics.  Saves x, y (only with relu), mean, rstd and the weight -- what the composition holds.  Backward: one
+    heal_bn_act_backward call for the gradients that are needed; without ReLU the residual's gradient is grad_out itself."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, running_mean, running_var, training, momentum, eps, relu):
+        if training:
+            mean, rstd = bn_stats(x, eps, momentum, running_mean, running_var)
+        else:
+            mean, rstd = running_mean, 1.0 / torch.sqrt(running_var + eps)      # F.batch_norm's own expression
+        y = bn_act_forward(x, residual, mean, rstd, weight, bias, relu)
+        ctx.save_for_backward(x, y if relu else None, mean, rstd, weight)
+        ctx.cfg = (bool(relu), bool(training), residual is not None)
+        BN_GRAD_CALLS["forward"] += 1
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, y, mean, rstd, weight = ctx.saved_tensors
+        relu, training, has_res = ctx.cfg
+        grad_out = grad_out.contiguous()
+        need = ctx.needs_input_grad
+        want_res = has_res and need[1]
+        dx, dres, dgamma, dbeta = bn_act_backward(grad_out, x, y, mean, rstd, weight, relu, training,
+                                                  want=(need[0], want_res and relu, need[2], need[3]))
+        if want_res and not relu:
+            dres = grad_out
+        BN_GRAD_CALLS["backward"] += 1
+        return dx, dres, dgamma, dbeta, None, None, None, None, None, None
+
+
 def channel_dot_supported(x):
     return x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and int(x.shape[2] * x.shape[3]) % 4 == 0
 
