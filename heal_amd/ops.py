@@ -709,12 +709,13 @@ def warp_fuse_levels_src(sources, shapes, affine_rows, grid_f64=True, crops=None
 WARP_ATT_MAX_AGENTS, WARP_ATT_MAX_LEVELS = WARP_MAX_AGENTS, WARP_MAX_LEVELS
 
 
-def warp_att_fuse_levels(feats_list, affine_rows, grid_f64=True, mode="att", sqrt_dims=None):
+def warp_att_fuse_levels(feats_list, affine_rows, grid_f64=True, mode="att", sqrt_dims=None, outs=None):
     """CoAlign's multiscale fusion for every level of one scene in ONE launch (heal_warp_att_fuse_levels): per ego pixel the
     agents' maps are warped into the ego frame (agent 0 included) and reduced with the ego row of the per-pixel agent attention
     (mode "att": softmax_j(x_0 . x_j / sqrt_dim) weights) or the maximum over agents (mode "max").
     feats_list[l] [n,C_l,H_l,W_l] fp32, affine_rows [n,2,3] (host array or CUDA tensor read at run time, shared by the levels),
-    sqrt_dims[l]: the divisor of the logits (None: sqrt(C_l)) -> list of [C_l,H_l,W_l]."""
+    sqrt_dims[l]: the divisor of the logits (None: sqrt(C_l)) -> list of [C_l,H_l,W_l] (outs[l] when the caller gives the
+    destinations: one contiguous fp32 tensor of that shape per level, on the level's device)."""
     if mode not in ("att", "max"):
         raise _capi.HealAmdError(f"warp_att_fuse_levels: mode must be 'att' or 'max', got {mode!r}")
     L = len(feats_list)
@@ -730,10 +731,12 @@ def warp_att_fuse_levels(feats_list, affine_rows, grid_f64=True, mode="att", sqr
         raise _capi.HealAmdError(f"warp_att_fuse_levels: 1..{WARP_ATT_MAX_AGENTS} agents per scene (got {n})")
     if sqrt_dims is not None and len(sqrt_dims) != L:
         raise _capi.HealAmdError(f"warp_att_fuse_levels: {len(sqrt_dims)} sqrt_dims for {L} levels")
-    outs, nbytes = [], 0.0
-    for f in feats_list:
+    if outs is not None and len(outs) != L:
+        raise _capi.HealAmdError(f"warp_att_fuse_levels: {len(outs)} outs for {L} levels")
+    given, outs, nbytes = outs, [], 0.0
+    for l, f in enumerate(feats_list):                      # every destination is checked before anything is launched
         C, H, W = (int(v) for v in f.shape[1:])
-        outs.append(torch.empty((C, H, W), dtype=torch.float32, device=f.device))
+        outs.append(_out_like(None if given is None else given[l], (C, H, W), f.device, f"warp_att_fuse_levels: level {l}"))
         nbytes += 4.0 * H * W * (n * C + C)                 # compulsory traffic: every agent's map once, the fused map once
     a, ap, adev = _affine_args(affine_rows, n)
     sd = [float(np.float32(np.sqrt(int(f.shape[1])) if sqrt_dims is None else sqrt_dims[l])) for l, f in enumerate(feats_list)]
@@ -1259,6 +1262,8 @@ def agent_window_attention(qkv, bias, n_valid, mode, heads, dim_head, window, sc
     q|k|v, token-major), bias [heads,T,T] (T = L window^2, token order (l w1 w2)) or None, n_valid: agents >= n_valid are masked
     keys, mode 'window' | 'grid' -> [L,H,W,heads*dim_head] (written into `out` when given)."""
     qkv = _need(qkv, torch.float32, "qkv")
+    if qkv.dim() != 4:
+        raise _capi.HealAmdError("agent_window_attention: qkv must be [L,H,W,3*heads*dim_head]")
     L, H, W, C3 = (int(v) for v in qkv.shape)
     if mode not in _AGENT_WINDOW_MODES:
         raise _capi.HealAmdError(f"agent_window_attention: mode must be 'window' or 'grid', got {mode!r}")
@@ -1274,10 +1279,7 @@ def agent_window_attention(qkv, bias, n_valid, mode, heads, dim_head, window, sc
         if tuple(bias.shape) != (heads, T, T):
             raise _capi.HealAmdError(f"agent_window_attention: bias must be [heads, T, T] = [{heads}, {T}, {T}]")
     inner = heads * dim_head
-    if out is None:
-        out = torch.empty((L, H, W, inner), dtype=torch.float32, device=qkv.device)
-    elif not (out.is_contiguous() and out.numel() == L * H * W * inner and out.dtype == torch.float32):
-        raise _capi.HealAmdError("agent_window_attention: `out` must be a contiguous f32 [L,H,W,heads*dim_head] buffer")
+    out = _out_like(out, (L, H, W, inner), qkv.device, "agent_window_attention")
     # per query token: q k^T and p v over the n_valid * window^2 unmasked keys = 4 n_valid window^2 inner FLOPs; q | k | v read +
     # the result written = 16 inner bytes
     with _Timed(f"agent_window_attention_{mode}", flops=4.0 * L * H * W * n_valid * window * window * inner,
@@ -1294,12 +1296,14 @@ def agent_window_attention_train_supported(n_agents, window, dim_head, H, W):
                 and _capi.lib().heal_agent_window_attention_backward_supported(int(n_agents), int(window), int(dim_head), int(H), int(W)))
 
 
-def agent_window_attention_backward(qkv, bias, grad_out, n_valid, mode, heads, dim_head, window, scale, parts=None):
+def agent_window_attention_backward(qkv, bias, grad_out, n_valid, mode, heads, dim_head, window, scale, parts=None,
+                                    grad_qkv=None, grad_bias=None):
     """Backward of agent_window_attention (heal_agent_window_attention_backward): qkv / bias / n_valid / mode as in the forward,
     grad_out like the forward's result -> (grad_qkv like qkv, grad_bias [heads,T,T] | None).  The forward's result itself is not
     needed: the kernel recomputes the probabilities and forms the softmax gradient's row term from them.  Masked agents' dK / dV
     rows and grad_bias columns are exact zeros.  parts: into how many ranges the groups are cut for the deterministic grad_bias sum
-    (None: the library's policy)."""
+    (None: the library's policy).  grad_qkv / grad_bias: optional destinations (contiguous fp32 tensors of those shapes on qkv's
+    device; grad_bias only together with a bias), checked before anything is launched."""
     who = "agent_window_attention_backward"
     qkv = _need(qkv, torch.float32, "qkv"); grad_out = _need(grad_out, torch.float32, "grad_out")
     if qkv.dim() != 4:
@@ -1322,15 +1326,17 @@ def agent_window_attention_backward(qkv, bias, grad_out, n_valid, mode, heads, d
     parts = 0 if parts is None else int(parts)
     if parts and not 1 <= parts <= G:
         raise _capi.HealAmdError(f"{who}: parts {parts} outside 1..{G} (the groups)")
-    grad_bias, ws, need = None, None, 0
+    ws, need = None, 0
+    if bias is None and grad_bias is not None:
+        raise _capi.HealAmdError(f"{who}: `grad_bias` goes with a bias")
+    grad_qkv = _out_like(grad_qkv, (L, H, W, C3), qkv.device, who, "grad_qkv")
     if bias is not None:
         bias = _need(bias, torch.float32, "bias")
         if tuple(bias.shape) != (heads, T, T) or bias.device != qkv.device:
             raise _capi.HealAmdError(f"{who}: bias must be [heads, T, T] = [{heads}, {T}, {T}] on the device of qkv")
-        grad_bias = torch.empty_like(bias)
+        grad_bias = _out_like(grad_bias, (heads, T, T), qkv.device, who, "grad_bias")
         need = _capi.query("heal_agent_window_attention_backward_workspace", L, H, W, int(heads), parts)
         ws = _workspace("agent_window_attention_bwd", need, qkv.device) if need else None
-    grad_qkv = torch.empty_like(qkv)
     # per query token: 7 products over the n_valid * window^2 unmasked keys (S and dP in both phases, dQ, dK, dV) = 14 n_valid
     # window^2 inner FLOPs; q | k | v and grad_out read + grad_qkv written = 28 inner bytes
     with _Timed(f"agent_window_attention_backward_{mode}", flops=14.0 * L * H * W * n_valid * window * window * inner,
@@ -2858,6 +2864,13 @@ def _out_or_empty(out, shape, device, who):
     if (tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous()):
         raise _capi.HealAmdError(f"{who}: `out` must be a contiguous f32 cuda tensor of shape {tuple(shape)}")
     return out
+
+
+def _out_like(out, shape, device, who, name="out"):
+    """_out_or_empty for a destination that must also lie on the operands' device (`name`: the argument in the message)."""
+    if out is not None and (not isinstance(out, torch.Tensor) or out.device != device):
+        raise _capi.HealAmdError(f"{who}: `{name}` must be a contiguous f32 tensor of shape {tuple(shape)} on {device}")
+    return _out_or_empty(out, shape, device, f"{who} ({name})" if name != "out" else who)
 
 
 def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixel_major=False, out=None):

@@ -1,9 +1,11 @@
-"""Float64 numpy references, per-element error bounds and hand-built fixtures of the attention conformance suite
+"""Float64 numpy references, per-element error bounds and hand-built fixtures of the attention conformance suites
 (tests/test_gpu_attention_conformance.py): K6 (heal_amd/csrc/agent_attn.hip: k_agent_attn, k_agent_attn_bwd) and K6b
-(heal_amd/csrc/window_attn.hip: k_window_attn, k_window_attn_bwd_q, k_window_attn_bwd_kv) -- numpy only and closed-form gradients,
-so that tests/test_attention_refs_cpu.py can prove every reference against float64 torch autograd on a machine without a GPU.
+(heal_amd/csrc/window_attn.hip: k_window_attn, k_window_attn_bwd_q, k_window_attn_bwd_kv), and (tests/test_gpu_swap_conformance.py)
+CoBEVT's agent-window attention (heal_amd/csrc/swap_attn.hip: k_agent_window_attn; swap_attn_bwd.hip: k_agent_window_attn_bwd,
+k_sum_parts) -- numpy only and closed-form gradients, so that tests/test_attention_refs_cpu.py and tests/test_swap_refs_cpu.py can
+prove every reference against float64 torch autograd on a machine without a GPU.
 
-Both kernels compute, per problem b (K6b: one (agent, window, head); K6: one (pixel, head)),
+All of them compute, per problem b (K6b: one (agent, window, head); K6: one (pixel, head); CoBEVT: one (group, head)),
     s = scale Q K^T (+ bias)  [masked keys: -inf],   P = softmax_rows(s),   O = P V
     dP = dO V^T,  D_q = sum_j P_qj dP_qj (= dO_q . O_q),  dS = P o (dP - D),
     dQ = scale dS K,  dK = scale dS^T Q,  dV = P^T dO,  grad_bias = sum_b dS_b.
@@ -68,15 +70,16 @@ def f32_scale(dim_head):
 # the shared core: B independent attention problems
 # =====================================================================================================================
 def _core(Q, K, V, dO, bias, valid, scale, c):
-    """Q [B,Tq,d], K, V [B,Tk,d], dO [B,Tq,d] or None, bias [Tq,Tk] or None, valid [Tk] bool or None (False: key masked to -inf),
-    all float64.  c: the rounding counts of window_k / agent_k.  Returns value / T / E of every output, per problem (the callers
+    """Q [B,Tq,d], K, V [B,Tk,d], dO [B,Tq,d] or None, bias [Tq,Tk] (shared by the problems) or [B,Tq,Tk] (one per problem: the
+    per-head bias of swap_reference) or None, valid [Tk] bool or None (False: key masked to -inf), all float64.  c: the rounding counts of window_k / agent_k.  Returns value / T / E of every output, per problem (the callers
     put them back into the tensors' layouts); E and the k * T products are in units of EPS."""
     aQ, aK, aV = np.abs(Q), np.abs(K), np.abs(V)
     s = scale * np.einsum("bqd,bkd->bqk", Q, K)
     A = scale * np.einsum("bqd,bkd->bqk", aQ, aK)
     if bias is not None:
-        s = s + bias[None]
-        A = A + np.abs(bias)[None]
+        bb = bias[None] if bias.ndim == 2 else bias
+        s = s + bb
+        A = A + np.abs(bb)
     if valid is not None:
         s = np.where(valid[None, None, :], s, -np.inf)
         A = np.where(valid[None, None, :], A, 0.0)
@@ -360,3 +363,208 @@ def to_layout(x, agent_major):
 
 def from_layout(x, agent_major):
     return np.transpose(x, (1, 0, 2)) if agent_major else x
+
+
+# =====================================================================================================================
+# CoBEVT: heal_agent_window_attention / heal_agent_window_attention_backward (swap_attn.hip, swap_attn_bwd.hip)
+# =====================================================================================================================
+SWAP_WS, SWAP_D = 4, 32
+SWAP_MAX_L = 8
+SWAP_PARTS_BLOCKS = 1024       # SWAPB_BLOCKS of swap_attn_bwd.hip: the parts policy aims at this many blocks
+
+
+def _permute(t, axes):
+    return t.permute(*axes) if hasattr(t, "permute") else t.transpose(axes)
+
+
+def swap_groups(t, mode, L, H, W):
+    """[L, H, W, c] -> [groups, T = 16 L, c] in the reference's (l w1 w2) token order; numpy arrays and torch tensors alike (the
+    float64 autograd witnesses regroup tensors that record a graph).  window: 'b m d (x w1) (y w2) -> (b x y) (m w1 w2) d', a group
+    is one 4 x 4 tile of every agent; grid: 'b m d (w1 x) (w2 y) -> ..', a group is a dilated 4 x 4 grid (swap_fusion_modules.py)."""
+    c = t.shape[-1]
+    X, Y = H // SWAP_WS, W // SWAP_WS
+    if mode == "window":
+        return _permute(t.reshape(L, X, SWAP_WS, Y, SWAP_WS, c), (1, 3, 0, 2, 4, 5)).reshape(X * Y, L * 16, c)
+    return _permute(t.reshape(L, SWAP_WS, X, SWAP_WS, Y, c), (2, 4, 0, 1, 3, 5)).reshape(X * Y, L * 16, c)
+
+
+def swap_ungroup(o, mode, L, H, W):
+    """The inverse of swap_groups: [groups, T, c] -> [L, H, W, c]."""
+    c = o.shape[-1]
+    X, Y = H // SWAP_WS, W // SWAP_WS
+    if mode == "window":
+        return _permute(o.reshape(X, Y, L, SWAP_WS, SWAP_WS, c), (2, 0, 3, 1, 4, 5)).reshape(L, H, W, c)
+    return _permute(o.reshape(X, Y, L, SWAP_WS, SWAP_WS, c), (2, 3, 0, 4, 1, 5)).reshape(L, H, W, c)
+
+
+def swap_split(x, mode, parts, heads, d):
+    """[L,H,W,parts*heads*d] -> [parts, B, T, d] with B = (group, head) and T = 16 L tokens in (l w1 w2) order."""
+    L, H, W, _ = x.shape
+    g = swap_groups(np.asarray(x), mode, L, H, W)                               # [G, T, parts * heads * d]
+    G, T = g.shape[:2]
+    return g.reshape(G, T, parts, heads, d).transpose(2, 0, 3, 1, 4).reshape(parts, G * heads, T, d)
+
+
+def swap_merge(t, mode, L, H, W, heads, d):
+    """The inverse of swap_split: [parts, B, T, d] -> [L,H,W,parts*heads*d]."""
+    parts, T = t.shape[0], t.shape[2]
+    G = t.shape[1] // heads
+    g = np.ascontiguousarray(t.reshape(parts, G, heads, T, d).transpose(1, 3, 0, 2, 4)).reshape(G, T, parts * heads * d)
+    return np.ascontiguousarray(swap_ungroup(g, mode, L, H, W))
+
+
+def swap_policy_parts(H, W, heads):
+    """heal_agent_window_attention_backward_parts restated: min(groups, max(1, 1024 / heads))."""
+    G = (H // SWAP_WS) * (W // SWAP_WS)
+    return min(G, max(1, SWAP_PARTS_BLOCKS // heads))
+
+
+def swap_k(L, n_valid, d, groups=1, parts=1):
+    """Roundings per term of k_agent_window_attn<L, d> and k_agent_window_attn_bwd<L, d> (+ k_sum_parts) in EPS.  T = 16 L query tokens,
+    Tk = 16 n_valid unmasked keys (a masked agent is a key tile that is neither staged nor multiplied: it adds nothing to any count),
+    groups = (H / 4) (W / 4), parts = the ranges the groups are cut into for grad_bias.  The differences from window_k:
+
+    s      : S^T = K Q^T is d MFMA reduction steps: product 1 + d adds; `* scale` 1; `+ bias` 1 (without a bias 0.0f is added:
+             exact, the count stays an upper bound).                                                    c_s  = d + 3
+    e      = expf(s - mx): the subtraction 1 (-> (c_s + 1) A and Amax in Cm, module docstring), expf 4.
+    sum    : a lane adds its 4 values of every valid tile in sequence (Tk / 4 values from 0.f: Tk / 4 - 1 roundings), two xor-shuffle
+             adds: Tk / 4 + 1, each term carrying its expf 4.
+    inv    = 1 / sum: 1.  p = e * inv (backward; the forward multiplies the accumulated O by inv): 1.
+             k_p = 4 + 4 + (Tk / 4 + 1) + 1 + 1 = Tk / 4 + 11, taken as                                 k_p  = Tk / 4 + 12
+             (the + 1: phase 2 rebuilds p as expf(sc * scale + bv - mx) * inv from the saved (mx, inv) and a second evaluation of
+             the score -- the same count, but an error that need not be the one inside `sum`; first order, the same formula.)
+    out    : O^T = V^T P^T is Tk reduction steps: product 1 + Tk adds (`* inv` is in k_p).               k_out = k_p + Tk + 1
+    dP     = V dO^T (phase 1) / dO V^T (phase 2): d reduction steps.                                     c_dp = d + 1
+    D      = sum_j P_j dP_j from the recomputed tiles: per valid tile `(e dp + e dp) + (e dp + e dp)`: product 1, two adds 2; the
+             running `dsum +=` over n_valid tiles: n_valid; two shuffle adds 2; `* inv` is the product that makes e a p (in k_p).
+             e within pi - 1, dp within c_dp of dP|.|: (k_p + c_dp + n_valid + 5) D|.| + E_D with D|.| = sum_j P_j dP|.|_j and
+             E_D = sum_j P_j Cm_j dP|.|_j (`D_from_out=False` in _core).                                 k_D  = k_p + c_dp + n_valid + 5
+    dS     = (e * inv) * (dp - D): the subtraction 1 of dP|.| + D|.|, the product 1, p within pi, dp within c_dp dP|.|, D within
+             k_D D|.| + E_D: as in window_k                                                              k_dS = k_p + 2 + max(c_dp, k_D)
+    dQ     = K^T dS^T over the Tk valid keys (Tk + 1), then `* scale` 1.                                 k_dq = k_dS + Tk + 2
+    dK     = Q^T dS over ALL T queries (queries are not masked), then `* scale`.                         k_dk = k_dS + T + 2
+    dV     = dO^T P over the T queries.                                                                  k_dv = k_p + T + 1
+    bias   : a lane's `db += ds` over the groups of its part in group order from 0.f (the largest part holds
+             ceil(groups / parts) groups: one rounding less than that), then k_sum_parts adds the parts in part order (parts - 1).
+             No atomics and no sum over heads (the bias is per head).                 k_bias = k_dS + ceil(groups / parts) - 1 + parts - 1"""
+    T, Tk = 16 * L, 16 * n_valid
+    k_p = Tk // 4 + 12
+    k_out = k_p + Tk + 1
+    c_dp = d + 1
+    k_D = k_p + c_dp + n_valid + 5
+    k_dS = k_p + 2 + max(c_dp, k_D)
+    per_part = -(-groups // parts)
+    return dict(s=d + 3, p=k_p, out=k_out, D=k_D, dp=c_dp, dS=k_dS, dq=k_dS + Tk + 2, dk=k_dS + T + 2, dv=k_p + T + 1,
+                bias=k_dS + per_part - 1 + parts - 1, D_from_out=False)
+
+
+def swap_reference(qkv, bias, grad_out, n_valid, mode, heads, scale, parts=None):
+    """qkv [L,H,W,3*heads*d] (q | k | v, each [heads, d]), bias [heads,T,T] or None, grad_out [L,H,W,heads*d] or None; n_valid:
+    agents >= n_valid are masked keys (their K and V are never read: whatever they hold, NaN included, is replaced by 0 here);
+    scale: the fp32 number passed to the kernel; parts: of the grad_bias sum (None: the library's policy).
+    -> dict: out / T_out / B_out in the output's layout; with grad_out also grad_qkv / T_grad_qkv / B_grad_qkv in qkv's layout,
+    grad_bias / T_grad_bias / E_grad_bias / B_grad_bias [heads,T,T] (zeros without a bias), dS [G, heads, T, T]."""
+    qkv = np.asarray(qkv, np.float64)
+    L, H, W, C3 = qkv.shape
+    d = C3 // (3 * heads)
+    T, G = 16 * L, (H // SWAP_WS) * (W // SWAP_WS)
+    valid = np.arange(T) < 16 * n_valid
+    q, k, v = swap_split(qkv, mode, 3, heads, d)
+    k, v = (np.where(valid[None, :, None], t, 0.0) for t in (k, v))
+    dO = None if grad_out is None else swap_split(np.asarray(grad_out, np.float64), mode, 1, heads, d)[0]
+    b = None if bias is None else np.tile(np.asarray(bias, np.float64), (G, 1, 1))          # problem (g, h) -> bias[h]
+    parts = swap_policy_parts(H, W, heads) if parts is None else int(parts)
+    kk = swap_k(L, n_valid, d, G, parts)
+    r = _core(q, k, v, dO, b, valid, float(scale), kk)
+    put = lambda t: swap_merge(t, mode, L, H, W, heads, d)      # noqa: E731
+    res = dict(k=kk, P=r["P"])
+    res["out"], res["T_out"] = put(r["out"][None]), put(r["T_out"][None])
+    res["B_out"] = _bound(kk["out"], res["T_out"], put(r["E_out"][None]))
+    if dO is None:
+        return res
+    res["grad_qkv"] = put(np.stack([r["dq"], r["dk"], r["dv"]]))
+    res["T_grad_qkv"] = put(np.stack([r["T_dq"], r["T_dk"], r["T_dv"]]))
+    res["B_grad_qkv"] = put(np.stack([_bound(kk[n], r["T_" + n], r["E_" + n]) for n in ("dq", "dk", "dv")]))
+    per = lambda t: t.reshape(G, heads, T, T)      # noqa: E731
+    res["dS"] = per(r["dS"])
+    res["grad_bias"], res["T_grad_bias"], res["E_grad_bias"] = per(r["dS"]).sum(0), per(r["dSa"]).sum(0), per(r["EdS"]).sum(0)
+    if bias is None:
+        for n in ("grad_bias", "T_grad_bias", "E_grad_bias"):
+            res[n] = np.zeros((heads, T, T))
+    res["B_grad_bias"] = swap_bias_bound(res, L, n_valid, d, G, parts)
+    return res
+
+
+def swap_bias_bound(ref, L, n_valid, d, groups, parts):
+    """The grad_bias bound of a launch with `parts` parts (only the order of the sum, hence only k_bias, depends on them)."""
+    return _bound(swap_k(L, n_valid, d, groups, parts)["bias"], ref["T_grad_bias"], ref["E_grad_bias"])
+
+
+def swap_perm(T, Tk, h=0):
+    """The key selected by each of the T queries of head h among the Tk = 16 n_valid valid keys: pi_h(i) = (11 i + 3 + 8 h) mod Tk.
+    11 is coprime to 16 n for n <= 8, so the first Tk queries select every key once (and T / Tk of the queries, rounded either
+    way, select one key); neighbouring queries select keys 11 apart: the selection crosses agent tiles whenever Tk > 16.
+    10 i + 3 + 8 h is odd: no query selects its own index; pi(pi(i)) - i = 4 (30 i + 9 + 24 h) is no multiple of 16: the bias is not
+    symmetric anywhere, a transposed read selects another key; the heads differ by 8 keys."""
+    return (11 * np.arange(T) + 3 + 8 * h) % Tk
+
+
+def swap_data(L, regime, seed, n_valid=None, H=8, W=12, heads=2, d=SWAP_D, use_bias=True):
+    """The CoBEVT fixtures on an H x W map -> dict(qkv, bias or None, grad_out), float32.  K and V of the agents >= n_valid hold
+    ordinary values here; the GPU tests poison them.
+      spread    : qkv N(0, 0.8), bias N(0, 1) per head -- a softmax with many comparable weights.
+      large     : q and k N(0, LARGE_STD): scores with a standard deviation of 20 (scale * sqrt(d) = 1), extremes beyond +-60; bias N(0, 1).
+      uniform   : q = 0, no bias, integer k, v and grad_out: every probability is 1 / (16 n_valid) -- exactly when n_valid is a power
+                  of two (T = 16 L itself is one only for L in {1, 2, 4, 8}).
+      selector  : q = 0, bias[h, i, pi_h(i)] = 0 and SELECT elsewhere (swap_perm): P[i, pi_h(i)] == 1 exactly, for every n_valid.
+    use_bias=False drops the bias of spread / large."""
+    g = np.random.default_rng(seed)
+    n_valid = L if n_valid is None else n_valid
+    T, Tk = 16 * L, 16 * n_valid
+    shape = (L, H, W, 3, heads, d)
+    if regime in ("spread", "large"):
+        qkv = g.standard_normal(shape) * 0.8
+        if regime == "large":
+            qkv[:, :, :, :2] *= LARGE_STD / 0.8
+        bias = g.standard_normal((heads, T, T)) if use_bias else None
+        gout = g.standard_normal((L, H, W, heads * d))
+    else:
+        qkv = g.integers(-3, 4, shape).astype(np.float64)
+        qkv[:, :, :, 0] = 0.0
+        gout = g.integers(-3, 4, (L, H, W, heads * d)).astype(np.float64)
+        bias = None
+        if regime == "selector":
+            bias = np.full((heads, T, T), SELECT)
+            for h in range(heads):
+                bias[h, np.arange(T), swap_perm(T, Tk, h)] = 0.0
+    f = lambda a: None if a is None else np.ascontiguousarray(a, F32)      # noqa: E731
+    return dict(qkv=f(qkv.reshape(L, H, W, 3 * heads * d)), bias=f(bias), grad_out=f(gout))
+
+
+def swap_exact(data, n_valid, mode, heads, regime):
+    """What the exact CoBEVT fixtures assert bit for bit, and the largest sum of absolute terms behind it in units of the grid.
+    uniform (n_valid a power of two; unit 1 / Tk): e = 1, sum = Tk, inv = 1 / Tk: out = (sum_j v_j) * inv and dV_j = sum_q dO_q * (1 * inv)
+        for the valid keys j (the same row for all of them); dK = scale * sum_q 0 * dS = 0.  dQ is NOT asserted: a real gradient.
+    selector (unit 1): e in {0, 1}, sum = inv = 1: out_i = v_pi(i); dP_j = dO_i . v_j and D = dP_pi(i) are integers of at most
+        d max|v| max|dO|, dS = 1 * (dP - D) = 0 or 0 * (..) = 0: dQ = dK = grad_bias = 0, dV_j = sum_{i: pi(i) = j} dO_i.
+    dK and dV of masked agents are zeros in both.
+    -> dict(out, dk, dv [L,H,W,heads*d] float64, dq (selector only), units)."""
+    qkv = data["qkv"].astype(np.float64)
+    L, H, W, C3 = qkv.shape
+    d = C3 // (3 * heads)
+    T, Tk = 16 * L, 16 * n_valid
+    v = swap_split(qkv, mode, 3, heads, d)[2]
+    g = swap_split(data["grad_out"].astype(np.float64), mode, 1, heads, d)[0]
+    put = lambda t: swap_merge(t[None], mode, L, H, W, heads, d)      # noqa: E731
+    vmax, gmax = float(np.abs(v).max()), float(np.abs(g).max())
+    dv = np.zeros_like(v)
+    if regime == "uniform":
+        out = np.broadcast_to(v[:, :Tk].sum(1, keepdims=True) / Tk, v.shape)
+        dv[:, :Tk] = g.sum(1, keepdims=True) / Tk
+        return dict(out=put(out), dk=put(np.zeros_like(v)), dv=put(dv), units=T * max(vmax, gmax))
+    out = np.empty_like(v)
+    for b in range(v.shape[0]):
+        pi = swap_perm(T, Tk, b % heads)
+        out[b] = v[b, pi]
+        np.add.at(dv[b], pi, g[b])
+    return dict(out=put(out), dq=put(np.zeros_like(v)), dk=put(np.zeros_like(v)), dv=put(dv), units=max(2.0 * d * vmax * gmax, T * gmax))

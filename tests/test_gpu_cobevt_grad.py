@@ -8,29 +8,13 @@ import functools
 import pytest
 import torch
 
+from tests.attention_refs import swap_groups as _groups, swap_ungroup as _ungroup
 from tests.golden.detfill import fill_module
 
 pytestmark = [pytest.mark.gpu, pytest.mark.grad]
 
 D, WS = 32, 4
 BOUND = 2e-5        # what test_window_attention_backward_kernel_vs_float64_autograd holds the window backward to (T <= 256, d = 32)
-
-
-def _groups(t, mode, L, H, W):
-    """[L, H, W, c] -> [groups, T = 16 L, c] in the reference's (l w1 w2) token order."""
-    c = t.shape[-1]
-    X, Y = H // WS, W // WS
-    if mode == "window":     # 'b m d (x w1) (y w2) -> (b x y) (m w1 w2) d'
-        return t.reshape(L, X, WS, Y, WS, c).permute(1, 3, 0, 2, 4, 5).reshape(X * Y, L * 16, c)
-    return t.reshape(L, WS, X, WS, Y, c).permute(2, 4, 0, 1, 3, 5).reshape(X * Y, L * 16, c)   # 'b m d (w1 x) (w2 y) -> ..'
-
-
-def _ungroup(o, mode, L, H, W):
-    c = o.shape[-1]
-    X, Y = H // WS, W // WS
-    if mode == "window":
-        return o.reshape(X, Y, L, WS, WS, c).permute(2, 0, 3, 1, 4, 5).reshape(L, H, W, c)
-    return o.reshape(X, Y, L, WS, WS, c).permute(2, 3, 0, 4, 1, 5).reshape(L, H, W, c)
 
 
 def reference_fp64(qkv, bias, gout, n_valid, mode, heads, scale):
