@@ -18,6 +18,7 @@ HEADER_TRAIN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train.h"
 HEADER_EXT = os.path.join(os.path.dirname(HERE), "include", "heal_amd_ext.h")
 HEADER_TRAIN_ATTN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train_attn.h")
 HEADER_TRAIN_BN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train_bn.h")
+HEADER_TRAIN_WARP = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train_warp.h")
 
 _lib = None
 
@@ -110,6 +111,15 @@ def signatures_train_bn():
         return parse_prototypes(f.read())
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_train_warp():
+    """{name: (restype, argtypes)} of include/heal_amd_train_warp.h: warp_affine_simple as a differentiable operator -- the forward
+    of all agents of a scene, its gather-form backward and the host-side support rule.  Every build exports them; like
+    signatures_train() they are outside the versioned inference ABI."""
+    with open(HEADER_TRAIN_WARP) as f:
+        return parse_prototypes(f.read())
+
+
 def declared_symbols(experimental=False):
     """Function names declared in include/heal_amd.h (the shipped C ABI), or with experimental=True in
     include/heal_amd_experimental.h."""
@@ -143,7 +153,7 @@ def lib():
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**signatures(), **signatures_train(), **signatures_ext(), **signatures_train_attn(),
-                                  **signatures_train_bn()}.items():
+                                  **signatures_train_bn(), **signatures_train_warp()}.items():
             if not hasattr(L, name):
                 continue  # declared but not built yet -> surfaces in call() / the symbol test
             f = getattr(L, name)

@@ -50,16 +50,6 @@ __device__ __forceinline__ float score_at(const float* __restrict__ occ, int idx
     return 1.f / (1.f + expf(-occ[idx])) + 1e-4f;
 }
 
-__device__ __forceinline__ float sample(const float* __restrict__ src, const Taps& t, int W) {
-    // nw, ne, sw, se accumulated in that order (taps outside contribute exactly zero)
-    float acc = 0.f;
-    if (t.ok & 1u) acc = src[t.off] * t.w[0];
-    if (t.ok & 2u) acc += src[t.off + 1] * t.w[1];
-    if (t.ok & 4u) acc += src[t.off + W] * t.w[2];
-    if (t.ok & 8u) acc += src[t.off + W + 1] * t.w[3];
-    return acc;
-}
-
 __device__ __forceinline__ float sample_score(const float* __restrict__ occ, const Taps& t, int W, const int* crop) {
     float acc = 0.f;
     if (t.ok & 1u) acc = score_at(occ, t.off, W, crop) * t.w[0];

@@ -1,5 +1,5 @@
 // The sampling arithmetic of warp_affine_simple (torch_transformation_utils.py:323-332), shared by every kernel that warps an
-// agent's map into the ego frame (warp_fuse.hip, disco_fuse.hip).  It follows PyTorch operation for operation: base grid =
+// agent's map into the ego frame (warp_fuse.hip, disco_fuse.hip, warp_mha.hip, warp_affine.hip).  It follows PyTorch operation for operation: base grid =
 // linspace(-1,1,W)*(W-1)/W in the dtype of the affine matrix (float64 when pairwise_t_matrix comes from numpy), grid =
 // base @ M^T, rounded to fp32, unnormalise ((g+1)*size-1)/2, floor, corner weights as products of fp32 differences, taps
 // outside the image contribute zero.
@@ -26,11 +26,16 @@ __device__ __forceinline__ T base_coord(int j, int n) {
     return v * (T)(n - 1) / (T)n;
 }
 
+// the grid point of base coordinates (xs, ys): base @ M^T in T, rounded once to fp32
 template <typename T>
-__device__ __forceinline__ void grid_point(const double* m, int h, int w, int H, int W, float& gx, float& gy) {
-    const T xs = base_coord<T>(w, W), ys = base_coord<T>(h, H);
+__device__ __forceinline__ void grid_from_base(const double* m, T xs, T ys, float& gx, float& gy) {
     gx = (float)(((T)m[0] * xs + (T)m[1] * ys) + (T)m[2]);
     gy = (float)(((T)m[3] * xs + (T)m[4] * ys) + (T)m[5]);
+}
+
+template <typename T>
+__device__ __forceinline__ void grid_point(const double* m, int h, int w, int H, int W, float& gx, float& gy) {
+    grid_from_base<T>(m, base_coord<T>(w, W), base_coord<T>(h, H), gx, gy);
 }
 
 __device__ __forceinline__ Taps make_taps(float gx, float gy, int H, int W) {
@@ -53,6 +58,16 @@ __device__ __forceinline__ Taps make_taps(float gx, float gy, int H, int W) {
     const float xc = fminf(fmaxf(x0, -2.f), (float)W), yc = fminf(fmaxf(y0, -2.f), (float)H);
     t.off = (int)yc * W + (int)xc;
     return t;
+}
+
+__device__ __forceinline__ float sample(const float* __restrict__ src, const Taps& t, int W) {
+    // nw, ne, sw, se accumulated in that order (taps outside contribute exactly zero)
+    float acc = 0.f;
+    if (t.ok & 1u) acc = src[t.off] * t.w[0];
+    if (t.ok & 2u) acc += src[t.off + 1] * t.w[1];
+    if (t.ok & 4u) acc += src[t.off + W] * t.w[2];
+    if (t.ok & 8u) acc += src[t.off + W + 1] * t.w[3];
+    return acc;
 }
 
 }  // namespace heal

@@ -1,7 +1,9 @@
 """Single-scale fusion operators used by HeterModelBaseline (reference: opencood/models/fuse_modules/
 fusion_in_one.py): MaxFusion (:87-124), AttFusion (:126-151, :14-45), DiscoFusion (:153-201), V2VNetFusion (:203-318),
-V2XViTFusion (:320-372), CoBEVT (:374-430), Where2commFusion (:431-484), Who2comFusion (:486-539).  Warping to the ego frame is K5's
-heal_warp_agent; the per-pixel attention is K6; CoBEVT's agent-window attention is heal_agent_window_attention
+V2XViTFusion (:320-372), CoBEVT (:374-430), Where2commFusion (:431-484), Who2comFusion (:486-539).  Warping to the ego frame is
+heal_warp_affine_forward (K5's sampling code, every agent of a scene in one launch; on the gradient path, in
+ops.warp_grad("kernel") mode, ops.WarpAffine with the gather-form heal_warp_affine_backward instead of affine_grid + grid_sample);
+the per-pixel attention is K6; CoBEVT's agent-window attention is heal_agent_window_attention
 (swap_fusion_modules.py; with `grad_kernel` its backward is heal_agent_window_attention_backward); V2VNet's masked message
 aggregation is heal_v2v_message; DiscoNet's warp + pixel-weight MLP + softmax is heal_disco_fuse; Where2comm's warp + multi-head attention over agents is heal_warp_mha_fuse."""
 
@@ -21,12 +23,17 @@ def regroup(x, record_len):
 
 def warp_to_ego(x, affine_rows, grid_f64=True):
     """warp_affine_simple(x, t_matrix[0, :], (H, W)) for one scene: x [n,C,H,W] -> [n,C,H,W]."""
-    if torch.is_grad_enabled() and x.requires_grad:   # gradient path: affine_grid + grid_sample (torch_transformation_utils.py:323-332)
+    if isinstance(affine_rows, (list, tuple)) and len(affine_rows) and isinstance(affine_rows[0], torch.Tensor):
+        affine_rows = torch.stack(list(affine_rows))      # per-agent rows (the agent-sharded runner): one [n, 2, 3] tensor
+    if torch.is_grad_enabled() and x.requires_grad:   # gradient path
+        if ops.warp_grad_enabled() and ops.warp_affine_train_supported(x, affine_rows):
+            return ops.WarpAffine.apply(x, affine_rows, grid_f64)     # ops.warp_grad("kernel"): forward + gather-form backward kernels
+        # affine_grid + grid_sample (torch_transformation_utils.py:323-332)
         import torch.nn.functional as F
+        ops.WARP_GRAD_CALLS["torch"] += 1
         M = torch.as_tensor(affine_rows, dtype=x.dtype, device=x.device)
         return F.grid_sample(x, F.affine_grid(M, list(x.shape), align_corners=False), align_corners=False)
-    zeros = torch.zeros((1,) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
-    return torch.stack([ops.warp_agent(x[a], zeros, affine_rows[a], grid_f64)[0] for a in range(x.shape[0])])
+    return ops.warp_affine(x, affine_rows, grid_f64)     # every agent of the scene in one launch (bit-equal to warp_agent per agent)
 
 
 def _host_affine(affine_matrix):
@@ -181,15 +188,14 @@ class CoBEVT(_WarpThenFuse):
         L = self.agent_size
         if not fused_ok(x, self, L, H, W, C):
             # the reference's arithmetic (fusion_in_one.py:412-430): Regroup's zero padding, warp_affine_simple of all L maps
-            # (the grid built in the affine matrix's dtype, then cast), the blocks on [B, L, C, H, W]
-            import torch.nn.functional as F
+            # (the grid built in the affine matrix's dtype, then cast; ops.WarpAffine in ops.warp_grad("kernel") mode unless a
+            # padded agent's row is singular), the blocks on [B, L, C, H, W]
             aff = affine_matrix if isinstance(affine_matrix, torch.Tensor) else torch.from_numpy(np.asarray(affine_matrix))
             aff = aff.to(x.device)
             warped = []
             for b, feats in enumerate(regroup(x, lens)):
                 pad = torch.cat([feats, feats.new_zeros((L - feats.shape[0],) + tuple(feats.shape[1:]))])
-                grid = F.affine_grid(aff[b, 0, :L], [L, C, H, W], align_corners=False).to(pad)
-                warped.append(F.grid_sample(pad, grid, align_corners=False))
+                warped.append(_warp_affine_simple(pad, aff[b, 0, :L], (H, W)))
             key_mask = (torch.arange(L, device=x.device)[None, :] < torch.tensor(lens, device=x.device)[:, None]).to(torch.int64)
             return self.transformer(torch.stack(warped), key_mask)
         # inference on the device: the real agents warped straight into the token-major layout (one launch per scene)
@@ -204,6 +210,11 @@ class CoBEVT(_WarpThenFuse):
 def _warp_affine_simple(src, M, dsize):
     """torch_transformation_utils.py:323-332: affine_grid (in M's dtype, then cast) + bilinear grid_sample, zero padding."""
     import torch.nn.functional as F
+    if (ops.warp_grad_enabled() and torch.is_grad_enabled() and src.requires_grad and tuple(dsize) == tuple(src.shape[2:])
+            and M.dtype in (torch.float32, torch.float64) and ops.warp_affine_train_supported(src, M)):
+        return ops.WarpAffine.apply(src, M, M.dtype == torch.float64)      # ops.warp_grad("kernel")
+    if torch.is_grad_enabled() and src.requires_grad:
+        ops.WARP_GRAD_CALLS["torch"] += 1
     grid = F.affine_grid(M, [src.shape[0], src.shape[1], dsize[0], dsize[1]], align_corners=False).to(src)
     return F.grid_sample(src, grid, align_corners=False)
 

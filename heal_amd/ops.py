@@ -3523,6 +3523,151 @@ class BatchNormAct(torch.autograd.Function):
         return dx, dres, dgamma, dbeta, None, None, None, None, None, None
 
 
+# ------------------------------------------------------------------------------- warp_affine_simple of the gradient path
+_WARP_GRAD_MODES = ("torch", "kernel")
+_WARP_GRAD_MODE = "torch"
+
+
+class warp_grad:
+    """ops.warp_grad("kernel"): the warps into the ego frame of the gradient path (fusion_in_one.warp_to_ego, _warp_affine_simple,
+    CoBEVT's inline warp) run as ops.WarpAffine on this library's kernels where ops.warp_affine_train_supported takes them;
+    ops.warp_grad("torch") (the default): F.affine_grid + F.grid_sample under autograd.  A plain setter -- the mode is set when the
+    object is made -- and a context manager, which puts the previous mode back on exit:
+        ops.warp_grad("kernel")                 # from here on
+        with ops.warp_grad("kernel"): ...       # for the block
+    A process-wide Python setting, deliberately not an environment switch."""
+
+    def __init__(self, mode):
+        global _WARP_GRAD_MODE
+        if mode not in _WARP_GRAD_MODES:
+            raise ValueError(f"warp_grad: mode must be one of {_WARP_GRAD_MODES}, got {mode!r}")
+        self.previous = _WARP_GRAD_MODE
+        _WARP_GRAD_MODE = mode
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        global _WARP_GRAD_MODE
+        _WARP_GRAD_MODE = self.previous
+        return False
+
+
+def warp_grad_enabled():
+    """True in ops.warp_grad("kernel") mode."""
+    return _WARP_GRAD_MODE == "kernel"
+
+
+# what the gradient-path warps ran since the process started (tests and scripts/warp_grad_bench.py read it): WarpAffine forwards and
+# backwards, and warps left to affine_grid + grid_sample (the default mode, CPU tensors, other dtypes, rows the backward refuses)
+WARP_GRAD_CALLS = {"forward": 0, "backward": 0, "torch": 0}
+
+
+def _warp_rows_host(affine_rows, n, who):
+    """The n affine rows as a contiguous float64 host array [n, 6].  A CUDA tensor is brought to the host (48 n bytes, a
+    synchronising copy: refused under stream capture)."""
+    if isinstance(affine_rows, torch.Tensor):
+        if affine_rows.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise _capi.HealAmdError(f"{who}: the affine rows are a device tensor and the backward's support rule is decided on the "
+                                     "host; that copy cannot run under stream capture (pass host rows)")
+        affine_rows = affine_rows.detach().cpu().numpy()
+    a = np.ascontiguousarray(np.asarray(affine_rows, dtype=np.float64).reshape(-1, 6))
+    if a.shape[0] != n:
+        raise _capi.HealAmdError(f"{who}: expected {n} x (2,3) affine rows, got {a.shape}")
+    return a
+
+
+def _warp_map(x, name, who):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise _capi.HealAmdError(f"{who}: {name} must be a CUDA/HIP tensor (heal_amd has no CPU path)")
+    if x.dtype != torch.float32 or x.dim() != 4 or min(x.shape) < 1:
+        raise _capi.HealAmdError(f"{who}: {name} must be a non-empty fp32 [n, C, H, W] map, got {x.dtype} {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def _warp_rows_supported(rows, H, W):
+    """heal_warp_affine_backward_supported on every chunk of at most WARP_MAX_AGENTS rows of a host array [n, 6]."""
+    L = _capi.lib()
+    return all(bool(L.heal_warp_affine_backward_supported(rows[i:i + WARP_MAX_AGENTS].ctypes.data_as(ctypes.c_void_p),
+                                                          int(min(WARP_MAX_AGENTS, rows.shape[0] - i)), H, W))
+               for i in range(0, rows.shape[0], WARP_MAX_AGENTS))
+
+
+def warp_affine(x, affine_rows, grid_f64=True):
+    """warp_affine_simple(x, rows, (H, W)) for one scene in one launch (heal_warp_affine_forward): x [n,C,H,W] -> [n,C,H,W], agent a
+    sampled with affine_rows[a] ([n,2,3]: a host array, or a CUDA tensor that is then read on the device at run time).  Bit-equal
+    to warp_agent agent by agent.  More than WARP_MAX_AGENTS agents go in chunks."""
+    who = "warp_affine"
+    x = _need(_warp_map(x, "x", who), torch.float32, "x")
+    n, C, H, W = (int(v) for v in x.shape)
+    out = torch.empty_like(x)
+    keep, ap, adev = _affine_args(affine_rows, n)
+    for i in range(0, n, WARP_MAX_AGENTS):
+        k = min(WARP_MAX_AGENTS, n - i)
+        api = ctypes.c_void_p(ap.value + 48 * i) if ap.value else ap
+        adi = ctypes.c_void_p(adev.value + 48 * i) if adev.value else adev
+        with _Timed("warp_affine", 0.0, 8.0 * k * C * H * W, kernel_events=True):
+            _capi.call("heal_warp_affine_forward", _ptr(x[i:i + k]), k, C, H, W, api, adi, int(bool(grid_f64)), _ptr(out[i:i + k]),
+                       _stream())
+    return out
+
+
+def warp_affine_backward(grad_out, affine_rows, grid_f64=True):
+    """The adjoint of warp_affine (heal_warp_affine_backward): grad_out [n,C,H,W] -> grad_x [n,C,H,W], every element written, no
+    atomics (two calls are bit-equal).  affine_rows: host rows [n,2,3] that heal_warp_affine_backward_supported takes."""
+    who = "warp_affine_backward"
+    g = _warp_map(grad_out, "grad_out", who)
+    n, C, H, W = (int(v) for v in g.shape)
+    rows = _warp_rows_host(affine_rows, n, who)
+    gx = torch.empty_like(g)
+    for i in range(0, n, WARP_MAX_AGENTS):
+        k = min(WARP_MAX_AGENTS, n - i)
+        with _Timed("warp_affine_backward", 0.0, 8.0 * k * C * H * W, kernel_events=True):
+            _capi.call("heal_warp_affine_backward", _ptr(g[i:i + k]), k, C, H, W, rows[i:i + k].ctypes.data_as(ctypes.c_void_p),
+                       int(bool(grid_f64)), _ptr(gx[i:i + k]), _stream())
+    return gx
+
+
+def warp_affine_train_supported(x, affine_rows):
+    """True if ops.WarpAffine takes the warp: x a fp32 CUDA map [n, C, H, W] (made contiguous by the operator), rows that carry no
+    gradient, and the C-side rule of heal_warp_affine_backward_supported (finite, invertible, reach <= HEAL_WARP_BWD_MAX_REACH).
+    Rows on the device are read back for the decision; under stream capture that is not possible and the answer is False."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and min(x.shape) >= 1):
+        return False
+    if isinstance(affine_rows, torch.Tensor):
+        if affine_rows.requires_grad or (affine_rows.is_cuda and torch.cuda.is_current_stream_capturing()):
+            return False
+        affine_rows = affine_rows.detach().cpu().numpy()
+    rows = np.asarray(affine_rows, dtype=np.float64)
+    n, C, H, W = (int(v) for v in x.shape)
+    if rows.size != 6 * n or H * W > 2 ** 30 or n * -(-C // 16) > 65535:
+        return False
+    return _warp_rows_supported(np.ascontiguousarray(rows.reshape(n, 6)), H, W)
+
+
+class WarpAffine(torch.autograd.Function):
+    """warp_affine_simple under autograd on this library's kernels: apply(x [n,C,H,W], affine_rows [n,2,3], grid_f64) -> [n,C,H,W].
+    Gradient with respect to x only (the rows are poses, not parameters).  Rows that arrive as a CUDA tensor are brought to the
+    host once, here in the forward: the backward's support rule is a host decision.  Nothing is saved but those 48 n bytes."""
+
+    @staticmethod
+    def forward(ctx, x, affine_rows, grid_f64=True):
+        n = int(x.shape[0])
+        rows = _warp_rows_host(affine_rows, n, "WarpAffine")
+        if not _warp_rows_supported(rows, int(x.shape[2]), int(x.shape[3])):
+            raise _capi.HealAmdError("WarpAffine: the backward kernel does not take these rows (singular, not finite or a reach above "
+                                     "HEAL_WARP_BWD_MAX_REACH): ask ops.warp_affine_train_supported first")
+        ctx.rows, ctx.grid_f64 = rows, bool(grid_f64)
+        WARP_GRAD_CALLS["forward"] += 1
+        return warp_affine(x, rows, grid_f64)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        WARP_GRAD_CALLS["backward"] += 1
+        return warp_affine_backward(grad_out, ctx.rows, ctx.grid_f64), None, None
+
+
 def channel_dot_supported(x):
     return x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and int(x.shape[2] * x.shape[3]) % 4 == 0
 
