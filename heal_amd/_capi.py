@@ -19,6 +19,7 @@ HEADER_EXT = os.path.join(os.path.dirname(HERE), "include", "heal_amd_ext.h")
 HEADER_TRAIN_ATTN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train_attn.h")
 HEADER_TRAIN_BN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train_bn.h")
 HEADER_TRAIN_WARP = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train_warp.h")
+HEADER_CENTER = os.path.join(os.path.dirname(HERE), "include", "heal_amd_center.h")
 
 _lib = None
 
@@ -120,18 +121,29 @@ def signatures_train_warp():
         return parse_prototypes(f.read())
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_center():
+    """{name: (restype, argtypes)} of include/heal_amd_center.h: the anchor-free centre head -- CenterPointLoss with its target
+    assignment, the box map and the decode + NMS front end.  Every build exports them; like signatures_ext() they are outside
+    the versioned inference ABI."""
+    with open(HEADER_CENTER) as f:
+        return parse_prototypes(f.read())
+
+
 def declared_symbols(experimental=False):
     """Function names declared in include/heal_amd.h (the shipped C ABI), or with experimental=True in
     include/heal_amd_experimental.h."""
     return sorted(signatures(bool(experimental)))
 
 
-def header_define(name):
-    """The value of `#define name <integer>` in include/heal_amd.h: the ABI version and the kernels' compile-time limits."""
-    with open(HEADER) as f:
+def header_define(name, header=None):
+    """The value of `#define name <integer>` in include/heal_amd.h (or in `header`): the ABI version and the kernels'
+    compile-time limits."""
+    header = header or HEADER
+    with open(header) as f:
         m = re.search(rf"^[ \t]*#define\s+{name}\s+(\d+)\b", f.read(), re.M)
     if not m:
-        raise HealAmdError(f"{HEADER} does not define {name}")
+        raise HealAmdError(f"{header} does not define {name}")
     return int(m.group(1))
 
 
@@ -153,7 +165,7 @@ def lib():
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**signatures(), **signatures_train(), **signatures_ext(), **signatures_train_attn(),
-                                  **signatures_train_bn(), **signatures_train_warp()}.items():
+                                  **signatures_train_bn(), **signatures_train_warp(), **signatures_center()}.items():
             if not hasattr(L, name):
                 continue  # declared but not built yet -> surfaces in call() / the symbol test
             f = getattr(L, name)

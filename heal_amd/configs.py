@@ -276,6 +276,43 @@ def oldstyle_pointpillar(fusion_method=None, lidar_range=FULL_RANGE, max_cav=5, 
     return load_general_params(h)
 
 
+def lidar_centerpoint(fusion_method="max", lidar_range=FULL_RANGE, max_cav=5, dir_head=False):
+    """Anchor-free centre head on the old-style PointPillars trunk: core_method center_point_baseline with a fusion_method
+    (max | att | v2xvit), or the single-agent center_point with fusion_method=None; center_point_loss as the criterion.
+    The reference ships no CenterPoint YAML: the KEY NAMES are the ones its code reads (center_point_baseline.py:22-77,
+    center_point_loss.py:189-203, :385-396); the VALUES are this project's -- the stride-2 head map of the trunk
+    (out_size_factor 2), CenterPoint's customary max_objs 500, min_radius 2 and gaussian_overlap 0.1, unit code weights."""
+    h = _common(lidar_range, max_cav)
+    voxel_size, factor = [0.4, 0.4, 4], 2
+    args = {"voxel_size": list(voxel_size), "lidar_range": list(lidar_range), "anchor_number": 1, "max_cav": max_cav,
+            "out_size_factor": factor, "backbone_fix": False,
+            "pillar_vfe": {"use_norm": True, "with_distance": False, "use_absolute_xyz": True, "num_filters": [64]},
+            "point_pillar_scatter": {"num_features": 64},
+            "base_bev_backbone": {"layer_nums": [3, 5, 8], "layer_strides": [2, 2, 2], "num_filters": [64, 128, 256],
+                                  "upsample_strides": [1, 2, 4], "num_upsample_filter": [128, 128, 128]},
+            "shrink_header": {"kernal_size": [3], "stride": [1], "padding": [1], "dim": [256], "input_dim": 384}}
+    core = "center_point"
+    if fusion_method is not None:
+        core = "center_point_baseline"
+        args["fusion_method"] = fusion_method
+        if fusion_method == "att":
+            args["att"] = {"feat_dim": 256}
+        elif fusion_method == "v2xvit":
+            args["v2xvit"] = _v2xvit_args()
+        if dir_head:
+            args["dir_args"] = copy.deepcopy(DIR_ARGS)
+    h["name"] = f"heal_amd_{core}"
+    h["model"] = {"core_method": core, "args": args}
+    h["postprocess"]["anchor_args"].update({"r": [0], "num": 1})
+    if not (dir_head and fusion_method is not None):
+        h["postprocess"].pop("dir_args")
+    h["loss"] = {"core_method": "center_point_loss", "args": {
+        "cls_weight": 1.0, "loc_weight": 2.0, "code_weights": [1.0] * 8,
+        "target_assigner_config": {"max_objs": 500, "min_radius": 2, "gaussian_overlap": 0.1, "out_size_factor": factor,
+                                   "voxel_size": list(voxel_size), "cav_lidar_range": list(lidar_range)}}}
+    return load_general_params(h)
+
+
 def lidar_disco_kd(lidar_range=FULL_RANGE, max_cav=5):
     """DiscoNet with distillation (opv2v/LiDAROnly/lidar_disco.yaml): the student `point_pillar_disconet`, the early-fusion
     teacher of `kd_flag` (same architecture arguments, as the YAML's `*model_args` alias) and `point_pillar_disconet_loss` with

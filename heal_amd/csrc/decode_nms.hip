@@ -20,10 +20,13 @@
 // Late fusion (heal_decode_nms_agents; voxel_postprocessor.py:277-405 with several cavs) puts a multi-agent front end before the
 // same tail: k_decode_key_agents decodes the concatenated anchor range of all cavs, each with its own cav -> ego matrix, into ONE
 // candidate list (composite = score key | POOLED index), and k_rank_prepare re-decodes the top-k through the agent table.
+// The centre head (heal_center_decode_nms; :305-306, 3-D reg_preds) has a front end of its own, k_decode_key_center: a cell's box
+// is read from the [H*W, 7] table instead of being decoded from an anchor; everything from the direction correction on is shared.
 #include <string.h>
 #include "prims.h"
 #include "quad_iou.h"
 #include "../../include/heal_amd.h"
+#include "../../include/heal_amd_center.h"
 
 namespace heal {
 
@@ -45,33 +48,11 @@ __device__ __forceinline__ float limit_period_f(float val, float offset, float p
     return val - floorf(val / period + offset) * period;
 }
 
-// Full per-anchor pipeline up to (and including) the size / z filters.
-__device__ __forceinline__ void decode_anchor(const float* __restrict__ cls, const float* __restrict__ reg,
-                                              const float* __restrict__ dir,
-                                              const float* __restrict__ anchors, const DecodeParams& p,
-                                              int j, bool want_corners, Box3D& o) {
+// The part of the pipeline after the box is known: direction correction, 'hwl' corners, projection, size / z filters.
+__device__ __forceinline__ void box_to_corners(const float* __restrict__ dir, const DecodeParams& p, int a, int hw, float x,
+                                               float y, float z, float bh, float bw, float bl, float yaw, bool want_corners,
+                                               Box3D& o) {
     const int HW = p.H * p.W;
-    const int a = j % p.A;
-    const int hw = j / p.A;
-    const float logit = cls[(size_t)a * HW + hw];
-    const float prob = 1.f / (1.f + expf(-logit));
-    o.score = prob;
-    o.pass = false;
-    if (!(prob > p.score_thr)) return;
-    float d[7], an[7];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        d[k] = reg[(size_t)(a * 7 + k) * HW + hw];
-        an[k] = anchors[(size_t)j * 7 + k];
-    }
-    const float ad = sqrtf(an[4] * an[4] + an[5] * an[5]);
-    const float x = d[0] * ad + an[0];
-    const float y = d[1] * ad + an[1];
-    const float z = d[2] * an[3] + an[2];
-    const float bh = expf(d[3]) * an[3];
-    const float bw = expf(d[4]) * an[4];
-    const float bl = expf(d[5]) * an[5];
-    float yaw = d[6] + an[6];
     if (dir != nullptr) {
         int label = 0;
         float best = dir[(size_t)(a * p.num_bins) * HW + hw];
@@ -111,6 +92,48 @@ __device__ __forceinline__ void decode_anchor(const float* __restrict__ cls, con
     o.pass = (x_len <= 6.f) && (y_len <= 6.f) && (y_len != 0.f) && (zmin >= -3.f) && (zmax <= 1.f);
 }
 
+// Full per-anchor pipeline up to (and including) the size / z filters.
+__device__ __forceinline__ void decode_anchor(const float* __restrict__ cls, const float* __restrict__ reg,
+                                              const float* __restrict__ dir,
+                                              const float* __restrict__ anchors, const DecodeParams& p,
+                                              int j, bool want_corners, Box3D& o) {
+    const int HW = p.H * p.W;
+    const int a = j % p.A;
+    const int hw = j / p.A;
+    const float logit = cls[(size_t)a * HW + hw];
+    const float prob = 1.f / (1.f + expf(-logit));
+    o.score = prob;
+    o.pass = false;
+    if (!(prob > p.score_thr)) return;
+    float d[7], an[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        d[k] = reg[(size_t)(a * 7 + k) * HW + hw];
+        an[k] = anchors[(size_t)j * 7 + k];
+    }
+    const float ad = sqrtf(an[4] * an[4] + an[5] * an[5]);
+    const float x = d[0] * ad + an[0];
+    const float y = d[1] * ad + an[1];
+    const float z = d[2] * an[3] + an[2];
+    const float bh = expf(d[3]) * an[3];
+    const float bw = expf(d[4]) * an[4];
+    const float bl = expf(d[5]) * an[5];
+    box_to_corners(dir, p, a, hw, x, y, z, bh, bw, bl, d[6] + an[6], want_corners, o);
+}
+
+// Centre head (heal_center_decode_nms): cell j's box is row j of the [H*W, 7] table (x, y, z, h, w, l, yaw), used as it is
+// (voxel_postprocessor.py:305-306); one score per cell.  Same pipeline from the score threshold on.
+__device__ __forceinline__ void decode_center(const float* __restrict__ cls, const float* __restrict__ boxes,
+                                              const float* __restrict__ dir, const DecodeParams& p, int j, bool want_corners,
+                                              Box3D& o) {
+    const float prob = 1.f / (1.f + expf(-cls[j]));
+    o.score = prob;
+    o.pass = false;
+    if (!(prob > p.score_thr)) return;
+    const float* __restrict__ b = boxes + (size_t)j * 7;
+    box_to_corners(dir, p, 0, j, b[0], b[1], b[2], b[3], b[4], b[5], b[6], want_corners, o);
+}
+
 // One thread per anchor: decode + filters.  Survivors are COMPACTED into a candidate list of 64-bit composites
 // (score key << 32 | anchor index; one wave-aggregated atomic per wave): all composites are distinct, and descending
 // composite order = the reference's order (descending score, ties: larger anchor index first == stable argsort reversed), so
@@ -137,6 +160,22 @@ __global__ __launch_bounds__(256) void k_decode_key(const float* __restrict__ cl
     if (j < n) {
         Box3D b;
         decode_anchor(cls, reg, dir, anchors, p, j, false, b);
+        cand = b.pass;
+        comp = ((unsigned long long)(__float_as_uint(b.score) - p.key_base) << 32) | (unsigned)j;
+    }
+    push_candidate(cand, comp, cand_list, n_cand);
+}
+
+// the same for the centre head: one thread per cell
+__global__ __launch_bounds__(256) void k_decode_key_center(const float* __restrict__ cls, const float* __restrict__ boxes,
+                                                          const float* __restrict__ dir, DecodeParams p, int n,
+                                                          unsigned long long* __restrict__ cand_list, int* __restrict__ n_cand) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    bool cand = false;
+    unsigned long long comp = 0ull;
+    if (j < n) {
+        Box3D b;
+        decode_center(cls, boxes, dir, p, j, false, b);
         cand = b.pass;
         comp = ((unsigned long long)(__float_as_uint(b.score) - p.key_base) << 32) | (unsigned)j;
     }
@@ -291,12 +330,8 @@ struct NmsBufs {
     int* n_cand;
 };
 
-// candidate (anchor j) decoded into slot r of the top-k buffers: corners, BEV quad, score, inside-gt_range flag
-__device__ __forceinline__ void decode_slot(const float* __restrict__ cls, const float* __restrict__ reg,
-                                            const float* __restrict__ dir, const float* __restrict__ anchors,
-                                            const DecodeParams& p, int j, int r, const NmsBufs& nb) {
-    Box3D b;
-    decode_anchor(cls, reg, dir, anchors, p, j, true, b);
+// a decoded candidate into slot r of the top-k buffers: corners, BEV quad, score, inside-gt_range flag
+__device__ __forceinline__ void store_slot(const Box3D& b, const DecodeParams& p, int r, const NmsBufs& nb) {
     bool inside = true;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -315,6 +350,15 @@ __device__ __forceinline__ void decode_slot(const float* __restrict__ cls, const
     nb.inrange[r] = inside ? 1 : 0;
 }
 
+// candidate (anchor j) decoded into slot r
+__device__ __forceinline__ void decode_slot(const float* __restrict__ cls, const float* __restrict__ reg,
+                                            const float* __restrict__ dir, const float* __restrict__ anchors,
+                                            const DecodeParams& p, int j, int r, const NmsBufs& nb) {
+    Box3D b;
+    decode_anchor(cls, reg, dir, anchors, p, j, true, b);
+    store_slot(b, p, r, nb);
+}
+
 // Rank + re-decode of the top candidates in one multi-block launch.  Composites are distinct, so the rank of a candidate in
 // descending order is the number of composites greater than its own: every block copies the candidate list (<= TOPK_CAP entries,
 // a few hundred in practice) into LDS, four threads count a quarter of it each for one candidate, and the candidate is decoded
@@ -326,6 +370,15 @@ struct OneAgent {
     const float *cls, *reg, *dir, *anchors;
     DecodeParams p;
     __device__ __forceinline__ void slot(int j, int r, const NmsBufs& nb) const { decode_slot(cls, reg, dir, anchors, p, j, r, nb); }
+};
+struct CenterCells {        // j is a cell of the centre head's score map (heal_center_decode_nms)
+    const float *cls, *boxes, *dir;
+    DecodeParams p;
+    __device__ __forceinline__ void slot(int j, int r, const NmsBufs& nb) const {
+        Box3D b;
+        decode_center(cls, boxes, dir, p, j, true, b);
+        store_slot(b, p, r, nb);
+    }
 };
 struct PooledAgents {
     const AgentRow* rows;   // [n_agents], written by k_decode_key_agents
@@ -675,6 +728,36 @@ extern "C" int heal_decode_nms(const float* cls, const float* reg, const float* 
     k_decode_key<<<ceil_div(n, 256), 256, 0, s>>>(cls, reg, dir, anchors, p, n, w.cand, w.nb.n_cand);
     const OneAgent src{cls, reg, dir, anchors, p};
     k_rank_prepare<OneAgent><<<TOPK_CAP / RANK_PER_BLOCK, TOPK_THREADS, 0, s>>>(src, w.cand, nms_top, w.nb);
+    return launch_nms_tail(w, nms_top, nms_thr, out_corners, out_scores, out_count, max_out, nullptr, false, s);
+}
+
+// the centre head's front end (include/heal_amd_center.h) before the same tail
+extern "C" int heal_center_decode_nms(const float* cls, const float* boxes, const float* dir, int H, int W, int num_bins,
+                                      float score_thr, float dir_offset, float nms_thr, int nms_top, const float* tfm_host,
+                                      const float* gt_range_host, float* out_corners, float* out_scores, int32_t* out_count,
+                                      int max_out, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    HEAL_REQUIRE(cls && boxes && tfm_host && gt_range_host && out_corners && out_scores && out_count && ws,
+                 "center_decode_nms: null pointer");
+    HEAL_REQUIRE(H >= 1 && W >= 1 && (long long)H * W < (1ll << 31) - 256, "center_decode_nms: bad shape");
+    HEAL_REQUIRE(nms_top >= 1 && nms_top <= 1088, "center_decode_nms: nms_top must be in [1,1088]");
+    HEAL_REQUIRE(dir == nullptr || num_bins >= 1, "center_decode_nms: num_bins must be >= 1");
+    HEAL_REQUIRE(max_out >= 1, "center_decode_nms: max_out must be >= 1");
+    HEAL_REQUIRE(((uintptr_t)ws & 255) == 0, "center_decode_nms: workspace must be 256-B aligned");
+    const int n = H * W;
+    Arena a(ws, ws_bytes);
+    DecWs w;
+    HEAL_REQUIRE(carve(a, n, nms_top, w), "center_decode_nms: workspace too small (%zu < %zu)", ws_bytes, a.off);
+
+    DecodeParams p;
+    fill_shared_params(p, 1, num_bins, score_thr, dir_offset, gt_range_host);
+    p.H = H; p.W = W;
+    for (int k = 0; k < 16; ++k) p.tfm[k] = tfm_host[k];
+
+    HEAL_FILL(w.nb.n_cand, 0, sizeof(int), s);
+    k_decode_key_center<<<ceil_div(n, 256), 256, 0, s>>>(cls, boxes, dir, p, n, w.cand, w.nb.n_cand);
+    const CenterCells src{cls, boxes, dir, p};
+    k_rank_prepare<CenterCells><<<TOPK_CAP / RANK_PER_BLOCK, TOPK_THREADS, 0, s>>>(src, w.cand, nms_top, w.nb);
     return launch_nms_tail(w, nms_top, nms_thr, out_corners, out_scores, out_count, max_out, nullptr, false, s);
 }
 

@@ -1,6 +1,6 @@
 """VoxelPostprocessor (reference: opencood/data_utils/post_processor/voxel_postprocessor.py):
 generate_anchor_box (:30-83) on the host, post_process (:245-405) on the gfx950 decode + rotated-NMS
-kernel K8 (heal_decode_nms), generate_label (:85-207) on heal_label_assign, collate_batch (:210-243) and the
+kernel K8 (heal_decode_nms; heal_center_decode_nms for the anchor-free head's 3-D reg_preds, :305-306), generate_label (:85-207) on heal_label_assign, collate_batch (:210-243) and the
 inherited generate_gt_bbx (base_postprocessor.py:47-107) on the host."""
 import math
 import sys
@@ -207,8 +207,11 @@ class VoxelPostprocessor:
             if 'iou_preds' in out:
                 raise NotImplementedError("iou_preds rescoring is not used by the HEAL configs")
             prob = torch.sigmoid(cls.permute(0, 2, 3, 1)).reshape(1, -1)
-            box3d = self.delta_to_boxes3d(reg, cav['anchor_box'] if isinstance(cav['anchor_box'], torch.Tensor)
-                                          else torch.from_numpy(np.asarray(cav['anchor_box'])))
+            if reg.dim() == 4:      # anchor-based: PointPillars, SECOND
+                box3d = self.delta_to_boxes3d(reg, cav['anchor_box'] if isinstance(cav['anchor_box'], torch.Tensor)
+                                              else torch.from_numpy(np.asarray(cav['anchor_box'])))
+            else:                   # anchor-free: CenterPoint's reg_preds are boxes already (:305-306)
+                box3d = reg.view(1, -1, 7)
             assert box3d.shape[0] == 1
             mask = torch.gt(prob, thr).view(-1)
             boxes3d, scores = box3d[0][mask], prob[0][mask]
@@ -318,10 +321,14 @@ class VoxelPostprocessor:
         dirp = out.get('dir_preds', out.get('dm'))
         if 'iou_preds' in out:
             raise NotImplementedError("iou_preds rescoring is not used by the HEAL configs")
-        anchors = self._anchors_f32(cav['anchor_box'], cls.device)
         tfm = cav['transformation_matrix']
         tfm = tfm.detach().cpu().numpy() if isinstance(tfm, torch.Tensor) else np.asarray(tfm)
         dir_args = self.params.get('dir_args', {'dir_offset': 0.7853, 'num_bins': 2})
+        if reg.dim() == 3:          # anchor-free (CenterPoint, :305-306): reg_preds [1, H*W, 7] are the boxes, no anchor table
+            return ops.center_decode_nms(cls, reg, dirp, self.params['target_args']['score_threshold'], dir_args['dir_offset'],
+                                         dir_args['num_bins'], self.params['nms_thresh'], tfm.astype(np.float32),
+                                         self.params['gt_range'])
+        anchors = self._anchors_f32(cav['anchor_box'], cls.device)
         return ops.decode_nms(cls, reg, dirp, anchors, self.params['target_args']['score_threshold'],
                               dir_args['dir_offset'], dir_args['num_bins'], self.params['nms_thresh'],
                               tfm.astype(np.float32), self.params['gt_range'])

@@ -2558,6 +2558,192 @@ def depth_focal_loss_term(depth_logit, depth_gt_indices, fg_mask=None, alpha=0.2
     return DepthFocalLoss.apply(depth_logit, depth_gt_indices, fg_mask, alpha, weight, _wants_grad(depth_logit))
 
 
+# ------------------------------------------------------------------------------------------------ CP
+# The anchor-free centre head (csrc/center_head.hip, the front end in csrc/decode_nms.hip; include/heal_amd_center.h): the
+# criterion with its target assignment, the box map and decode + NMS.  HEAL_LOSS_FUSED=0 forces the torch composition of
+# heal_amd/opencood/loss/center_point_loss.py (scripts/center_bench.py).
+CENTER_MAX_OBJS = _limit("HEAL_CENTER_MAX_OBJS", _capi.HEADER_CENTER)
+CENTER_MAX_BATCH = _limit("HEAL_CENTER_MAX_BATCH", _capi.HEADER_CENTER)
+
+
+def _doubles(values, n, name, who):
+    values = [float(v) for v in values]
+    if len(values) != n:
+        raise _capi.HealAmdError(f"{who}: {name} must have {n} values, got {len(values)}")
+    return (ctypes.c_double * n)(*values)
+
+
+def _center_shapes(cls_preds, bbox_preds, object_bbx_center, object_bbx_mask):
+    """(B, Mmax, H, W) of a centre-head problem, or None where the tensors are not one: CUDA fp32 maps [B, 1, H, W] and [B, 8, H, W],
+    boxes [B, Mmax, 7] (floating point) and mask [B, Mmax] on the same device."""
+    if not (_loss_map_ok(cls_preds) and _loss_map_ok(bbox_preds)):
+        return None
+    B, A, H, W = (int(v) for v in cls_preds.shape)
+    dev = cls_preds.device
+    if A != 1 or tuple(bbox_preds.shape) != (B, 8, H, W) or bbox_preds.device != dev:
+        return None
+    if not (isinstance(object_bbx_center, torch.Tensor) and isinstance(object_bbx_mask, torch.Tensor)
+            and object_bbx_center.device == dev and object_bbx_mask.device == dev and object_bbx_center.is_floating_point()
+            and object_bbx_center.dim() == 3 and int(object_bbx_center.shape[0]) == B and int(object_bbx_center.shape[2]) == 7
+            and tuple(object_bbx_mask.shape) == tuple(object_bbx_center.shape[:2]) and object_bbx_center.shape[1] >= 1):
+        return None
+    return B, int(object_bbx_center.shape[1]), H, W
+
+
+def center_loss_supported(cls_preds, bbox_preds, object_bbx_center, object_bbx_mask, cav_lidar_range, voxel_size,
+                          out_size_factor, max_objs):
+    """The fused CenterPointLoss: CUDA fp32 maps [B, 1, H, W] and [B, 8, H, W] with (H, W) the feature map of the range, the voxel
+    size and the factor, boxes [B, Mmax, 7] and mask [B, Mmax] on the same device, max_objs <= CENTER_MAX_OBJS
+    (heal_center_loss_supported).  HEAL_LOSS_FUSED=0 forces the composition."""
+    if not loss_fused_enabled():
+        return False
+    shapes = _center_shapes(cls_preds, bbox_preds, object_bbx_center, object_bbx_mask)
+    if shapes is None or len(cav_lidar_range) != 6 or len(voxel_size) != 3:
+        return False
+    B, Mmax, H, W = shapes
+    return bool(_capi.query("heal_center_loss_supported", B, Mmax, H, W, _doubles(cav_lidar_range, 6, "cav_lidar_range", "center_loss"),
+                            _doubles(voxel_size, 3, "voxel_size", "center_loss"), int(out_size_factor), int(max_objs)))
+
+
+def center_loss(cls_preds, bbox_preds, object_bbx_center, object_bbx_mask, cav_lidar_range, voxel_size, out_size_factor, max_objs,
+                min_radius, gaussian_overlap, code_weights, cls_weight, loc_weight, need_grad=True, grad_out=None, debug=False,
+                workspace=None):
+    """CP.  CenterPointLoss.forward, target assignment included, in one call: cls_preds [B, 1, H, W], bbox_preds [B, 8, H, W] f32
+    cuda (made contiguous); object_bbx_center [B, Mmax, 7] (cast to float32 as the reference does) and object_bbx_mask [B, Mmax]
+    (cast to int32) stay on the device.  -> (terms [2] = cls, reg loss, (grad_cls, grad_bbox) | None), with debug=True also a
+    dict of the assigned targets: heatmap [B, 1, H, W], anno_boxes [B, max_objs, 8], inds [B, max_objs] int64, masks
+    [B, max_objs] uint8.  need_grad: bool or one per map; False passes NULL gradients.  grad_out: buffers to write into.
+    workspace: a uint8 buffer to use instead of the operator's own (the tests hand in a poisoned one)."""
+    who = "center_loss"
+    shapes = _center_shapes(cls_preds, bbox_preds, object_bbx_center, object_bbx_mask)
+    if shapes is None:
+        raise _capi.HealAmdError(f"{who}: needs CUDA/HIP f32 maps [B, 1, H, W] and [B, 8, H, W], boxes [B, Mmax, 7] and a mask "
+                                 "[B, Mmax] on the same device (heal_amd has no CPU path)")
+    B, Mmax, H, W = shapes
+    (cls_preds, bbox_preds), _ = _loss_inputs(who, (("cls_preds", cls_preds), ("bbox_preds", bbox_preds)), ())
+    dev = cls_preds.device
+    boxes = object_bbx_center.detach().to(torch.float32).contiguous()
+    mask = object_bbx_mask.detach().to(torch.int32).contiguous()
+    rng, vox = _doubles(cav_lidar_range, 6, "cav_lidar_range", who), _doubles(voxel_size, 3, "voxel_size", who)
+    cw = _doubles(code_weights, 8, "code_weights", who)
+    max_objs = int(max_objs)
+    if not _capi.query("heal_center_loss_supported", B, Mmax, H, W, rng, vox, int(out_size_factor), max_objs):
+        raise _capi.HealAmdError(f"{who}: maps {(B, H, W)} with max_objs {max_objs} (<= {CENTER_MAX_OBJS}) are out of range, or "
+                                 "(H, W) is not the feature map of cav_lidar_range / voxel_size / out_size_factor")
+    grads = _loss_grad_buffers(who, (cls_preds, bbox_preds), need_grad, grad_out)
+    nbytes = _capi.query("heal_center_loss_workspace", B, H, W, max_objs)
+    if workspace is not None:
+        if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= nbytes
+                and workspace.data_ptr() % 256 == 0):
+            raise _capi.HealAmdError(f"{who}: workspace must be a contiguous 256-B aligned uint8 CUDA tensor of >= {nbytes} bytes")
+        ws = workspace
+    else:
+        ws = _workspace("center_loss", nbytes, dev)
+    terms = torch.empty(2, dtype=torch.float32, device=dev)
+    dbg = None
+    if debug:
+        dbg = {"heatmap": torch.empty((B, 1, H, W), dtype=torch.float32, device=dev),
+               "anno_boxes": torch.empty((B, max_objs, 8), dtype=torch.float32, device=dev),
+               "inds": torch.empty((B, max_objs), dtype=torch.int64, device=dev),
+               "masks": torch.empty((B, max_objs), dtype=torch.uint8, device=dev)}
+    opt = (lambda k: _ptr(dbg[k])) if dbg is not None else (lambda k: ctypes.c_void_p(0))
+    moved = 4.0 * (cls_preds.numel() + bbox_preds.numel()) + sum(4.0 * g.numel() for g in grads if g is not None) \
+        + 4.0 * (boxes.numel() + mask.numel())
+    with _Timed("center_loss", nbytes=moved):
+        _capi.call("heal_center_loss", _ptr(cls_preds), _ptr(bbox_preds), _ptr(boxes), _ptr(mask), B, Mmax, H, W, rng, vox,
+                   int(out_size_factor), max_objs, int(min_radius), float(gaussian_overlap), cw, float(cls_weight),
+                   float(loc_weight), _ptr(terms), _ptr(grads[0]), _ptr(grads[1]), opt("heatmap"), opt("anno_boxes"), opt("inds"),
+                   opt("masks"), _ptr(ws), ctypes.c_size_t(nbytes), _stream())
+    grads = tuple(grads) if any(g is not None for g in grads) else None
+    return (terms, grads, dbg) if debug else (terms, grads)
+
+
+class CenterLoss(torch.autograd.Function):
+    """center_loss under autograd: forward = heal_center_loss, which also writes d term / d map (saved); backward scales each by
+    the incoming gradient of its term.  The boxes and the mask receive none."""
+
+    @staticmethod
+    def forward(ctx, cls_preds, bbox_preds, boxes, mask, cfg, need):
+        terms, grads = center_loss(cls_preds, bbox_preds, boxes, mask, need_grad=need, **cfg)
+        grads = grads if grads is not None else (None, None)
+        ctx.have = tuple(g is not None for g in grads)
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        return terms
+
+    @staticmethod
+    def backward(ctx, grad_terms):
+        saved = list(ctx.saved_tensors)
+        out = [grad_terms[i] * saved.pop(0) if have else None for i, have in enumerate(ctx.have)]
+        return (*out, None, None, None, None)
+
+
+def center_loss_terms(cls_preds, bbox_preds, object_bbx_center, object_bbx_mask, **cfg):
+    """The differentiable form of center_loss: -> terms [2] (cls, reg), gradients for the maps that require one."""
+    need = tuple(_wants_grad(t) for t in (cls_preds, bbox_preds))
+    return CenterLoss.apply(cls_preds, bbox_preds, object_bbx_center, object_bbx_mask, cfg, need)
+
+
+def center_boxes(bbox_preds, cav_lidar_range, voxel_size, out_size_factor):
+    """CP.  generate_predicted_boxes: bbox_preds [B, 8, H, W] f32 cuda -> reg_preds [B, H*W, 7] = (x, y, z, h, w, l, yaw) in
+    metres, one streaming launch.  No gradient flows through it (the criterion reads bbox_preds): the input is detached."""
+    who = "center_boxes"
+    if not _loss_map_ok(bbox_preds) or int(bbox_preds.shape[1]) != 8:
+        raise _capi.HealAmdError(f"{who}: bbox_preds must be a CUDA/HIP f32 map [B, 8, H, W] (heal_amd has no CPU path; the "
+                                 "reference's reshape only lines up for anchor_number 1)")
+    x = bbox_preds.detach().contiguous()
+    B, _, H, W = (int(v) for v in x.shape)
+    out = torch.empty((B, H * W, 7), dtype=torch.float32, device=x.device)
+    with _Timed("center_boxes", nbytes=4.0 * (x.numel() + out.numel()), kernel_events=True):
+        _capi.call("heal_center_boxes", _ptr(x), B, H, W, _doubles(cav_lidar_range, 6, "cav_lidar_range", who),
+                   _doubles(voxel_size, 3, "voxel_size", who), int(out_size_factor), _ptr(out), _stream())
+    return out
+
+
+def center_decode_nms(cls, boxes, dirp, score_thr, dir_offset, num_bins, nms_thr, tfm, gt_range, nms_top=1000, sync=True):
+    """K8 for the centre head.  cls [1,1,H,W] (or [1,H,W]), boxes [1,H*W,7] (or [H*W,7]: the 3-D reg_preds), dirp
+    [1,bins,H,W] or None, f32 cuda.  -> as decode_nms."""
+    who = "center_decode_nms"
+    cls = _need(cls, torch.float32, "cls_preds")
+    boxes = _need(boxes, torch.float32, "reg_preds")
+    if dirp is not None:
+        dirp = _need(dirp, torch.float32, "dir_preds")
+    if cls.dim() == 4:
+        if cls.shape[0] != 1:
+            raise _capi.HealAmdError(f"{who}: batch size must be 1 (voxel_postprocessor.py:314)")
+        cls = cls[0]
+        dirp = dirp[0] if dirp is not None else None
+    if boxes.dim() == 3:
+        if boxes.shape[0] != 1:
+            raise _capi.HealAmdError(f"{who}: batch size must be 1 (voxel_postprocessor.py:314)")
+        boxes = boxes[0]
+    A, H, W = (int(v) for v in cls.shape)
+    if A != 1 or tuple(boxes.shape) != (H * W, 7):
+        raise _capi.HealAmdError(f"{who}: scores {tuple(cls.shape)} and boxes {tuple(boxes.shape)} are not [1, H, W] and "
+                                 "[H*W, 7] (one box per cell: anchor_number 1)")
+    if dirp is not None and tuple(dirp.shape) != (int(num_bins), H, W):
+        raise _capi.HealAmdError(f"{who}: dir_preds {tuple(dirp.shape)} is not [{int(num_bins)}, {H}, {W}]")
+    dev = cls.device
+    out_c = torch.empty((nms_top, 8, 3), dtype=torch.float32, device=dev)
+    out_s = torch.empty((nms_top,), dtype=torch.float32, device=dev)
+    out_n = torch.zeros((1,), dtype=torch.int32, device=dev)
+    nbytes = _capi.query("heal_decode_nms_workspace", H * W, int(nms_top))
+    ws = _workspace("decode_nms", nbytes, dev)
+    t = _host_array([float(v) for v in np.asarray(tfm, dtype=np.float32).reshape(-1)], ctypes.c_float)
+    g = _host_array([float(v) for v in gt_range], ctypes.c_float)
+    with _Timed("center_decode_nms"):
+        _capi.call("heal_center_decode_nms", _ptr(cls), _ptr(boxes), _ptr(dirp), H, W, int(num_bins), float(score_thr),
+                   float(dir_offset), float(nms_thr), int(nms_top), t, g, _ptr(out_c), _ptr(out_s), _ptr(out_n), int(nms_top),
+                   _ptr(ws), ws.numel(), _stream())
+    _remember("center_decode_nms", lambda: center_decode_nms(cls, boxes, dirp, score_thr, dir_offset, num_bins, nms_thr, tfm,
+                                                             gt_range, nms_top, sync=False))
+    if not sync:
+        return out_c, out_s, out_n
+    k = int(out_n.item())
+    if k == 0:
+        return None, None
+    return out_c[:k], out_s[:k]
+
+
 # ------------------------------------------------------------------------------------------------ K6c
 def ln_stats(x, eps):
     """(mean, rstd) of every token of x [..., C] -> [T, 2] f32: the statistics half of a LayerNorm whose application is
