@@ -20,6 +20,7 @@ HEADER_TRAIN_ATTN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_tra
 HEADER_TRAIN_BN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train_bn.h")
 HEADER_TRAIN_WARP = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train_warp.h")
 HEADER_CENTER = os.path.join(os.path.dirname(HERE), "include", "heal_amd_center.h")
+HEADER_COMM = os.path.join(os.path.dirname(HERE), "include", "heal_amd_comm.h")
 
 _lib = None
 
@@ -130,6 +131,15 @@ def signatures_center():
         return parse_prototypes(f.read())
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_comm():
+    """{name: (restype, argtypes)} of include/heal_amd_comm.h: Where2comm's communication mask (heal_comm_mask with its host-side
+    support and workspace rules) and the masked form of the multiscale warp + attention fusion.  Every build exports them; like
+    signatures_ext() they are outside the versioned inference ABI."""
+    with open(HEADER_COMM) as f:
+        return parse_prototypes(f.read())
+
+
 def declared_symbols(experimental=False):
     """Function names declared in include/heal_amd.h (the shipped C ABI), or with experimental=True in
     include/heal_amd_experimental.h."""
@@ -165,7 +175,8 @@ def lib():
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**signatures(), **signatures_train(), **signatures_ext(), **signatures_train_attn(),
-                                  **signatures_train_bn(), **signatures_train_warp(), **signatures_center()}.items():
+                                  **signatures_train_bn(), **signatures_train_warp(), **signatures_center(),
+                                  **signatures_comm()}.items():
             if not hasattr(L, name):
                 continue  # declared but not built yet -> surfaces in call() / the symbol test
             f = getattr(L, name)

@@ -313,6 +313,34 @@ def lidar_centerpoint(fusion_method="max", lidar_range=FULL_RANGE, max_cav=5, di
     return load_general_params(h)
 
 
+def lidar_centerpoint_where2comm(agg="ATTEN", multi_scale=True, backbone="resnet", communication=True, lidar_range=FULL_RANGE,
+                                 max_cav=5, thre=0.01, k_size=5, c_sigma=1.0):
+    """core_method center_point_where2comm: lidar_centerpoint's trunk, heads and criterion with Where2comm's spatially masked
+    fusion (`fusion_args`).  agg: ATTEN | MAX (agg_operator.mode); multi_scale: the fusion runs per backbone level on the canvas
+    (downsample_rate 1: the affine matrix is normalised with the canvas size) or once on the stride-2 output map
+    (downsample_rate 2); backbone: "resnet" (`base_bev_backbone.resnet`: every level from the unmasked input) | "plain" (the
+    masked level feeds the next block); communication: False leaves the `communication` entry out (no mask, rate 0).
+    The reference ships no YAML for this model: the KEY NAMES are the ones its code reads (center_point_where2comm.py:17-54,
+    where2comm_attn.py:178-217, comm_modules/where2comm.py:13-21); the VALUES (thre 0.01, a 5 x 5 filter with sigma 1) are this project's
+    defaults, to be replaced by a checkpoint's own."""
+    if backbone not in ("resnet", "plain"):
+        raise ValueError(f"backbone must be 'resnet' or 'plain', got {backbone!r}")
+    h = lidar_centerpoint(None, lidar_range, max_cav)
+    args = h["model"]["args"]
+    bb = args["base_bev_backbone"]
+    if backbone == "resnet":
+        bb["resnet"] = True
+    fusion = {"voxel_size": list(args["voxel_size"]), "downsample_rate": 1 if multi_scale else 2, "in_channels": 256,
+              "multi_scale": bool(multi_scale), "layer_nums": list(bb["layer_nums"]), "num_filters": list(bb["num_filters"]),
+              "agg_operator": {"mode": agg, "feature_dim": 256}}
+    if communication:
+        fusion["communication"] = {"thre": thre, "gaussian_smooth": {"k_size": k_size, "c_sigma": c_sigma}}
+    args["fusion_args"] = fusion
+    h["name"] = "heal_amd_center_point_where2comm"
+    h["model"]["core_method"] = "center_point_where2comm"
+    return h
+
+
 def lidar_disco_kd(lidar_range=FULL_RANGE, max_cav=5):
     """DiscoNet with distillation (opv2v/LiDAROnly/lidar_disco.yaml): the student `point_pillar_disconet`, the early-fusion
     teacher of `kd_flag` (same architecture arguments, as the YAML's `*model_args` alias) and `point_pillar_disconet_loss` with

@@ -21,6 +21,7 @@
 #include "common.h"
 #include "warp_taps.h"
 #include "../../include/heal_amd.h"
+#include "../../include/heal_amd_comm.h"
 
 namespace heal {
 
@@ -614,9 +615,15 @@ struct WaLevels {
     double m[WF_MAXA][6];
 };
 
-template <int NA>
-__global__ __launch_bounds__(WA_THREADS) void k_warp_att_fuse(const WaLevels P) {
-    __shared__ float s_dot[NA * WA_THREADS];     // [slice][agent][pixel]
+// The masked form (heal_warp_att_fuse_levels_masked, include/heal_amd_comm.h): one mask [n_agents, 1, H, W] per level.  A thread reads
+// the mask at its four taps per agent once, next to the tap weights, and every sampled value is src * mask before it is weighted:
+// the arithmetic of the unmasked kernel on premultiplied maps.  MASKED = false is the unmasked kernel, instruction for instruction.
+struct WaMasks {
+    const float* m[WL_MAXL];
+};
+
+template <int NA, bool MASKED>
+__device__ __forceinline__ void warp_att_fuse_body(const WaLevels& P, const WaMasks* M, float* s_dot) {
     int lvl = 0;
 #pragma unroll
     for (int i = 1; i < WL_MAXL; ++i)
@@ -631,6 +638,7 @@ __global__ __launch_bounds__(WA_THREADS) void k_warp_att_fuse(const WaLevels P) 
     const int HW = L.H * L.W;
     int off[NA][4];
     float wt[NA][4];
+    float mk[MASKED ? NA : 1][4];
     unsigned reach = 0;      // bit a: some lane of this wave samples agent a inside its map
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
@@ -652,6 +660,11 @@ __global__ __launch_bounds__(WA_THREADS) void k_warp_att_fuse(const WaLevels P) 
                 wt[a][k] = ok ? t.w[k] : 0.f;
             }
         }
+        if constexpr (MASKED) {
+            const float* mp = M->m[lvl] + (size_t)a * HW;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) mk[a][k] = mp[off[a][k]];     // off is 0 (a valid address) where the tap has no weight
+        }
         const bool any = (wt[a][0] != 0.f) | (wt[a][1] != 0.f) | (wt[a][2] != 0.f) | (wt[a][3] != 0.f);
         reach |= __ballot(any) ? (1u << a) : 0u;
     }
@@ -660,11 +673,19 @@ __global__ __launch_bounds__(WA_THREADS) void k_warp_att_fuse(const WaLevels P) 
 
     auto tap4 = [&](int a, int c) -> float {      // sample(): nw, ne, sw, se accumulated in that order
         const float* src = L.feats + ((size_t)a * L.C + c) * HW;
-        float v = src[off[a][0]] * wt[a][0];
-        v += src[off[a][1]] * wt[a][1];
-        v += src[off[a][2]] * wt[a][2];
-        v += src[off[a][3]] * wt[a][3];
-        return v;
+        if constexpr (MASKED) {
+            float v = (src[off[a][0]] * mk[a][0]) * wt[a][0];
+            v += (src[off[a][1]] * mk[a][1]) * wt[a][1];
+            v += (src[off[a][2]] * mk[a][2]) * wt[a][2];
+            v += (src[off[a][3]] * mk[a][3]) * wt[a][3];
+            return v;
+        } else {
+            float v = src[off[a][0]] * wt[a][0];
+            v += src[off[a][1]] * wt[a][1];
+            v += src[off[a][2]] * wt[a][2];
+            v += src[off[a][3]] * wt[a][3];
+            return v;
+        }
     };
 
     float prob[NA];
@@ -720,6 +741,18 @@ __global__ __launch_bounds__(WA_THREADS) void k_warp_att_fuse(const WaLevels P) 
         }
         if (live) L.out[(size_t)c * HW + pix] = acc;
     }
+}
+
+template <int NA>
+__global__ __launch_bounds__(WA_THREADS) void k_warp_att_fuse(const WaLevels P) {
+    __shared__ float s_dot[NA * WA_THREADS];     // [slice][agent][pixel]
+    warp_att_fuse_body<NA, false>(P, nullptr, s_dot);
+}
+
+template <int NA>
+__global__ __launch_bounds__(WA_THREADS) void k_warp_att_fuse_masked(const WaLevels P, const WaMasks M) {
+    __shared__ float s_dot[NA * WA_THREADS];
+    warp_att_fuse_body<NA, true>(P, &M, s_dot);
 }
 
 static int fill_params(WarpParams& p, int n_agents, int C, int H, int W, const double* affine_host,
@@ -896,10 +929,11 @@ extern "C" int heal_warp_fuse_levels_src(int n_levels, const heal_k5_source* src
                                    affine_dev, grid_f64, crop_host, out_host, stream);
 }
 
-extern "C" int heal_warp_att_fuse_levels(int n_levels, const float* const* feats_host, int n_agents, const int32_t* channels_host,
-                                         const int32_t* h_host, const int32_t* w_host, const float* sqrt_dim_host,
-                                         const double* affine_host, const double* affine_dev, int grid_f64, int mode,
-                                         float* const* out_host, void* stream) {
+// heal_warp_att_fuse_levels and its masked form: the same checks and launch descriptor; mask_host null = the unmasked kernel.
+static int launch_warp_att_fuse_levels(int n_levels, const float* const* feats_host, const float* const* mask_host, int n_agents,
+                                       const int32_t* channels_host, const int32_t* h_host, const int32_t* w_host,
+                                       const float* sqrt_dim_host, const double* affine_host, const double* affine_dev, int grid_f64,
+                                       int mode, float* const* out_host, void* stream) {
     HEAL_REQUIRE(n_levels >= 1 && n_levels <= WL_MAXL, "warp_att_fuse_levels: 1..%d levels per launch (got %d)", WL_MAXL, n_levels);
     HEAL_REQUIRE(n_agents >= 1 && n_agents <= WF_MAXA, "warp_att_fuse_levels: n_agents must be in [1,%d] (got %d)", WF_MAXA, n_agents);
     HEAL_REQUIRE(mode == 0 || mode == 1, "warp_att_fuse_levels: mode must be 0 (attention) or 1 (max), got %d", mode);
@@ -928,6 +962,20 @@ extern "C" int heal_warp_att_fuse_levels(int n_levels, const float* const* feats
     }
     HEAL_REQUIRE(blocks < (1ll << 30), "warp_att_fuse_levels: grid too large");
     hipStream_t st = (hipStream_t)stream;
+    if (mask_host) {
+        WaMasks M;
+        for (int l = 0; l < WL_MAXL; ++l) {
+            M.m[l] = mask_host[l < n_levels ? l : 0];
+            HEAL_REQUIRE(M.m[l], "warp_att_fuse_levels_masked: mask of level %d is NULL", l);
+        }
+        switch (n_agents) {
+#define HEAL_WAF(N) case N: HEAL_LAUNCH_EV(k_warp_att_fuse_masked<N>, dim3((unsigned)blocks), dim3(WA_THREADS), 0, st, P, M); break;
+            HEAL_WAF(1) HEAL_WAF(2) HEAL_WAF(3) HEAL_WAF(4) HEAL_WAF(5) HEAL_WAF(6) HEAL_WAF(7) HEAL_WAF(8)
+#undef HEAL_WAF
+        }
+        HEAL_LAUNCH_CHECK();
+        return 0;
+    }
     switch (n_agents) {
 #define HEAL_WAF(N) case N: HEAL_LAUNCH_EV(k_warp_att_fuse<N>, dim3((unsigned)blocks), dim3(WA_THREADS), 0, st, P); break;
         HEAL_WAF(1) HEAL_WAF(2) HEAL_WAF(3) HEAL_WAF(4) HEAL_WAF(5) HEAL_WAF(6) HEAL_WAF(7) HEAL_WAF(8)
@@ -935,6 +983,24 @@ extern "C" int heal_warp_att_fuse_levels(int n_levels, const float* const* feats
     }
     HEAL_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int heal_warp_att_fuse_levels(int n_levels, const float* const* feats_host, int n_agents, const int32_t* channels_host,
+                                         const int32_t* h_host, const int32_t* w_host, const float* sqrt_dim_host,
+                                         const double* affine_host, const double* affine_dev, int grid_f64, int mode,
+                                         float* const* out_host, void* stream) {
+    return launch_warp_att_fuse_levels(n_levels, feats_host, nullptr, n_agents, channels_host, h_host, w_host, sqrt_dim_host,
+                                       affine_host, affine_dev, grid_f64, mode, out_host, stream);
+}
+
+extern "C" int heal_warp_att_fuse_levels_masked(int n_levels, const float* const* feats_host, const float* const* mask_host,
+                                                int n_agents, const int32_t* channels_host, const int32_t* h_host,
+                                                const int32_t* w_host, const float* sqrt_dim_host, const double* affine_host,
+                                                const double* affine_dev, int grid_f64, int mode, float* const* out_host,
+                                                void* stream) {
+    HEAL_REQUIRE(mask_host, "warp_att_fuse_levels_masked: mask_host is NULL");
+    return launch_warp_att_fuse_levels(n_levels, feats_host, mask_host, n_agents, channels_host, h_host, w_host, sqrt_dim_host,
+                                       affine_host, affine_dev, grid_f64, mode, out_host, stream);
 }
 
 extern "C" int heal_warp_agent(const float* feat, const float* occ, int channels, int H, int W,

@@ -896,6 +896,10 @@ def make_sharded(model, rank, world, wire_dtype=None, collective=None, split=Non
                 and switches.on("HEAL_V2XVIT_STRIPES")):
             return ShardedBaselineStriped(model, rank, world, wire_dtype, collective)
         return ShardedBaseline(model, rank, world, wire_dtype, collective)
+    if name == "CenterPointWhere2comm":
+        raise NotImplementedError("no agent-sharded split for CenterPointWhere2comm: its communication masks come from the heads on "
+                                  "every agent's UNWARPED map (center_point_where2comm.py:122-131) and gate the maps before the warp, "
+                                  "which the warp-then-gather exchange does not carry")
     raise NotImplementedError(f"no agent-sharded split for {name}")
 
 

@@ -709,13 +709,15 @@ def warp_fuse_levels_src(sources, shapes, affine_rows, grid_f64=True, crops=None
 WARP_ATT_MAX_AGENTS, WARP_ATT_MAX_LEVELS = WARP_MAX_AGENTS, WARP_MAX_LEVELS
 
 
-def warp_att_fuse_levels(feats_list, affine_rows, grid_f64=True, mode="att", sqrt_dims=None, outs=None):
+def warp_att_fuse_levels(feats_list, affine_rows, grid_f64=True, mode="att", sqrt_dims=None, outs=None, masks=None):
     """CoAlign's multiscale fusion for every level of one scene in ONE launch (heal_warp_att_fuse_levels): per ego pixel the
     agents' maps are warped into the ego frame (agent 0 included) and reduced with the ego row of the per-pixel agent attention
     (mode "att": softmax_j(x_0 . x_j / sqrt_dim) weights) or the maximum over agents (mode "max").
     feats_list[l] [n,C_l,H_l,W_l] fp32, affine_rows [n,2,3] (host array or CUDA tensor read at run time, shared by the levels),
     sqrt_dims[l]: the divisor of the logits (None: sqrt(C_l)) -> list of [C_l,H_l,W_l] (outs[l] when the caller gives the
-    destinations: one contiguous fp32 tensor of that shape per level, on the level's device)."""
+    destinations: one contiguous fp32 tensor of that shape per level, on the level's device).
+    masks[l] [n,1,H_l,W_l] fp32 (Where2comm's communication masks; None: no masking): heal_warp_att_fuse_levels_masked, every
+    tap of agent j times the mask value at that tap -- the result on maps premultiplied by their masks, which are never written."""
     if mode not in ("att", "max"):
         raise _capi.HealAmdError(f"warp_att_fuse_levels: mode must be 'att' or 'max', got {mode!r}")
     L = len(feats_list)
@@ -733,6 +735,14 @@ def warp_att_fuse_levels(feats_list, affine_rows, grid_f64=True, mode="att", sqr
         raise _capi.HealAmdError(f"warp_att_fuse_levels: {len(sqrt_dims)} sqrt_dims for {L} levels")
     if outs is not None and len(outs) != L:
         raise _capi.HealAmdError(f"warp_att_fuse_levels: {len(outs)} outs for {L} levels")
+    if masks is not None:                                   # the same checks as the feature maps, before anything is launched
+        if len(masks) != L:
+            raise _capi.HealAmdError(f"warp_att_fuse_levels: {len(masks)} masks for {L} levels")
+        masks = [_need(m, torch.float32, "masks") for m in masks]
+        for l, (m, f) in enumerate(zip(masks, feats_list)):
+            if tuple(m.shape) != (n, 1, int(f.shape[2]), int(f.shape[3])) or m.device != f.device:
+                raise _capi.HealAmdError(f"warp_att_fuse_levels: level {l}: the mask is {tuple(m.shape)} on {m.device}, want "
+                                         f"{(n, 1, int(f.shape[2]), int(f.shape[3]))} on {f.device}")
     given, outs, nbytes = outs, [], 0.0
     for l, f in enumerate(feats_list):                      # every destination is checked before anything is launched
         C, H, W = (int(v) for v in f.shape[1:])
@@ -742,12 +752,80 @@ def warp_att_fuse_levels(feats_list, affine_rows, grid_f64=True, mode="att", sqr
     sd = [float(np.float32(np.sqrt(int(f.shape[1])) if sqrt_dims is None else sqrt_dims[l])) for l, f in enumerate(feats_list)]
     fp = _host_array([f.data_ptr() for f in feats_list], ctypes.c_void_p)
     yp = _host_array([y.data_ptr() for y in outs], ctypes.c_void_p)
+    shape = (_host_array([int(f.shape[1]) for f in feats_list], ctypes.c_int32),
+             _host_array([int(f.shape[2]) for f in feats_list], ctypes.c_int32),
+             _host_array([int(f.shape[3]) for f in feats_list], ctypes.c_int32), _host_array(sd, ctypes.c_float))
+    if masks is not None:
+        nbytes += sum(4.0 * m.numel() for m in masks)
+        _capi.guard_note("heal_warp_att_fuse_levels_masked", [t.data_ptr() for t in feats_list + masks + outs])
+        with _Timed("warp_att_fuse_levels_masked", 0.0, nbytes, kernel_events=True):
+            _capi.call("heal_warp_att_fuse_levels_masked", L, fp, _host_array([m.data_ptr() for m in masks], ctypes.c_void_p), n,
+                       *shape, ap, adev, int(bool(grid_f64)), 0 if mode == "att" else 1, yp, _stream())
+        return outs
     with _Timed("warp_att_fuse_levels", 0.0, nbytes, kernel_events=True):
-        _capi.call("heal_warp_att_fuse_levels", L, fp, n, _host_array([int(f.shape[1]) for f in feats_list], ctypes.c_int32),
-                   _host_array([int(f.shape[2]) for f in feats_list], ctypes.c_int32),
-                   _host_array([int(f.shape[3]) for f in feats_list], ctypes.c_int32), _host_array(sd, ctypes.c_float),
+        _capi.call("heal_warp_att_fuse_levels", L, fp, n, *shape,
                    ap, adev, int(bool(grid_f64)), 0 if mode == "att" else 1, yp, _stream())
     return outs
+
+
+COMM_MAX_K = _capi.header_define("HEAL_COMM_MAX_K", _capi.HEADER_COMM)
+COMM_MAX_AGENTS = _capi.header_define("HEAL_COMM_MAX_AGENTS", _capi.HEADER_COMM)
+
+
+def comm_fused_enabled():
+    """HEAL_COMM_FUSED as the library reads it (heal_comm_fused_enabled: the variable is one of the library's own, declared as such
+    in heal_amd/switches.py): False for "0" -- Where2comm then runs the reference's torch composition on the device."""
+    v = int(_capi.lib().heal_comm_fused_enabled())
+    if v < 0:
+        raise _capi.HealAmdError("HEAL_COMM_FUSED is not a valid setting: expected 0 or 1")
+    return v == 1
+
+
+def comm_mask(psm, record_len, weight, bias, thre, n_levels=1):
+    """CM.  Where2comm's communication masks of every scene of a batch and every pyramid level in one pass (heal_comm_mask;
+    comm_modules/where2comm.py:34-78 with the max_pool2d per level of where2comm_attn.py:264-275).
+    psm [n_total, A, H, W] f32 cuda confidence logits, record_len the agents per scene (a list, or a tensor read on the host),
+    weight [.., k, k] and bias [1] the smoothing filter's parameters on the device (weight None: no smoothing), thre the threshold
+    -> (masks: list of [n_total, 1, H >> l, W >> l] f32 zeros and ones with the even-agent override applied,
+        count [B] int32: the ones of each scene's first agent before the override,
+        rate [] f32: mean over scenes of count / (H W)).  No gradient flows through it (the reference's mask has none either)."""
+    who = "comm_mask"
+    if not isinstance(psm, torch.Tensor) or not psm.is_cuda or psm.dtype != torch.float32 or psm.dim() != 4:
+        raise _capi.HealAmdError(f"{who}: psm must be a CUDA/HIP f32 map [n_total, A, H, W] (heal_amd has no CPU path)")
+    x = psm.detach().contiguous()
+    n_total, A, H, W = (int(v) for v in x.shape)
+    lens = [int(v) for v in (record_len.tolist() if isinstance(record_len, torch.Tensor) else record_len)]
+    if not lens or min(lens) < 1 or sum(lens) != n_total:
+        raise _capi.HealAmdError(f"{who}: record_len {lens} does not sum to the {n_total} agents of psm")
+    k = 1
+    if weight is not None:
+        if bias is None:
+            raise _capi.HealAmdError(f"{who}: a filter weight without a bias")
+        for t, name in ((weight, "weight"), (bias, "bias")):
+            if not isinstance(t, torch.Tensor) or t.device != x.device or t.dtype != torch.float32:
+                raise _capi.HealAmdError(f"{who}: {name} must be a f32 tensor on {x.device}")
+        k = int(weight.shape[-1])
+        if weight.dim() < 2 or int(weight.shape[-2]) != k or weight.numel() != k * k or bias.numel() != 1:
+            raise _capi.HealAmdError(f"{who}: weight {tuple(weight.shape)} / bias {tuple(bias.shape)} are not a [k, k] filter and "
+                                     "one bias")
+        if k % 2 == 0 or not 1 <= k <= COMM_MAX_K:
+            raise _capi.HealAmdError(f"{who}: the filter size must be odd and in [1, {COMM_MAX_K}] (got {k})")
+        weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+    n_levels = int(n_levels)
+    if not _capi.lib().heal_comm_mask_supported(n_total, len(lens), A, H, W, k, n_levels):
+        raise _capi.HealAmdError(f"{who}: unsupported problem: {n_total} agents in {len(lens)} scenes (at most {COMM_MAX_AGENTS}), "
+                                 f"map {A} x {H} x {W}, filter {k}, {n_levels} levels (1..{WARP_MAX_LEVELS})")
+    dev = x.device
+    masks = [torch.empty((n_total, 1, H >> l, W >> l), dtype=torch.float32, device=dev) for l in range(n_levels)]
+    count = torch.empty((len(lens),), dtype=torch.int32, device=dev)
+    rate = torch.empty((), dtype=torch.float32, device=dev)
+    ws = _workspace("comm_mask", _capi.query("heal_comm_mask_workspace", len(lens), H, W), dev)
+    _capi.guard_note("heal_comm_mask", [m.data_ptr() for m in masks])
+    with _Timed("comm_mask", nbytes=4.0 * (x.numel() + sum(m.numel() for m in masks)), kernel_events=True):
+        _capi.call("heal_comm_mask", _ptr(x), n_total, A, H, W, _host_array(lens, ctypes.c_int32), len(lens), _ptr(weight),
+                   _ptr(bias), k, float(thre), n_levels, _host_array([m.data_ptr() for m in masks], ctypes.c_void_p), _ptr(count),
+                   _ptr(rate), _ptr(ws), ws.numel(), _stream())
+    return masks, count, rate
 
 
 DISCO_MAX_AGENTS = WARP_MAX_AGENTS

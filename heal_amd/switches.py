@@ -95,6 +95,7 @@ SWITCHES = {
     "HEAL_C3_TH": _LIBRARY,
     "HEAL_CANVAS_CG": _LIBRARY,
     "HEAL_CANVAS_NT": _LIBRARY,
+    "HEAL_COMM_FUSED": _LIBRARY,
     "HEAL_GC3_DBG": _LIBRARY,
     "HEAL_GCONV_1PX": _LIBRARY,
     "HEAL_GS_TH": _LIBRARY,
