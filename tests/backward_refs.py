@@ -522,15 +522,16 @@ def k2_k():
     return dict(s1=18, S=25, out=19, A=13, B=6, Cx=25)
 
 
-def k2_argmax_margin(f, fabs, num_points, prm):
+def k2_argmax_margin(f, fabs, num_points, prm, k=18):
     """Smallest (gap between the best and the second-best candidate of a (pillar, channel), or distance of the best pre-ReLU
     value from 0) minus twice the forward error bound of those candidates: > 0 means fp32 cannot pick another row or another
-    side of the ReLU.  Candidates: the pre-ReLU values of the real rows, and `shift` for the padding rows if np < P."""
+    side of the ReLU.  Candidates: the pre-ReLU values of the real rows, and `shift` for the padding rows if np < P.
+    k: the forward error of a pre-ReLU value in EPS (18 for the four-pillars-per-wave kernels, see k2_k)."""
     w, sc, sh = (np.asarray(prm[k], np.float64) for k in ("weight", "scale", "shift"))
     M, P, _ = f.shape
     npt = np.asarray(num_points).reshape(M)
     v = (f @ w.T) * sc + sh                                          # pre-ReLU [M,P,64]
-    b = 18 * EPS * ((fabs @ np.abs(w).T) * np.abs(sc) + np.abs(sh))
+    b = k * EPS * ((fabs @ np.abs(w).T) * np.abs(sc) + np.abs(sh))
     worst = np.inf
     for m in range(M):
         cand, cb = v[m, :npt[m]], b[m, :npt[m]]
