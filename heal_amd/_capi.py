@@ -21,6 +21,7 @@ HEADER_TRAIN_BN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train
 HEADER_TRAIN_WARP = os.path.join(os.path.dirname(HERE), "include", "heal_amd_train_warp.h")
 HEADER_CENTER = os.path.join(os.path.dirname(HERE), "include", "heal_amd_center.h")
 HEADER_COMM = os.path.join(os.path.dirname(HERE), "include", "heal_amd_comm.h")
+HEADER_UNC = os.path.join(os.path.dirname(HERE), "include", "heal_amd_unc.h")
 
 _lib = None
 
@@ -140,6 +141,15 @@ def signatures_comm():
         return parse_prototypes(f.read())
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_unc():
+    """{name: (restype, argtypes)} of include/heal_amd_unc.h: CoAlign's uncertainty detector -- PointPillarUncertaintyLoss in one
+    pass (heal_unc_loss with its host-side support and workspace rules) and the pooled decode + NMS that returns the kept boxes'
+    uncertainty.  Every build exports them; like signatures_ext() they are outside the versioned inference ABI."""
+    with open(HEADER_UNC) as f:
+        return parse_prototypes(f.read())
+
+
 def declared_symbols(experimental=False):
     """Function names declared in include/heal_amd.h (the shipped C ABI), or with experimental=True in
     include/heal_amd_experimental.h."""
@@ -176,7 +186,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**signatures(), **signatures_train(), **signatures_ext(), **signatures_train_attn(),
                                   **signatures_train_bn(), **signatures_train_warp(), **signatures_center(),
-                                  **signatures_comm()}.items():
+                                  **signatures_comm(), **signatures_unc()}.items():
             if not hasattr(L, name):
                 continue  # declared but not built yet -> surfaces in call() / the symbol test
             f = getattr(L, name)

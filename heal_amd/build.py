@@ -75,6 +75,7 @@ def _deps():
     hdrs.append(os.path.join(inc, "heal_amd_train_warp.h"))  # the differentiable warp_affine_simple: part of every build
     hdrs.append(os.path.join(inc, "heal_amd_center.h"))     # the centre head (criterion, box map, decode): part of every build
     hdrs.append(os.path.join(inc, "heal_amd_comm.h"))       # Where2comm's communication mask and masked fusion: part of every build
+    hdrs.append(os.path.join(inc, "heal_amd_unc.h"))        # the uncertainty detector's criterion and decode: part of every build
     if EXPERIMENTAL:
         hdrs.append(os.path.join(inc, "heal_amd_experimental.h"))
     return hdrs

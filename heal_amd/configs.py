@@ -313,6 +313,35 @@ def lidar_centerpoint(fusion_method="max", lidar_range=FULL_RANGE, max_cav=5, di
     return load_general_params(h)
 
 
+def lidar_uncertainty(lidar_range=FULL_RANGE, dim=3, dir_head=True):
+    """CoAlign's first stage: core_method point_pillar_uncertainty (the single-agent PointPillars detector with a per-box pose
+    uncertainty head of `dim` components: 2 = x, y; 3 = x, y, yaw; 7 = every regression target), point_pillar_uncertainty_loss
+    and the UncertaintyVoxelPostprocessor.  The reference ships no YAML for this model: the KEY NAMES are the ones its code
+    reads (point_pillar_uncertainty.py:14-41, point_pillar_uncertainty_loss.py:16-22, :195-216); the VALUES of the
+    `uncertainty` block are this project's test values, not recovered ones."""
+    h = _common(lidar_range, 1)
+    args = {"voxel_size": [0.4, 0.4, 4], "lidar_range": list(lidar_range), "anchor_num": 2, "uncertainty_dim": dim,
+            "pillar_vfe": {"use_norm": True, "with_distance": False, "use_absolute_xyz": True, "num_filters": [64]},
+            "point_pillar_scatter": {"num_features": 64},
+            "base_bev_backbone": {"layer_nums": [3, 5, 8], "layer_strides": [2, 2, 2], "num_filters": [64, 128, 256],
+                                  "upsample_strides": [1, 2, 4], "num_upsample_filter": [128, 128, 128]}}
+    if dir_head:
+        args["dir_args"] = copy.deepcopy(DIR_ARGS)
+    h["name"] = "heal_amd_point_pillar_uncertainty"
+    h["model"] = {"core_method": "point_pillar_uncertainty", "args": args}
+    h["postprocess"]["core_method"] = "UncertaintyVoxelPostprocessor"
+    if not dir_head:
+        h["postprocess"].pop("dir_args")
+    base = h["loss"]["args"]
+    h["loss"] = {"core_method": "point_pillar_uncertainty_loss", "args": {
+        "pos_cls_weight": base["pos_cls_weight"], "cls": base["cls"], "reg": base["reg"],
+        "uncertainty": {"weight": 0.25, "dim": dim, "xy_loss_type": "l2", "angle_loss_type": "von-mise", "angle_weight": 0.5,
+                        "lambda_V": 0.001, "s0": 1.0, "limit_period": True}}}
+    if dir_head:
+        h["loss"]["args"]["dir"] = base["dir"]
+    return load_general_params(h)
+
+
 def lidar_centerpoint_where2comm(agg="ATTEN", multi_scale=True, backbone="resnet", communication=True, lidar_range=FULL_RANGE,
                                  max_cav=5, thre=0.01, k_size=5, c_sigma=1.0):
     """core_method center_point_where2comm: lidar_centerpoint's trunk, heads and criterion with Where2comm's spatially masked

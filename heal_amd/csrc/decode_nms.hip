@@ -27,6 +27,7 @@
 #include "quad_iou.h"
 #include "../../include/heal_amd.h"
 #include "../../include/heal_amd_center.h"
+#include "../../include/heal_amd_unc.h"
 
 namespace heal {
 
@@ -398,6 +399,17 @@ struct PooledAgents {
     }
 };
 
+// heal_decode_nms_agents_unc: the same slots, and the POOLED index of the candidate where PooledAgents keeps its agent -- the
+// reduce then hands out_index[pos] = slot_index[row] out through its `agent` arguments, and k_unc_gather works from that
+struct PooledAgentsIndexed {
+    PooledAgents pool;      // slot_agent NULL
+    int* slot_index;        // [top] pooled index of the box in slot r
+    __device__ __forceinline__ void slot(int j, int r, const NmsBufs& nb) const {
+        pool.slot(j, r, nb);
+        slot_index[r] = j;
+    }
+};
+
 constexpr int RANK_PER_BLOCK = TOPK_THREADS / 4;
 template <class Src>
 __global__ __launch_bounds__(TOPK_THREADS) void k_rank_prepare(Src src, const unsigned long long* __restrict__ cand_list, int top,
@@ -616,6 +628,28 @@ __global__ __launch_bounds__(NMS_RED_THREADS) void k_nms_reduce(NmsBufs nb, cons
     }
 }
 
+// heal_decode_nms_agents_unc, after the reduce: kept box `pos` came from pooled anchor index[pos] = agent k's anchor j (cell
+// j / A, anchor j % A); out_unc[pos][d] <- channel (j % A) * dim + d of agent k's [dim * A, H, W] map at that cell.  One thread
+// per (pos, d) up to the capacity; the count is read on the device.
+struct UncMaps { const float* p[DEC_MAX_AGENTS]; };
+__global__ __launch_bounds__(256) void k_unc_gather(UncMaps maps, const AgentRow* __restrict__ rows, int n_agents, int A, int dim,
+                                                   const int* __restrict__ index, const int* __restrict__ out_count,
+                                                   float* __restrict__ out_unc, int* __restrict__ out_agent) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int pos = t / dim, d = t - pos * dim;
+    if (pos >= *out_count) return;
+    const int j = index[pos];
+    int k = 0;
+    for (int u = 1; u < n_agents; ++u) k += j >= rows[u].d.off ? 1 : 0;
+    const float* __restrict__ m = maps.p[0];
+#pragma unroll
+    for (int u = 1; u < DEC_MAX_AGENTS; ++u) m = u == k ? maps.p[u] : m;    // by comparison: the by-value table stays in registers
+    const AgentDesc ad = rows[k].d;
+    const int local = j - ad.off, a = local % A, hw = local / A;
+    out_unc[(size_t)pos * dim + d] = m[(size_t)(a * dim + d) * ((size_t)ad.H * ad.W) + hw];
+    if (d == 0 && out_agent != nullptr) out_agent[pos] = k;
+}
+
 __global__ __launch_bounds__(256) void k_quad_iou(const float* __restrict__ a, int n,
                                                  const float* __restrict__ b, int m, float* __restrict__ iou) {
     const int t = blockIdx.x * 256 + threadIdx.x;
@@ -765,13 +799,15 @@ extern "C" size_t heal_decode_nms_agents_workspace(int anchors_total, int nms_to
     return heal_decode_nms_workspace(anchors_total, nms_top) + align_up(DEC_MAX_AGENTS * sizeof(AgentRow));
 }
 
-extern "C" int heal_decode_nms_agents(int n_agents, const float* const* cls_host, const float* const* reg_host,
-                                      const float* const* dir_host, const float* const* anchors_host, const int32_t* h_host,
-                                      const int32_t* w_host, int anchor_num, int num_bins, float score_thr, float dir_offset,
-                                      float nms_thr, int nms_top, const float* tfm_host, const float* tfm_dev,
-                                      const float* gt_range_host, float* out_corners, float* out_scores, int32_t* out_agent,
-                                      int32_t* out_count, int max_out, void* ws, size_t ws_bytes, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
+namespace heal {
+// heal_decode_nms_agents (unc_host NULL) and heal_decode_nms_agents_unc: one front end, one tail.  With uncertainty maps the top-k
+// slots carry the pooled index instead of the agent, and k_unc_gather follows the reduce.
+static int decode_agents(int n_agents, const float* const* cls_host, const float* const* reg_host, const float* const* dir_host,
+                         const float* const* anchors_host, const float* const* unc_host, const int32_t* h_host,
+                         const int32_t* w_host, int anchor_num, int num_bins, int unc_dim, float score_thr, float dir_offset,
+                         float nms_thr, int nms_top, const float* tfm_host, const float* tfm_dev, const float* gt_range_host,
+                         float* out_corners, float* out_scores, float* out_unc, int32_t* out_agent, int32_t* out_index,
+                         int32_t* out_count, int max_out, void* ws, size_t ws_bytes, hipStream_t s) {
     HEAL_REQUIRE(n_agents >= 1 && n_agents <= DEC_MAX_AGENTS, "decode_nms_agents: n_agents must be in [1,%d] (got %d)",
                  DEC_MAX_AGENTS, n_agents);
     HEAL_REQUIRE(cls_host && reg_host && anchors_host && h_host && w_host && gt_range_host && out_corners && out_scores &&
@@ -807,6 +843,7 @@ extern "C" int heal_decode_nms_agents(int n_agents, const float* const* cls_host
     DecWs w;
     const bool fits = carve(a, (int)total, nms_top, w);
     AgentRow* rows = a.take<AgentRow>(DEC_MAX_AGENTS);
+    int* index = (unc_host != nullptr && out_index == nullptr) ? a.take<int>(nms_top) : out_index;
     HEAL_REQUIRE(fits && a.ok(), "decode_nms_agents: workspace too small (%zu < %zu)", ws_bytes, a.off);
 
     DecodeParams p;
@@ -814,9 +851,56 @@ extern "C" int heal_decode_nms_agents(int n_agents, const float* const* cls_host
 
     HEAL_FILL(w.nb.n_cand, 0, sizeof(int), s);
     k_decode_key_agents<<<blocks, 256, 0, s>>>(t, p, rows, w.cand, w.nb.n_cand);
-    const PooledAgents src{rows, n_agents, out_agent ? (int*)w.sel : nullptr, p};
-    k_rank_prepare<PooledAgents><<<TOPK_CAP / RANK_PER_BLOCK, TOPK_THREADS, 0, s>>>(src, w.cand, nms_top, w.nb);
-    return launch_nms_tail(w, nms_top, nms_thr, out_corners, out_scores, out_count, max_out, out_agent, true, s);
+    if (unc_host == nullptr) {
+        const PooledAgents src{rows, n_agents, out_agent ? (int*)w.sel : nullptr, p};
+        k_rank_prepare<PooledAgents><<<TOPK_CAP / RANK_PER_BLOCK, TOPK_THREADS, 0, s>>>(src, w.cand, nms_top, w.nb);
+        return launch_nms_tail(w, nms_top, nms_thr, out_corners, out_scores, out_count, max_out, out_agent, true, s);
+    }
+    UncMaps maps;
+    for (int k = 0; k < DEC_MAX_AGENTS; ++k) maps.p[k] = k < n_agents ? unc_host[k] : nullptr;
+    const PooledAgentsIndexed src{PooledAgents{rows, n_agents, nullptr, p}, (int*)w.sel};
+    k_rank_prepare<PooledAgentsIndexed><<<TOPK_CAP / RANK_PER_BLOCK, TOPK_THREADS, 0, s>>>(src, w.cand, nms_top, w.nb);
+    if (launch_nms_tail(w, nms_top, nms_thr, out_corners, out_scores, out_count, max_out, index, true, s)) return 1;
+    const int rows_out = max_out < nms_top ? max_out : nms_top;       // the reduce keeps at most min(nms_top, max_out) boxes
+    k_unc_gather<<<ceil_div(rows_out * unc_dim, 256), 256, 0, s>>>(maps, rows, n_agents, anchor_num, unc_dim, index, out_count,
+                                                                   out_unc, out_agent);
+    HEAL_LAUNCH_CHECK();
+    return 0;
+}
+}  // namespace heal
+
+extern "C" int heal_decode_nms_agents(int n_agents, const float* const* cls_host, const float* const* reg_host,
+                                      const float* const* dir_host, const float* const* anchors_host, const int32_t* h_host,
+                                      const int32_t* w_host, int anchor_num, int num_bins, float score_thr, float dir_offset,
+                                      float nms_thr, int nms_top, const float* tfm_host, const float* tfm_dev,
+                                      const float* gt_range_host, float* out_corners, float* out_scores, int32_t* out_agent,
+                                      int32_t* out_count, int max_out, void* ws, size_t ws_bytes, void* stream) {
+    return decode_agents(n_agents, cls_host, reg_host, dir_host, anchors_host, nullptr, h_host, w_host, anchor_num, num_bins, 0,
+                         score_thr, dir_offset, nms_thr, nms_top, tfm_host, tfm_dev, gt_range_host, out_corners, out_scores,
+                         nullptr, out_agent, nullptr, out_count, max_out, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t heal_decode_nms_agents_unc_workspace(int anchors_total, int nms_top) {
+    return heal_decode_nms_agents_workspace(anchors_total, nms_top) + align_up((size_t)(nms_top < 1 ? 1 : nms_top) * sizeof(int));
+}
+
+extern "C" int heal_decode_nms_agents_unc(int n_agents, const float* const* cls_host, const float* const* reg_host,
+                                          const float* const* dir_host, const float* const* anchors_host,
+                                          const float* const* unc_host, const int32_t* h_host, const int32_t* w_host,
+                                          int anchor_num, int num_bins, int unc_dim, float score_thr, float dir_offset,
+                                          float nms_thr, int nms_top, const float* tfm_host, const float* tfm_dev,
+                                          const float* gt_range_host, float* out_corners, float* out_scores, float* out_unc,
+                                          int32_t* out_agent, int32_t* out_index, int32_t* out_count, int max_out, void* ws,
+                                          size_t ws_bytes, void* stream) {
+    HEAL_REQUIRE(unc_host != nullptr && out_unc != nullptr, "decode_nms_agents_unc: unc_host and out_unc must be set");
+    HEAL_REQUIRE(unc_dim >= 1 && unc_dim <= 16, "decode_nms_agents_unc: unc_dim must be in [1,16] (got %d)", unc_dim);
+    HEAL_REQUIRE(n_agents >= 1 && n_agents <= HEAL_DECODE_MAX_AGENTS, "decode_nms_agents_unc: n_agents must be in [1,%d] (got %d)",
+                 HEAL_DECODE_MAX_AGENTS, n_agents);
+    for (int k = 0; k < n_agents; ++k)
+        HEAL_REQUIRE(unc_host[k] != nullptr, "decode_nms_agents_unc: null uncertainty map for agent %d", k);
+    return decode_agents(n_agents, cls_host, reg_host, dir_host, anchors_host, unc_host, h_host, w_host, anchor_num, num_bins,
+                         unc_dim, score_thr, dir_offset, nms_thr, nms_top, tfm_host, tfm_dev, gt_range_host, out_corners,
+                         out_scores, out_unc, out_agent, out_index, out_count, max_out, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int heal_quad_iou(const float* a, int n, const float* b, int m, float* iou, void* stream) {

@@ -1056,13 +1056,32 @@ def decode_nms_agents(cls_list, reg_list, dir_list, anchors_list, tfms, score_th
     that mixes the two is refused.
     -> sync=True: (corners [K,8,3], scores [K]) or (None, None); sync=False: the full-capacity buffers and the device count,
     no host synchronisation.  want_agent appends the source agent of every kept box (int32)."""
-    who = "decode_nms_agents"
+    return _decode_nms_agents("decode_nms_agents", cls_list, reg_list, dir_list, anchors_list, None, tfms, score_thr, dir_offset,
+                              num_bins, nms_thr, gt_range, nms_top, sync, want_agent, False)
+
+
+def decode_nms_agents_unc(cls_list, reg_list, dir_list, anchors_list, unc_list, tfms, score_thr, dir_offset, num_bins, nms_thr,
+                          gt_range, nms_top=1000, sync=True, want_agent=False, want_index=False):
+    """decode_nms_agents for the uncertainty detector (heal_decode_nms_agents_unc; uncertainty_voxel_postprocessor.py:116-249):
+    the same arguments plus unc_list, agent k's [1,dim*A,H_k,W_k] or [dim*A,H_k,W_k] uncertainty map.  Corners, scores and count
+    are decode_nms_agents' bit for bit; every kept box also gets the `dim` uncertainty channels of the anchor it was decoded from.
+    -> sync=True: (corners [K,8,3], scores [K], uncertainty [K,dim][, agent [K]][, index [K]]) or Nones; sync=False: the
+    full-capacity buffers (corners, scores, count, uncertainty[, agent][, index]), no host synchronisation.  want_index appends
+    the pooled anchor index of every kept box (int32: agent k's anchors start at sum_{u<k} H_u W_u A)."""
+    return _decode_nms_agents("decode_nms_agents_unc", cls_list, reg_list, dir_list, anchors_list, unc_list, tfms, score_thr,
+                              dir_offset, num_bins, nms_thr, gt_range, nms_top, sync, want_agent, want_index)
+
+
+def _decode_nms_agents(who, cls_list, reg_list, dir_list, anchors_list, unc_list, tfms, score_thr, dir_offset, num_bins, nms_thr,
+                       gt_range, nms_top, sync, want_agent, want_index):
     n = len(cls_list)
     if not 1 <= n <= DECODE_MAX_AGENTS:
         raise _capi.HealAmdError(f"{who}: 1..{DECODE_MAX_AGENTS} agents per scene (got {n})")
     if len(reg_list) != n or len(anchors_list) != n or (dir_list is not None and len(dir_list) != n):
         raise _capi.HealAmdError(f"{who}: {n} score maps, {len(reg_list)} regression maps, "
                                  f"{'no' if dir_list is None else len(dir_list)} direction maps, {len(anchors_list)} anchor tables")
+    if unc_list is not None and len(unc_list) != n:
+        raise _capi.HealAmdError(f"{who}: {n} score maps, {len(unc_list)} uncertainty maps")
     if tfms is None:
         raise _capi.HealAmdError(f"{who}: tfms is required (an [n,4,4] CUDA tensor or {n} host matrices)")
 
@@ -1082,6 +1101,13 @@ def decode_nms_agents(cls_list, reg_list, dir_list, anchors_list, tfms, score_th
         dir_list = [maps(t, "dir_preds", k) for k, t in enumerate(dir_list)]
     anchors_list = [_need(a, torch.float32, f"anchors[{k}]") for k, a in enumerate(anchors_list)]
     A = int(cls_list[0].shape[0])
+    unc_dim = 0
+    if unc_list is not None:
+        unc_list = [maps(t, "unc_preds", k) for k, t in enumerate(unc_list)]
+        unc_dim = int(unc_list[0].shape[0]) // A
+        if unc_dim < 1 or any(tuple(u.shape) != (unc_dim * A,) + tuple(c.shape[1:]) for u, c in zip(unc_list, cls_list)):
+            raise _capi.HealAmdError(f"{who}: uncertainty maps {[tuple(u.shape) for u in unc_list]} are not [dim * {A}, H_k, W_k] "
+                                     "with one dim for every agent")
     hs, ws_, total = [], [], 0
     for k in range(n):
         Ak, H, W = (int(v) for v in cls_list[k].shape)
@@ -1125,30 +1151,40 @@ def decode_nms_agents(cls_list, reg_list, dir_list, anchors_list, tfms, score_th
     out_s = torch.empty((nms_top,), dtype=torch.float32, device=dev)
     out_a = torch.empty((nms_top,), dtype=torch.int32, device=dev) if want_agent else None
     out_n = torch.zeros((1,), dtype=torch.int32, device=dev)
-    nbytes = _capi.query("heal_decode_nms_agents_workspace", total, int(nms_top))
-    ws = _workspace("decode_nms_agents", nbytes, dev)
+    out_u = torch.empty((nms_top, unc_dim), dtype=torch.float32, device=dev) if unc_list is not None else None
+    out_i = torch.empty((nms_top,), dtype=torch.int32, device=dev) if unc_list is not None and want_index else None
+    entry = "heal_" + who
+    nbytes = _capi.query(entry + "_workspace", total, int(nms_top))
+    ws = _workspace(who, nbytes, dev)
     g = _host_array([float(v) for v in gt_range], ctypes.c_float)
 
     def ptrs(ts):
         return _host_array([x.data_ptr() for x in ts], ctypes.c_void_p)
 
-    _capi.guard_note("heal_decode_nms_agents", [x.data_ptr() for ts in (cls_list, reg_list, dir_list or [], anchors_list) for x in ts])
-    with _Timed("decode_nms_agents"):
-        _capi.call("heal_decode_nms_agents", n, ptrs(cls_list), ptrs(reg_list), ptrs(dir_list) if dir_list is not None else null,
-                   ptrs(anchors_list), _host_array(hs, ctypes.c_int32), _host_array(ws_, ctypes.c_int32), A, int(num_bins),
-                   float(score_thr), float(dir_offset), float(nms_thr), int(nms_top), t_host, t_dev, g,
-                   _ptr(out_c), _ptr(out_s), _ptr(out_a), _ptr(out_n), int(nms_top), _ptr(ws), ws.numel(), _stream())
-    _remember("decode_nms_agents", lambda: decode_nms_agents(cls_list, reg_list, dir_list, anchors_list, tfms, score_thr, dir_offset,
-                                                             num_bins, nms_thr, gt_range, nms_top, sync=False,
-                                                             want_agent=want_agent))
+    _capi.guard_note(entry, [x.data_ptr() for ts in (cls_list, reg_list, dir_list or [], anchors_list, unc_list or []) for x in ts])
+    dir_ptrs = ptrs(dir_list) if dir_list is not None else null
+    hs_c, ws_c = _host_array(hs, ctypes.c_int32), _host_array(ws_, ctypes.c_int32)
+    with _Timed(who):
+        if unc_list is None:
+            _capi.call(entry, n, ptrs(cls_list), ptrs(reg_list), dir_ptrs, ptrs(anchors_list), hs_c, ws_c, A, int(num_bins),
+                       float(score_thr), float(dir_offset), float(nms_thr), int(nms_top), t_host, t_dev, g,
+                       _ptr(out_c), _ptr(out_s), _ptr(out_a), _ptr(out_n), int(nms_top), _ptr(ws), ws.numel(), _stream())
+        else:
+            _capi.call(entry, n, ptrs(cls_list), ptrs(reg_list), dir_ptrs, ptrs(anchors_list), ptrs(unc_list), hs_c, ws_c, A,
+                       int(num_bins), unc_dim, float(score_thr), float(dir_offset), float(nms_thr), int(nms_top), t_host, t_dev, g,
+                       _ptr(out_c), _ptr(out_s), _ptr(out_u), _ptr(out_a), _ptr(out_i), _ptr(out_n), int(nms_top), _ptr(ws),
+                       ws.numel(), _stream())
+    _remember(who, lambda: _decode_nms_agents(who, cls_list, reg_list, dir_list, anchors_list, unc_list, tfms, score_thr, dir_offset,
+                                              num_bins, nms_thr, gt_range, nms_top, False, want_agent, want_index))
+    extra = [t for t in (out_u, out_a, out_i) if t is not None]
     if not sync:
-        return (out_c, out_s, out_n, out_a) if want_agent else (out_c, out_s, out_n)
+        return (out_c, out_s, out_n, *extra)
     k = int(out_n.item())
     if _SPARSE_CHECKS and not torch.cuda.is_current_stream_capturing():
         verify_sparse_capacity()   # as decode_nms: the first host sync after a no-sync SECOND encoder
     if k == 0:
-        return (None, None, None) if want_agent else (None, None)
-    return (out_c[:k], out_s[:k], out_a[:k]) if want_agent else (out_c[:k], out_s[:k])
+        return (None,) * (2 + len(extra))
+    return (out_c[:k], out_s[:k], *(t[:k] for t in extra))
 
 
 def quad_iou(a, b):
@@ -2486,6 +2522,105 @@ def det_loss_terms(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one
     """The differentiable form of det_loss: -> terms [3] (cls, reg, dir), gradients for the maps that require one."""
     need = tuple(_wants_grad(t) for t in (cls_preds, reg_preds, dir_preds))
     return DetLoss.apply(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targets, cfg, need)
+
+
+_UNC_XY = {"l2": 0, "l1": 1}              # HEAL_UNC_L2 / HEAL_UNC_L1 of include/heal_amd_unc.h
+_UNC_ANGLE = {"l2": 0, "von-mise": 1}     # HEAL_UNC_L2 / HEAL_UNC_VON_MISES
+
+
+def unc_loss_supported(cls_preds, reg_preds, unc_preds, dir_preds, pos_equal_one, neg_equal_one, targets, dim, xy_loss_type="l2",
+                       angle_loss_type="l2", gamma=2.0, num_bins=2, iou=None, batch_size=None):
+    """The fused terms of PointPillarUncertaintyLoss: what det_loss_supported asks of the maps, labels, gamma, num_bins, iou and
+    batch_size, a CUDA fp32 unc_preds [N, dim*A, H, W] on the same device, dim in {2, 3, 7}, xy_loss_type l2 | l1 and
+    angle_loss_type l2 | von-mise (heal_unc_loss_supported).  HEAL_LOSS_FUSED=0 forces the composition."""
+    if not det_loss_supported(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targets, gamma=gamma,
+                              num_bins=num_bins, iou=iou, batch_size=batch_size):
+        return False
+    N, A, H, W = (int(v) for v in cls_preds.shape)
+    if xy_loss_type not in _UNC_XY or angle_loss_type not in _UNC_ANGLE or not isinstance(dim, int):
+        return False
+    return bool(_loss_map_ok(unc_preds) and unc_preds.device == cls_preds.device and tuple(unc_preds.shape) == (N, dim * A, H, W)
+                and _capi.lib().heal_unc_loss_supported(A, dim, _UNC_XY[xy_loss_type], _UNC_ANGLE[angle_loss_type],
+                                                        int(dir_preds is not None))
+                and _capi.query("heal_unc_loss_workspace", N, A, H, W) > 0)
+
+
+def unc_loss(cls_preds, reg_preds, unc_preds, dir_preds, pos_equal_one, neg_equal_one, targets, pos_cls_weight, alpha, sigma,
+             weights, dim, xy_loss_type="l2", angle_loss_type="l2", angle_weight=1.0, lambda_V=1.0, s0=1.0, limit_period=False,
+             anchor_yaw=None, dir_offset=0.0, need_grad=True, grad_out=None):
+    """UL.  PointPillarUncertaintyLoss's four terms and their gradients in one pass (heal_unc_loss): det_loss's maps and labels
+    plus unc_preds [N, dim*A, H, W]; weights = (cls, reg, unc, dir) loss weights; dim, the loss types and angle_weight, lambda_V,
+    s0, limit_period are the `uncertainty` block's.  -> (terms [4] = cls, reg, unc, dir loss, each x weight / N,
+    (grad_cls, grad_reg, grad_unc, grad_dir) | None); grad_reg carries the reg term's and the unc term's gradient.
+    need_grad: bool or one per map; False passes NULL gradients: the kernels only read.  grad_out: buffers to write into."""
+    who = "unc_loss"
+    (cls_preds, reg_preds, unc_preds, dir_preds), (pos, neg, tgt) = _loss_inputs(
+        who, (("cls_preds", cls_preds), ("reg_preds", reg_preds), ("unc_preds", unc_preds), ("dir_preds", dir_preds)),
+        (("pos_equal_one", pos_equal_one), ("neg_equal_one", neg_equal_one), ("targets", targets)))
+    N, A, H, W = (int(v) for v in cls_preds.shape)
+    if xy_loss_type not in _UNC_XY or angle_loss_type not in _UNC_ANGLE:
+        raise _capi.HealAmdError(f"{who}: xy_loss_type {xy_loss_type!r} (l2 | l1), angle_loss_type {angle_loss_type!r} (l2 | von-mise)")
+    dim = int(dim)
+    if (A > LOSS_MAX_ANCHORS or tuple(reg_preds.shape) != (N, 7 * A, H, W) or tuple(unc_preds.shape) != (N, dim * A, H, W)
+            or (dir_preds is not None and tuple(dir_preds.shape) != (N, 2 * A, H, W))):
+        raise _capi.HealAmdError(f"{who}: maps {tuple(cls_preds.shape)}, {tuple(reg_preds.shape)}, {tuple(unc_preds.shape)}"
+                                 f"{'' if dir_preds is None else ', ' + str(tuple(dir_preds.shape))} are not [N, A, H, W], "
+                                 f"[N, 7A, H, W], [N, {dim}A, H, W] (, [N, 2A, H, W]) with at most {LOSS_MAX_ANCHORS} anchors")
+    if pos.numel() != N * H * W * A or neg.numel() != N * H * W * A or tgt.numel() != 7 * N * H * W * A:
+        raise _capi.HealAmdError(f"{who}: labels of {pos.numel()}, {neg.numel()}, {tgt.numel()} elements for N*H*W*A = {N * H * W * A}")
+    yaw = None
+    if dir_preds is not None:
+        if anchor_yaw is None or len(anchor_yaw) != A:
+            raise _capi.HealAmdError(f"{who}: dir_preds needs anchor_yaw with {A} angles (radians)")
+        yaw = (ctypes.c_double * A)(*[float(v) for v in anchor_yaw])
+    if len(weights) != 4 or not float(sigma) > 0:
+        raise _capi.HealAmdError(f"{who}: weights must be (cls, reg, unc, dir) and sigma positive")
+    maps = (cls_preds, reg_preds, unc_preds, dir_preds)
+    grads = _loss_grad_buffers(who, maps, need_grad, grad_out)
+    nbytes = _capi.query("heal_unc_loss_workspace", N, A, H, W)
+    if nbytes == 0:
+        raise _capi.HealAmdError(f"{who}: shape {(N, A, H, W)} is out of range")
+    ws = _workspace("unc_loss", nbytes, cls_preds.device)
+    terms = torch.empty(4, dtype=torch.float32, device=cls_preds.device)
+    moved = sum(4.0 * m.numel() for m in maps if m is not None) + sum(4.0 * g.numel() for g in grads if g is not None) \
+        + float(pos.element_size()) * (2 * pos.numel() + tgt.numel())
+    with _Timed(f"unc_loss_a{A}_d{dim}", nbytes=moved):
+        _capi.call("heal_unc_loss", _ptr(cls_preds), _ptr(reg_preds), _ptr(unc_preds), _ptr(dir_preds), _ptr(pos), _ptr(neg),
+                   _ptr(tgt), int(pos.dtype == torch.float64), N, A, H, W, dim, float(pos_cls_weight), float(alpha), float(sigma),
+                   float(weights[0]), float(weights[1]), float(weights[2]), float(weights[3]), _UNC_XY[xy_loss_type],
+                   _UNC_ANGLE[angle_loss_type], float(angle_weight), float(lambda_V), float(s0), int(bool(limit_period)),
+                   ctypes.cast(yaw, ctypes.c_void_p) if yaw is not None else ctypes.c_void_p(0), float(dir_offset), _ptr(terms),
+                   _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(ws), ctypes.c_size_t(nbytes), _stream())
+    return terms, (tuple(grads) if any(g is not None for g in grads) else None)
+
+
+class UncLoss(torch.autograd.Function):
+    """unc_loss under autograd.  grad_reg is the sum of two terms' gradients (reg and unc), so the differentiable output is the
+    TOTAL, added in the loss module's order (dir + ((reg + cls) + unc)); the four terms come along for the bookkeeping and carry
+    no gradient.  The forward writes d total / d map (saved); backward scales each by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, cls_preds, reg_preds, unc_preds, dir_preds, pos, neg, targets, cfg, need):
+        terms, grads = unc_loss(cls_preds, reg_preds, unc_preds, dir_preds, pos, neg, targets, need_grad=need, **cfg)
+        grads = grads if grads is not None else (None, None, None, None)
+        ctx.have = tuple(g is not None for g in grads)
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        ctx.mark_non_differentiable(terms)
+        total = (terms[1] + terms[0]) + terms[2]
+        return (terms[3] + total if dir_preds is not None else total), terms
+
+    @staticmethod
+    def backward(ctx, grad_total, _):
+        saved = list(ctx.saved_tensors)
+        out = [grad_total * saved.pop(0) if have else None for have in ctx.have]
+        return (*out, None, None, None, None, None)
+
+
+def unc_loss_terms(cls_preds, reg_preds, unc_preds, dir_preds, pos_equal_one, neg_equal_one, targets, **cfg):
+    """The differentiable form of unc_loss: -> (total, terms [4] = cls, reg, unc, dir); the total carries the gradients for the
+    maps that require one, the terms are detached."""
+    need = tuple(_wants_grad(t) for t in (cls_preds, reg_preds, unc_preds, dir_preds))
+    return UncLoss.apply(cls_preds, reg_preds, unc_preds, dir_preds, pos_equal_one, neg_equal_one, targets, cfg, need)
 
 
 def occ_loss_supported(occ_list, pos_equal_one, neg_equal_one, relative_downsample, gamma=2.0):
