@@ -22,6 +22,7 @@ HEADER_TRAIN_WARP = os.path.join(os.path.dirname(HERE), "include", "heal_amd_tra
 HEADER_CENTER = os.path.join(os.path.dirname(HERE), "include", "heal_amd_center.h")
 HEADER_COMM = os.path.join(os.path.dirname(HERE), "include", "heal_amd_comm.h")
 HEADER_UNC = os.path.join(os.path.dirname(HERE), "include", "heal_amd_unc.h")
+HEADER_ROI = os.path.join(os.path.dirname(HERE), "include", "heal_amd_roi.h")
 
 _lib = None
 
@@ -150,6 +151,15 @@ def signatures_unc():
         return parse_prototypes(f.read())
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_roi():
+    """{name: (restype, argtypes)} of include/heal_amd_roi.h: the per-image region-of-interest launches of the pointwise and the
+    small-group 3x3 convolution, and the reader of HEAL_PYRAMID_ROI.  Every build exports them; like signatures_ext() they are
+    outside the versioned inference ABI."""
+    with open(HEADER_ROI) as f:
+        return parse_prototypes(f.read())
+
+
 def declared_symbols(experimental=False):
     """Function names declared in include/heal_amd.h (the shipped C ABI), or with experimental=True in
     include/heal_amd_experimental.h."""
@@ -186,7 +196,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**signatures(), **signatures_train(), **signatures_ext(), **signatures_train_attn(),
                                   **signatures_train_bn(), **signatures_train_warp(), **signatures_center(),
-                                  **signatures_comm(), **signatures_unc()}.items():
+                                  **signatures_comm(), **signatures_unc(), **signatures_roi()}.items():
             if not hasattr(L, name):
                 continue  # declared but not built yet -> surfaces in call() / the symbol test
             f = getattr(L, name)

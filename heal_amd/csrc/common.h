@@ -89,6 +89,50 @@ LaunchEvents take_launch_events();
             hipLaunchKernelGGL(kernel, grid, block, (std::uint32_t)(lds), stream, __VA_ARGS__);                      \
     } while (0)
 
+// Per-image OUTPUT region of interest of a launch (heal_conv1x1_roi, heal_grouped_small_conv3x3_roi; include/heal_amd_roi.h): box
+// (y0, y1, x0, x1) in output pixels for each image, passed BY VALUE as a kernel argument -- no device memory, so a captured graph
+// holds the boxes as constants.  A block whose output tile holds no pixel of its image's box returns before its first load and writes
+// nothing; the test runs on block-uniform values in the prologue, before any barrier, so every wave of a block takes the same path.
+// The kernels take the table as a template choice (`bool ROI`, default false): the plain instantiation -- what the old entry points
+// launch -- receives the empty NoRoi instead and compiles to the code it always was (no test, no larger argument block).
+constexpr int ROI_MAX_IMAGES = 8;   // == HEAL_WARP_MAX_AGENTS (checked where the header is included)
+struct RoiTable {
+    int n;
+    unsigned perm;   // see roi_spread
+    int box[ROI_MAX_IMAGES][4];
+};
+inline RoiTable no_roi() { RoiTable r; r.n = 0; r.perm = 1; return r; }
+struct NoRoi {};
+template <bool ROI> struct RoiArg { using type = NoRoi; };
+template <> struct RoiArg<true> { using type = RoiTable; };
+// Workgroups go to the 8 XCDs round-robin and xcd_block() hands every XCD one CONTIGUOUS range of the logical block order, image index
+// slowest: the tiles a ROI skips (whole images' borders) would all fall to a few XCDs, which then idle while the others set the kernel's
+// time.  A ROI launch therefore walks its G (tile, image) pairs in the order L -> L * perm mod G, perm coprime to G and near G / phi:
+// every contiguous range of L holds an even sample of all images and all tile positions.  Blocks that share a pair (the Cout chunks
+// of a pixel tile, the super-groups of a 3x3 tile) stay together.  perm == 1: identity.
+inline unsigned roi_spread(unsigned G) {
+    if (G < 16 || G >= 65536) return 1;            // (L * perm stays below 2^32)
+    auto gcd = [](unsigned a, unsigned b) { while (b) { const unsigned t = a % b; a = b; b = t; } return a; };
+    unsigned p = (unsigned)(G * 0.6180339887) | 1u;
+    while (p < G && gcd(p, G) != 1) p += 2;
+    return p < G ? p : 1;
+}
+// host side of the two entry points: checks the boxes (inside the Ho x Wo output map; y1 <= y0 or x1 <= x0 is an EMPTY box, the whole image is
+// skipped) and fills the table.  Returns nullptr, or the message of the failed check.
+inline const char* roi_from_host(const int32_t* roi_host, int n, int Ho, int Wo, RoiTable* out) {
+    if (!roi_host) return "null ROI table";
+    if (n > ROI_MAX_IMAGES) return "more images than ROI table rows (HEAL_WARP_MAX_AGENTS)";
+    out->n = n;
+    for (int i = 0; i < ROI_MAX_IMAGES; ++i)
+        for (int k = 0; k < 4; ++k) out->box[i][k] = i < n ? roi_host[4 * i + k] : 0;
+    for (int i = 0; i < n; ++i) {
+        const int* b = out->box[i];
+        if (b[0] < 0 || b[1] > Ho || b[2] < 0 || b[3] > Wo || b[1] < 0 || b[0] > Ho || b[3] < 0 || b[2] > Wo)
+            return "ROI box outside the output map";
+    }
+    return nullptr;
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
 __device__ __forceinline__ unsigned long long lanemask_lt() {

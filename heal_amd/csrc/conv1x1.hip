@@ -16,21 +16,33 @@
 //   * XCD-contiguous block order with the Cout-chunk index fastest: the (<=4) blocks that re-read one pixel tile
 //     for different output-channel chunks share an L2.
 // Roofline: HBM-bound for Cin,Cout <= 128 (ridge 20 FLOP/B in fp32), MFMA-bound above; §6 of DESIGN.md.
+//
+// ROI (heal_conv1x1_roi; `roi`, a RoiTable kernel argument passed by value): one box (y0, y1, x0, x1) of OUTPUT pixels per image.  A
+// block's tile is BN consecutive pixels of the flattened output image; a block whose tile holds no pixel of its image's box
+// returns in the prologue -- before the first load, the LDS staging and every barrier -- and writes nothing.  The test is exact for
+// a tile that lies in one output row (Wo % BN == 0: a row segment, rows AND columns are tested; Wo == BN: a whole row) and
+// conservative for a tile that spans rows (kept when any spanned row meets the box's rows; columns are not looked at).  Kept
+// blocks run the instructions of the plain launch on the same values: bit-identical results.  It is the ROI = true instantiation of the
+// kernel template (the 64 x 64 x 32 tile, both strides); heal_conv1x1 and the other entry points launch the default, ROI = false, which
+// takes no table and has no test.  Not combined with split-K, pixel-major or depth-to-space output.  A ROI launch also walks its (pixel tile,
+// image) pairs in a spread order (roi_spread, common.h): the skipped tiles are then shared evenly among the XCDs.
 #include <stdlib.h>
 #include "common.h"
 #include "../../include/heal_amd.h"
+#include "../../include/heal_amd_roi.h"
+static_assert(heal::ROI_MAX_IMAGES == HEAL_WARP_MAX_AGENTS, "RoiTable rows");
 
 namespace heal {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-template <int BM, int BN, int KC, int STRIDE>
+template <int BM, int BN, int KC, int STRIDE, bool ROI = false>
 __global__ __launch_bounds__(256) void k_conv1x1(const float* __restrict__ x, const float* __restrict__ wfrag,
                                                 const float* __restrict__ bias, const float* __restrict__ res,
                                                 const float* __restrict__ in_scale, int Cin, int Kpad, int Cout,
                                                 int HW, int Wo, int in_W, int in_HW, int act, int out_pm,
                                                 int d2s_k, int d2s_ctot, int d2s_coff, int n_img, int ksplit,
-                                                float* __restrict__ y) {
+                                                float* __restrict__ y, const typename RoiArg<ROI>::type roi) {
     // ksplit > 1 (small maps with a deep reduction: 36 blocks for the 1152 -> 192 projection at 12 x 16 x 4 pixels): grid.z =
     // ksplit * n_img, block z reduces chunk range ks of image n and writes its PARTIAL sum to y[ks][n][Cout][HW] (no bias /
     // residual / activation: k_conv1x1_splitk_reduce adds the partials in split order and applies them).
@@ -47,8 +59,21 @@ __global__ __launch_bounds__(256) void k_conv1x1(const float* __restrict__ x, co
     constexpr int NPASS = KC / RPP;  // float4 loads per thread per chunk
     static_assert(NPASS >= 1 && KC % RPP == 0, "bad staging shape");
     __shared__ __attribute__((aligned(16))) float sB[2][KC][LD];
-    const Block3 bk = xcd_block();  // x: Cout chunk, y: pixel tile, z: image
+    Block3 bk = xcd_block();  // x: Cout chunk, y: pixel tile, z: image
+    if constexpr (ROI) {      // ROI launch: (tile, image) pairs in spread order (roi_spread), so that every XCD skips its share
+        const unsigned L = (bk.y + gridDim.y * bk.z) * roi.perm % (gridDim.y * gridDim.z);
+        bk.y = L % gridDim.y;
+        bk.z = L / gridDim.y;
+    }
     const int m0 = bk.x * BM, p0 = bk.y * BN, n = bk.z % n_img, kpart = bk.z / n_img;
+    if constexpr (ROI) {   // block-uniform, before any load or barrier: leave if no pixel of the tile [p0, p0 + BN) lies in image n's box
+        const int y0 = roi.box[n][0], y1 = roi.box[n][1], x0 = roi.box[n][2], x1 = roi.box[n][3];
+        const int pl = min(p0 + BN, HW) - 1;                 // last pixel of the tile
+        const int r0 = p0 / Wo, r1 = pl / Wo;                // first and last output row the tile touches
+        bool keep = y0 < y1 && x0 < x1 && r0 < y1 && r1 >= y0;
+        if (keep && r0 == r1) keep = p0 - r0 * Wo < x1 && pl - r0 * Wo >= x0;   // one row: its column range against the box's
+        if (!keep) return;
+    }
     const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
     const int lk = l >> 4, ln = l & 15;
     const float* __restrict__ xin = x + (size_t)n * Cin * in_HW;
@@ -285,7 +310,7 @@ int splitk_reduce_launch(const float* partials, const float* bias, const float* 
 static int conv1x1_launch(const float* x, const float* weight_frag, const float* bias, const float* residual,
                           const float* in_scale, int n, int cin, int cout, int H, int W, int stride, int act,
                           int out_pixel_major, int d2s_k, int d2s_ctot, int d2s_coff, float* y, void* stream,
-                          int ksplit = 1, float* partials = nullptr) {
+                          int ksplit = 1, float* partials = nullptr, const int32_t* roi_host = nullptr) {
     HEAL_REQUIRE(n >= 1 && H >= 1 && W >= 1 && cin >= 1 && cout >= 1, "conv1x1: bad shape");
     HEAL_REQUIRE(stride == 1 || stride == 2, "conv1x1: stride must be 1 or 2 (got %d)", stride);
     const int kpad = (cin + 31) / 32 * 32, mpad = (cout + 63) / 64 * 64;  // dims of the zero-padded fragment layout
@@ -298,6 +323,12 @@ static int conv1x1_launch(const float* x, const float* weight_frag, const float*
         HEAL_REQUIRE(residual == nullptr && act != 3, "conv1x1: pixel-major output takes no residual / GELU");
         HEAL_REQUIRE(cout % 4 == 0 && ((uintptr_t)bias & 15) == 0, "conv1x1: pixel-major output needs Cout %% 4 == 0 and a 16-B aligned bias");
     }
+    RoiTable roi = no_roi();
+    if (roi_host) {
+        HEAL_REQUIRE(ksplit == 1 && out_pixel_major == 0, "conv1x1_roi: no split-K, pixel-major or depth-to-space output with a ROI");
+        const char* bad = roi_from_host(roi_host, n, Ho, Wo, &roi);
+        HEAL_REQUIRE(!bad, "conv1x1_roi: %s (n = %d, output %d x %d)", bad, n, Ho, Wo);
+    }
     hipStream_t s = (hipStream_t)stream;
     // Tile choice (BM, BN, KC).  Measured on MI355X at the PyramidFusion shapes (scripts/conv1x1_bench.py --sweep): the
     // smallest tile wins everywhere (64 channels x 64 pixels: 48 VGPR + 16 AGPR, 20 KB LDS -> 8 waves/SIMD); the kernel
@@ -309,24 +340,37 @@ static int conv1x1_launch(const float* x, const float* weight_frag, const float*
         if (stride == 1 && sscanf(e, "%d,%d,%d", &a_, &b_, &c_) == 3) { bm = a_; bn = b_; kc = c_; }
     }
     HEAL_REQUIRE(mpad % bm == 0, "conv1x1: padded Cout %d not a multiple of the tile height %d", mpad, bm);
+    if (roi.n) roi.perm = roi_spread((unsigned)ceil_div(HW, bn) * (unsigned)n);   // over the grid's (pixel tile, image) pairs
 #define HEAL_C1(BM_, BN_, KC_, ST_)                                                                              \
     if (bm == BM_ && bn == BN_ && kc == KC_ && stride == ST_) {                                                  \
         if (ksplit > 1)                                                                                          \
             HEAL_LAUNCH_EV2((k_conv1x1<BM_, BN_, KC_, ST_>), dim3(mpad / BM_, ceil_div(HW, BN_), n * ksplit), dim3(256), 0, s, \
                             ev.start, (hipEvent_t) nullptr,                                                      \
                             x, weight_frag, (const float*)nullptr, (const float*)nullptr, in_scale, cin, kpad, cout, HW, Wo, W, \
-                            H * W, 0, 0, 1, 0, 0, n, ksplit, partials);                                          \
+                            H * W, 0, 0, 1, 0, 0, n, ksplit, partials, NoRoi{});                                 \
         else                                                                                                     \
             HEAL_LAUNCH_EV2((k_conv1x1<BM_, BN_, KC_, ST_>), dim3(mpad / BM_, ceil_div(HW, BN_), n), dim3(256), 0, s, \
                             ev.start, ev.stop,                                                                   \
                             x, weight_frag, bias, residual, in_scale, cin, kpad, cout, HW, Wo, W, H * W, act, out_pixel_major, \
-                            d2s_k, d2s_ctot, d2s_coff, n, 1, y);                                                 \
+                            d2s_k, d2s_ctot, d2s_coff, n, 1, y, NoRoi{});                                        \
         launched = true;                                                                                         \
     }
     bool launched = false;
     const LaunchEvents ev = take_launch_events();   // measurement hook (heal_next_launch_events): the kernel's own begin / end
-    HEAL_C1(64, 64, 32, 1) HEAL_C1(64, 64, 32, 2)
-    HEAL_C1(128, 128, 32, 1) HEAL_C1(64, 128, 32, 1) HEAL_C1(128, 64, 32, 1)
+    if (roi.n) {   // the ROI instantiations: the production tile, both strides
+        HEAL_REQUIRE(bm == 64 && bn == 64 && kc == 32, "conv1x1_roi: the 64 x 64 x 32 tile only (HEAL_C1_CFG is set)");
+        const dim3 grid(mpad / 64, ceil_div(HW, 64), n);
+        if (stride == 1)
+            HEAL_LAUNCH_EV2((k_conv1x1<64, 64, 32, 1, true>), grid, dim3(256), 0, s, ev.start, ev.stop, x, weight_frag, bias, residual,
+                            in_scale, cin, kpad, cout, HW, Wo, W, H * W, act, 0, 1, 0, 0, n, 1, y, roi);
+        else
+            HEAL_LAUNCH_EV2((k_conv1x1<64, 64, 32, 2, true>), grid, dim3(256), 0, s, ev.start, ev.stop, x, weight_frag, bias, residual,
+                            in_scale, cin, kpad, cout, HW, Wo, W, H * W, act, 0, 1, 0, 0, n, 1, y, roi);
+        launched = true;
+    } else {
+        HEAL_C1(64, 64, 32, 1) HEAL_C1(64, 64, 32, 2)
+        HEAL_C1(128, 128, 32, 1) HEAL_C1(64, 128, 32, 1) HEAL_C1(128, 64, 32, 1)
+    }
 #undef HEAL_C1
     HEAL_REQUIRE(launched, "conv1x1: no kernel for tile (%d,%d,%d) stride %d", bm, bn, kc, stride);
     if (ksplit > 1) {
@@ -345,6 +389,20 @@ extern "C" int heal_conv1x1(const float* x, const float* weight_frag, const floa
     HEAL_REQUIRE(out_pixel_major == 0 || out_pixel_major == 1, "conv1x1: out_pixel_major must be 0 or 1");
     return conv1x1_launch(x, weight_frag, bias, residual, in_scale, n, cin, cout, H, W, stride, act, out_pixel_major, 1, 0, 0,
                           y, stream);
+}
+
+extern "C" int heal_conv1x1_roi(const float* x, const float* weight_frag, const float* bias, const float* residual,
+                                const float* in_scale, int n, int cin, int cout, int H, int W, int stride, int act,
+                                int out_pixel_major, const int32_t* roi_host, float* y, void* stream) {
+    HEAL_REQUIRE(out_pixel_major == 0, "conv1x1_roi: NCHW output only (out_pixel_major must be 0)");
+    HEAL_REQUIRE(roi_host, "conv1x1_roi: null ROI table");
+    return conv1x1_launch(x, weight_frag, bias, residual, in_scale, n, cin, cout, H, W, stride, act, 0, 1, 0, 0, y, stream, 1,
+                          nullptr, roi_host);
+}
+
+extern "C" int heal_roi_enabled(void) {
+    const char* e = getenv("HEAL_PYRAMID_ROI");   // read at every call: the walks ask before they plan a stage
+    return !(e && e[0] == '0' && e[1] == 0);
 }
 
 extern "C" int heal_conv1x1_d2s(const float* x, const float* weight_frag, const float* bias, int n, int cin, int cout, int H,

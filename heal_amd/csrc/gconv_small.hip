@@ -21,18 +21,27 @@
 // registers into four 16-B LDS stores), unconditional and clamped with the zero padding applied at the store.
 // Bytes: every input element is read once per tile (+ halo 1.2x, from L2), every output written once: HBM-bound at these
 // widths (0.33 GB per call at 128 channels x 256^2 x 5 agents).
+//
+// ROI (heal_grouped_small_conv3x3_roi; `roi`, a RoiTable kernel argument passed by value): one box (y0, y1, x0, x1) of OUTPUT pixels per
+// image.  A block whose TH x TW output tile (clipped to the map) holds no pixel of its image's box returns in the prologue, before
+// the first load and the barrier, and writes nothing: an exact test on rows and columns.  Kept blocks run the plain launch's
+// instructions on the same values.  It is the ROI = true instantiation of the kernel template (the default tile heights);
+// heal_grouped_small_conv3x3 launches the default, ROI = false, which takes no table and has no test.  A ROI launch also walks its (tile, image)
+// pairs in a spread order (roi_spread, common.h): the skipped tiles are then shared evenly among the XCDs.
 #include <stdlib.h>
 #include "common.h"
 #include "../../include/heal_amd.h"
+#include "../../include/heal_amd_roi.h"
+static_assert(heal::ROI_MAX_IMAGES == HEAL_WARP_MAX_AGENTS, "RoiTable rows");
 
 namespace heal {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-template <int CG, int TH, int STRIDE>
+template <int CG, int TH, int STRIDE, bool ROI = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_gconv_small(
     const float* __restrict__ x, const float* __restrict__ wq, const float* __restrict__ bias, int C, int H, int W, int Ho,
-    int Wo, int tiles_x, int relu, float* __restrict__ y) {
+    int Wo, int tiles_x, int relu, float* __restrict__ y, const typename RoiArg<ROI>::type roi) {
     static_assert(CG == 4 || CG == 8 || CG == 16, "4, 8 or 16 channels per group");
     static_assert(TH == 8 || TH == 16, "tile height");
     static_assert(STRIDE == 1 || STRIDE == 2, "stride");
@@ -46,10 +55,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
     constexpr int NB = CG / 4, NBH = CGH / 4;   // 16-B units per pixel of a group | read per (row, segment, dx) and pass
     __shared__ float4 sP[PR * PC * 4];       // [row][pixel][unit = channel / 4]
     __shared__ float4 sW[NSTEP * 16 / 4];    // [tap][ci][output channel of the super-group]
-    const Block3 bk = xcd_block();           // x: tile, y: super-group, z: image
+    Block3 bk = xcd_block();                 // x: tile, y: super-group, z: image
+    if constexpr (ROI) {                     // ROI launch: (tile, image) pairs in spread order (roi_spread): every XCD skips its share
+        const unsigned L = (bk.x + gridDim.x * bk.z) * roi.perm % (gridDim.x * gridDim.z);
+        bk.x = L % gridDim.x;
+        bk.z = L / gridDim.x;
+    }
     const int sg = bk.y, n = bk.z;
     const int ty = bk.x / tiles_x, tx = bk.x - ty * tiles_x;
     const int oy0 = ty * TH, ox0 = tx * TW;
+    if constexpr (ROI) {   // block-uniform, before any load or barrier: leave if no pixel of the tile lies in image n's box
+        const int y0 = roi.box[n][0], y1 = roi.box[n][1], x0 = roi.box[n][2], x1 = roi.box[n][3];
+        if (!(y0 < y1 && x0 < x1 && oy0 < y1 && min(oy0 + TH, Ho) > y0 && ox0 < x1 && min(ox0 + TW, Wo) > x0)) return;
+    }
     const int gy0 = oy0 * STRIDE - 1, gx0 = ox0 * STRIDE;          // patch row 0 | first interior column (16-B aligned)
     const int t = threadIdx.x, wave = t >> 6, l = t & 63;
     const size_t HW = (size_t)H * W, HWo = (size_t)Ho * Wo;
@@ -179,8 +197,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
 
 using namespace heal;
 
-extern "C" int heal_grouped_small_conv3x3(const float* x, const float* weight_q, const float* bias, int n, int channels,
-                                          int group_channels, int H, int W, int stride, int relu, float* y, void* stream) {
+static int gconv_small_launch(const float* x, const float* weight_q, const float* bias, int n, int channels, int group_channels,
+                              int H, int W, int stride, int relu, const int32_t* roi_host, float* y, void* stream) {
     HEAL_REQUIRE(group_channels == 4 || group_channels == 8 || group_channels == 16,
                  "grouped_small_conv3x3: 4, 8 or 16 channels per group (got %d)", group_channels);
     HEAL_REQUIRE(stride == 1 || stride == 2, "grouped_small_conv3x3: stride must be 1 or 2 (got %d)", stride);
@@ -195,16 +213,46 @@ extern "C" int heal_grouped_small_conv3x3(const float* x, const float* weight_q,
     if (const char* e = getenv("HEAL_GS_TH")) th = atoi(e) == 8 ? 8 : atoi(e) == 16 ? 16 : th;
     if (stride == 2 || group_channels == 16) th = 8;   // (a 16-row stride-2 patch is 72 KB)
     const int tw = stride == 1 ? 32 : 16;
+    RoiTable roi = no_roi();
+    if (roi_host) {
+        const char* bad = roi_from_host(roi_host, n, Ho, Wo, &roi);
+        HEAL_REQUIRE(!bad, "grouped_small_conv3x3_roi: %s (n = %d, output %d x %d)", bad, n, Ho, Wo);
+    }
     const int tiles_x = ceil_div(Wo, tw), tiles_y = ceil_div(Ho, th);
+    if (roi.n) roi.perm = roi_spread((unsigned)(tiles_x * tiles_y) * (unsigned)n);   // over the grid's (tile, image) pairs
     HEAL_REQUIRE(channels / 16 <= 65535 && n <= 65535, "grouped_small_conv3x3: grid limit");
     const dim3 grid(tiles_x * tiles_y, channels / 16, n);
     hipStream_t s_ = (hipStream_t)stream;
 #define HEAL_GS(CG_, TH_, ST_)                                                                                        \
     if (group_channels == CG_ && th == TH_ && stride == ST_)                                                          \
-        HEAL_LAUNCH_EV((k_gconv_small<CG_, TH_, ST_>), grid, dim3(256), 0, s_, x, weight_q, bias, channels, H, W, Ho, Wo, tiles_x, relu, y);
-    HEAL_GS(4, 16, 1) HEAL_GS(4, 8, 1) HEAL_GS(8, 16, 1) HEAL_GS(8, 8, 1)
-    HEAL_GS(4, 8, 2) HEAL_GS(8, 8, 2) HEAL_GS(16, 8, 1) HEAL_GS(16, 8, 2)
+        HEAL_LAUNCH_EV((k_gconv_small<CG_, TH_, ST_>), grid, dim3(256), 0, s_, x, weight_q, bias, channels, H, W, Ho, Wo, tiles_x, relu, y, NoRoi{});
+#define HEAL_GS_ROI(CG_, TH_, ST_)                                                                                    \
+    if (group_channels == CG_ && th == TH_ && stride == ST_) {                                                        \
+        HEAL_LAUNCH_EV((k_gconv_small<CG_, TH_, ST_, true>), grid, dim3(256), 0, s_, x, weight_q, bias, channels, H, W, Ho, Wo, tiles_x, relu, y, roi); \
+        launched = true;                                                                                              \
+    }
+    if (roi.n) {   // the ROI instantiations: the default tile height of every group width and stride
+        bool launched = false;
+        HEAL_GS_ROI(4, 16, 1) HEAL_GS_ROI(8, 8, 1) HEAL_GS_ROI(16, 8, 1) HEAL_GS_ROI(4, 8, 2) HEAL_GS_ROI(8, 8, 2) HEAL_GS_ROI(16, 8, 2)
+        HEAL_REQUIRE(launched, "grouped_small_conv3x3_roi: the default tile height only (HEAL_GS_TH is set)");
+    } else {
+        HEAL_GS(4, 16, 1) HEAL_GS(4, 8, 1) HEAL_GS(8, 16, 1) HEAL_GS(8, 8, 1)
+        HEAL_GS(4, 8, 2) HEAL_GS(8, 8, 2) HEAL_GS(16, 8, 1) HEAL_GS(16, 8, 2)
+    }
 #undef HEAL_GS
+#undef HEAL_GS_ROI
     HEAL_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int heal_grouped_small_conv3x3(const float* x, const float* weight_q, const float* bias, int n, int channels,
+                                          int group_channels, int H, int W, int stride, int relu, float* y, void* stream) {
+    return gconv_small_launch(x, weight_q, bias, n, channels, group_channels, H, W, stride, relu, nullptr, y, stream);
+}
+
+extern "C" int heal_grouped_small_conv3x3_roi(const float* x, const float* weight_q, const float* bias, int n, int channels,
+                                              int group_channels, int H, int W, int stride, int relu, const int32_t* roi_host,
+                                              float* y, void* stream) {
+    HEAL_REQUIRE(roi_host, "grouped_small_conv3x3_roi: null ROI table");
+    return gconv_small_launch(x, weight_q, bias, n, channels, group_channels, H, W, stride, relu, roi_host, y, stream);
 }

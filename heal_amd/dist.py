@@ -375,7 +375,9 @@ class _Sharded:
 
 class ShardedCollab(_Sharded):
     """HeterPyramidCollab (heter_pyramid_collab.py:133-209): the shard is every pyramid level's features + occupancy
-    scores, warped to the ego frame by the owning rank."""
+    scores, warped to the ego frame by the owning rank.  The stages run on the rank's own agents by the plain / camera-crop walk:
+    the per-image regions of interest of the single-process lean walk (HEAL_PYRAMID_ROI, PyramidFusion.lean_roi_plan) are not used
+    here."""
 
     def __new__(cls, model, rank, world, wire_dtype=None, collective=None, split=None):
         split = split or switches.get("HEAL_SPLIT")

@@ -1,5 +1,7 @@
 """PyramidFusion (reference: opencood/models/fuse_modules/pyramid_fuse.py:65-168) on top of the
 fused warp + occupancy-softmax kernel K5 (heal_warp_fuse)."""
+import functools
+
 import torch
 import torch.nn as nn
 
@@ -104,6 +106,50 @@ def _stage_needs(olo, ohi, layer, size_in):
         s_ = blk.stride
         olo, ohi = s_ * olo - 1, s_ * (ohi - 1) + 2
     return max(0, olo), min(size_in, ohi)
+
+
+def k5_read_box(H, W, window):
+    """The box (y0, y1, x0, x1) of a camera agent's H x W map that K5 reads when the agent's score is kept on `window` (crop_window):
+    the window's bilinear ring, clipped to the map, the columns rounded out to 16 bytes (heal_warp_fuse_levels_src's box rule)."""
+    wy0, wy1, wx0, wx1 = window
+    return max(0, wy0 - 1), min(H, wy1 + 1), max(0, wx0 - 1) // 4 * 4, min(W, -(-(wx1 + 1) // 4) * 4)
+
+
+@functools.lru_cache(maxsize=None)
+def stage_roi_plan(box, strides, H, W):
+    """Region-of-interest plan of ONE image through one stage of Bottlenecks (1x1 -> 3x3 stride s, padding 1 -> 1x1, + identity; the
+    first block's identity may be a 1x1 stride-s downsample): box = (y0, y1, x0, x1) of the stage OUTPUT that somebody reads,
+    strides = the blocks' strides, H x W the stage input ->
+        (per block {"conv1", "conv2", "conv3", "downsample"} -> the box of that convolution's OUTPUT that is needed,
+         the box of the stage INPUT that is read).
+    Backwards, the interval arithmetic of _stage_needs one block at a time: conv3, conv2 and the downsample are needed on the block's
+    output need O (conv3 is pointwise and adds the identity at the same pixel); conv1 (pointwise, at the block's input resolution)
+    on what the 3x3 reads for O: rows s lo - 1 .. s (hi - 1) + 1, clipped to the map; the block's input is read there too (the
+    identity's pixels, s O, lie inside), and that is the previous block's output need.  Pure function of shapes and configuration:
+    cached.  An empty box gives empty needs."""
+    y0, y1, x0, x1 = (int(v) for v in box)
+    sizes = [(int(H), int(W))]
+    for s_ in strides:
+        sizes.append(((sizes[-1][0] - 1) // s_ + 1, (sizes[-1][1] - 1) // s_ + 1))
+    if not (0 <= y0 <= y1 <= sizes[-1][0] and 0 <= x0 <= x1 <= sizes[-1][1]):
+        raise ValueError(f"stage_roi_plan: box {box} outside the {sizes[-1][0]} x {sizes[-1][1]} stage output")
+    blocks = []
+    for j in reversed(range(len(strides))):
+        s_, (hi_, wi_) = strides[j], sizes[j]
+        out = (y0, y1, x0, x1)
+        if y1 > y0 and x1 > x0:
+            y0, y1, x0, x1 = max(0, s_ * y0 - 1), min(hi_, s_ * (y1 - 1) + 2), max(0, s_ * x0 - 1), min(wi_, s_ * (x1 - 1) + 2)
+        else:
+            y0 = y1 = x0 = x1 = 0
+        blocks.append({"conv1": (y0, y1, x0, x1), "conv2": out, "conv3": out, "downsample": out})
+    return tuple(reversed(blocks)), (y0, y1, x0, x1)
+
+
+def box_union(a, b):
+    """Bounding box of two (y0, y1, x0, x1) boxes; None stands for "nothing"."""
+    if a is None or b is None:
+        return a if b is None else b
+    return min(a[0], b[0]), max(a[1], b[1]), min(a[2], b[2]), max(a[3], b[3])
 
 
 class PyramidFusion(ResNetBEVBackbone):
@@ -258,6 +304,50 @@ class PyramidFusion(ResNetBEVBackbone):
     def _cam_window(H, W, mod, cam_crop_info):
         return crop_window(H, W, cam_crop_info[mod][f"crop_ratio_H_{mod}"], cam_crop_info[mod][f"crop_ratio_W_{mod}"])
 
+    # ---- regions of interest: stages that run "in full" skip the tiles of the camera agents' maps that nobody reads -------------------
+    # A stage the crop plan leaves alone (plan[i] is None: the last level, whose content box reaches the border) runs on the full maps
+    # of all agents in one launch per convolution.  K5 reads a camera agent's map of that level only on the crop window's bilinear
+    # ring (k5_read_box) and multiplies everything else by a score of exactly zero, so going backwards through the blocks each
+    # convolution's output is needed on a known box (stage_roi_plan) -- and the kernels skip the 64-pixel / 8 x 32 tiles outside it
+    # (ops.conv1x1 / ops.grouped_conv3x3 with `roi`: same buffers, same single launch over all agents, blocks that leave early).  LiDAR
+    # agents get the full image.  Outside the boxes the stage output is UNINITIALISED memory: no needed pixel reads it (the plan is
+    # exactly the receptive field), the occupancy head may (its result is sliced to the K5 box afterwards).
+    # HEAL_PYRAMID_ROI=0 (ops.pyramid_roi_enabled) restores the walk without ROIs.
+    def lean_roi_plan(self, shape, plan, c0, c1, agent_modality_list, cam_crop_info):
+        """{stage index: ResNetModified.run_stage's `roi`} for the stages forward_collab_lean runs in full (plan[i] is None, i >= 1),
+        {} when ROIs are off.  shape: (H, W) of the pyramid input.  Last stage first: a stage's output need is the box K5 reads at
+        its level, united with what the NEXT stage reads of it (its input need when that stage runs by ROI too, its input crop when
+        it is cropped)."""
+        if not ops.pyramid_roi_enabled():
+            return {}
+        n = len(agent_modality_list)
+        sizes = [tuple(int(v) for v in shape)]
+        for i in range(self.layernum_):
+            h, w = sizes[-1]
+            for blk in getattr(self.resnet, f"layer{i}"):
+                h, w = (h - 1) // blk.stride + 1, (w - 1) // blk.stride + 1
+            sizes.append((h, w))
+        rois, next_need = {}, [None] * n        # next_need[k]: box of THIS stage's output the following stage reads for agent k
+        for i in reversed(range(1, self.layernum_)):
+            (hi_, wi_), (ho, wo) = sizes[i], sizes[i + 1]
+            if plan[i] is not None:
+                next_need = [tuple(plan[i][0]) if c0 <= k < c1 else (0, hi_, 0, wi_) for k in range(n)]
+                continue
+            strides = tuple(int(blk.stride) for blk in getattr(self.resnet, f"layer{i}"))
+            per_agent, needs_in = [], []
+            for k in range(n):
+                if c0 <= k < c1:
+                    box = box_union(k5_read_box(ho, wo, self._cam_window(ho, wo, agent_modality_list[k], cam_crop_info)), next_need[k])
+                else:
+                    box = (0, ho, 0, wo)
+                blocks, need_in = stage_roi_plan(box, strides, hi_, wi_)
+                per_agent.append(blocks)
+                needs_in.append(need_in)
+            rois[i] = [{name: [per_agent[k][j][name] for k in range(n)] for name in ("conv1", "conv2", "conv3", "downsample")}
+                       for j in range(len(strides))]
+            next_need = needs_in
+        return rois
+
     def lean_plan(self, like, record_len, agent_modality_list, cam_boxes, cam_crop_info):
         """What forward_collab_lean needs, or None when the lean walk does not apply: one scene of at most 8 agents at inference, the
         conditions of the camera-crop walk (_camcrop_args), a crop window for every camera agent, a cropped stage 0, the other agents
@@ -328,10 +418,11 @@ class PyramidFusion(ResNetBEVBackbone):
                              (gbox[0], gbox[2]))
         sources.append(level)
         shapes.append(tuple(int(v) for v in bg[0].shape[2:]))
+        rois = self.lean_roi_plan(like.shape[2:], plan, c0, c1, agent_modality_list, cam_crop_info)
         for i in range(1, self.layernum_):
             layer = getattr(self.resnet, f"layer{i}")
             if plan[i] is None:
-                full = self.resnet.run_stage(layer, full)
+                full = self.resnet.run_stage(layer, full, roi=rois.get(i))
             else:
                 (cy0, cy1, cx0, cx1), g2, p2 = plan[i]
                 nxt = torch.empty((n,) + tuple(bg[i].shape[1:]), dtype=dt, device=dev)
@@ -361,9 +452,7 @@ class PyramidFusion(ResNetBEVBackbone):
                 if c0 <= k < c1:
                     # the stack holds the camera agents' whole map; K5 needs it on the crop window's bilinear ring only (columns
                     # rounded out to 16 bytes): its staging is clipped to that box
-                    wy0, wy1, wx0, wx1 = self._cam_window(H, W, agent_modality_list[k], cam_crop_info)
-                    y0, y1 = max(0, wy0 - 1), min(H, wy1 + 1)
-                    x0, x1 = max(0, wx0 - 1) // 4 * 4, min(W, -(-(wx1 + 1) // 4) * 4)
+                    y0, y1, x0, x1 = k5_read_box(H, W, self._cam_window(H, W, agent_modality_list[k], cam_crop_info))
                 level.append((full[k, :, y0:y1, x0:x1], occ[k, 0, y0:y1, x0:x1], (y0, x0)))
             sources.append(level)
             shapes.append((H, W))

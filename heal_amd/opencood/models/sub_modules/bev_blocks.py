@@ -48,8 +48,11 @@ def conv3x3_enabled():
     return switches.on("HEAL_CONV3X3")
 
 
-def conv_bias_act(x, w, b, stride, padding, dilation=1, groups=1, relu=True, residual=None, out=None):
-    """conv2d + per-channel bias (+ residual) (+ ReLU); `out`: optional destination (a batch slice of a stage output).  The ResNeXt 32-group 3x3 convolutions run on the
+def conv_bias_act(x, w, b, stride, padding, dilation=1, groups=1, relu=True, residual=None, out=None, roi=None):
+    """conv2d + per-channel bias (+ residual) (+ ReLU); `out`: optional destination (a batch slice of a stage output).
+    roi: per-image output boxes [(y0, y1, x0, x1)] * n the caller needs (inference; the fusion pyramid's stages for camera agents): the
+    pointwise and the small-group 3x3 kernels skip the tiles outside them (ops.conv1x1 / ops.grouped_conv3x3, `roi`) and leave that
+    part of the result UNDEFINED; every other path computes the whole map.  The ResNeXt 32-group 3x3 convolutions run on the
     hand-written stencil kernel (heal_grouped_conv3x3); everything else is a library convolution WITHOUT
     bias followed by ONE fused in-place pass (heal_bias_act) instead of separate bias / add / ReLU kernels."""
     from heal_amd import ops
@@ -65,11 +68,11 @@ def conv_bias_act(x, w, b, stride, padding, dilation=1, groups=1, relu=True, res
     dl = dilation if isinstance(dilation, int) else dilation[0]
     if (groups > 1 and w.shape[2:] == (3, 3) and pd == 1 and dl == 1 and st in (1, 2) and residual is None
             and w.shape[1] in (4, 8, 16) and w.shape[0] == x.shape[1]):
-        return ops.grouped_conv3x3(x, w, b, groups, st, relu)
+        return ops.grouped_conv3x3(x, w, b, groups, st, relu, roi=roi)
     if groups == 1 and w.shape[2:] == (1, 1) and st in (1, 2) and pd == 0 and conv1x1_enabled():
         Ho, Wo = (int(x.shape[2]) - 1) // st + 1, (int(x.shape[3]) - 1) // st + 1
         if ops.conv1x1_supported(int(w.shape[1]), int(w.shape[0]), Ho * Wo, st, Wo):
-            return ops.conv1x1(x, w, b, residual, 1 if relu else 0, stride=st, out=out)
+            return ops.conv1x1(x, w, b, residual, 1 if relu else 0, stride=st, out=out, roi=roi)
     if (x.is_cuda and groups == 1 and tuple(w.shape[2:]) == (3, 3) and pd == 1 and dl == 1 and st in (1, 2)
             and (padding if isinstance(padding, int) else padding[1]) == 1
             and (stride if isinstance(stride, int) else stride[1]) == st and conv3x3_enabled()):
@@ -176,10 +179,11 @@ class ConvBN(nn.Module):
     owner; this helper only provides the folded forward."""
 
     @staticmethod
-    def run(x, conv, bn, relu, residual=None, out=None):
+    def run(x, conv, bn, relu, residual=None, out=None, roi=None):
+        """roi: per-image output boxes (conv_bias_act); the inference path alone looks at it -- the gradient path computes the map."""
         if out is not None and not grad_path(x, bn, conv):      # (inference: the agent-chunked / camera-crop stage walks)
             w, b = fold_bn(conv, bn)
-            y = conv_bias_act(x, w, b, conv.stride, conv.padding, conv.dilation, conv.groups, relu, residual, out=out)
+            y = conv_bias_act(x, w, b, conv.stride, conv.padding, conv.dilation, conv.groups, relu, residual, out=out, roi=roi)
             if y.data_ptr() != out.data_ptr():
                 out.copy_(y)
             return out
@@ -188,7 +192,7 @@ class ConvBN(nn.Module):
         if grad_path(x, bn, conv):   # training / fine-tuning: conv -> BatchNorm (batch statistics when training) -> + -> ReLU
             return grad_bn_act(bn, grad_conv(conv, x), relu, residual)
         w, b = fold_bn(conv, bn)
-        return conv_bias_act(x, w, b, conv.stride, conv.padding, conv.dilation, conv.groups, relu, residual)
+        return conv_bias_act(x, w, b, conv.stride, conv.padding, conv.dilation, conv.groups, relu, residual, roi=roi)
 
 
 def conv3x3(in_planes, out_planes, stride=1, groups=1, dilation=1):
@@ -298,18 +302,21 @@ class Bottleneck(nn.Module):
         s = self.stride
         return (int(x.shape[0]), self.conv3.out_channels, (int(x.shape[2]) - 1) // s + 1, (int(x.shape[3]) - 1) // s + 1)
 
-    def forward(self, x, out=None):
-        """out: optional destination of the block's result (inference; the agent-chunked stage walk of ResNetModified)."""
+    def forward(self, x, out=None, roi=None):
+        """out: optional destination of the block's result (inference; the agent-chunked stage walk of ResNetModified).
+        roi: None, or {"conv1", "conv2", "conv3", "downsample"} -> per-image output boxes [(y0, y1, x0, x1)] * n: what the caller
+        needs of each convolution's output (pyramid_fuse.stage_roi_plan).  Outside them the block's result is undefined."""
+        roi = roi or {}
         if not grad_path(x, self) and self._fusable(x):
             from heal_amd import ops
             y = ops.resnext_bottleneck(x.contiguous(), *self._fused_params())
             return y if out is None else out.copy_(y)
         identity = x
         if self.downsample is not None:
-            identity = ConvBN.run(x, self.downsample[0], self.downsample[1], relu=False)
-        y = ConvBN.run(x, self.conv1, self.bn1, relu=True)
-        y = ConvBN.run(y, self.conv2, self.bn2, relu=True)
-        return ConvBN.run(y, self.conv3, self.bn3, relu=True, residual=identity, out=out)
+            identity = ConvBN.run(x, self.downsample[0], self.downsample[1], relu=False, roi=roi.get("downsample"))
+        y = ConvBN.run(x, self.conv1, self.bn1, relu=True, roi=roi.get("conv1"))
+        y = ConvBN.run(y, self.conv2, self.bn2, relu=True, roi=roi.get("conv2"))
+        return ConvBN.run(y, self.conv3, self.bn3, relu=True, residual=identity, out=out, roi=roi.get("conv3"))
 
 
 class ResNetModified(nn.Module):
@@ -361,10 +368,15 @@ class ResNetModified(nn.Module):
         chunk = max(1, int(mb // per_agent))
         return chunk if chunk < n else 0
 
-    def run_stage(self, layer, x):
+    def run_stage(self, layer, x, roi=None):
+        """roi: None, or one Bottleneck.forward `roi` per block of the stage (boxes for all images of x)."""
         chunk = self.stage_chunk(layer, x)
         if not chunk:
-            return layer(x)
+            if roi is None:
+                return layer(x)
+            for blk, r in zip(layer, roi):
+                x = blk(x, roi=r)
+            return x
         n = int(x.shape[0])
         shape = list(x.shape)
         for blk in layer:
@@ -373,7 +385,8 @@ class ResNetModified(nn.Module):
         for a in range(0, n, chunk):
             xa = x[a:a + chunk]
             for j, blk in enumerate(layer):
-                xa = blk(xa, out=y[a:a + chunk]) if j == len(layer) - 1 else blk(xa)
+                r = None if roi is None else {k: v[a:a + chunk] for k, v in roi[j].items()}
+                xa = blk(xa, out=y[a:a + chunk], roi=r) if j == len(layer) - 1 else blk(xa, roi=r)
         return y
 
     def forward(self, x):

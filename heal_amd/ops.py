@@ -3070,26 +3070,50 @@ def grouped_small_fragments(weight, cg):
                     lambda: weight.detach().reshape(C // 16, 16, cg, 9).permute(0, 3, 2, 1).contiguous())   # [sg, tap, ci, co]
 
 
-def grouped_conv3x3(x, weight, bias, groups, stride=1, relu=True):
+def pyramid_roi_enabled():
+    """HEAL_PYRAMID_ROI (default on; the library reads it, heal_roi_enabled): may the fusion pyramid's lean walk run a stage with
+    per-image regions of interest?  Asked at every call."""
+    return bool(_capi.query("heal_roi_enabled"))
+
+
+def _roi_table(roi, n, Ho, Wo, who):
+    """Per-image output boxes [(y0, y1, x0, x1)] * n -> the host int32 [n, 4] array of the *_roi entry points (keep it alive over the
+    call).  The table travels by value in the kernel arguments: under graph capture the boxes are constants of the graph."""
+    t = np.ascontiguousarray(np.asarray(roi, dtype=np.int64).reshape(-1, 4))
+    if t.shape[0] != n or n > WARP_MAX_AGENTS:
+        raise _capi.HealAmdError(f"{who}: a ROI needs one (y0, y1, x0, x1) box for each of the {n} images, at most {WARP_MAX_AGENTS}")
+    if (t < 0).any() or (t[:, :2] > Ho).any() or (t[:, 2:] > Wo).any():
+        raise _capi.HealAmdError(f"{who}: ROI box outside the {Ho} x {Wo} output map: {t.tolist()}")
+    return np.ascontiguousarray(t.astype(np.int32))
+
+
+def grouped_conv3x3(x, weight, bias, groups, stride=1, relu=True, roi=None):
     """32-group 3x3 conv (padding 1, stride 1 | 2) with fused bias + ReLU.  x [n,C,H,W], weight [C,C/groups,3,3].  4, 8 or 16
     channels per group run on the 16-block 4x4x1 MFMA (heal_grouped_small_conv3x3; measured 5 agents, us: 128 ch 256^2 166 ->
     98, 256 ch 128^2 84 -> 59, 512 ch 64^2 78 -> 49, stride 2: 256 ch 256^2 207 -> 107, 512 ch 128^2 122 -> 68);
     HEAL_GCONV_MFMA=16 | 8 selects the older 16x16x4 kernel (one m-tile per 16-channel group: 53 us; pairs of 8-channel groups
-    with block-diagonal weights: 98 us), =0 the vector-ALU stencil, which also takes the shapes the MFMA kernels do not."""
+    with block-diagonal weights: 98 us), =0 the vector-ALU stencil, which also takes the shapes the MFMA kernels do not.
+    roi: per-image output boxes [(y0, y1, x0, x1)] * n (heal_grouped_small_conv3x3_roi): tiles that hold no pixel of their image's
+    box are not computed and their part of the result is UNINITIALISED memory; the other kernels compute the whole map."""
     x = _need(x, torch.float32, "x")
     weight = _need(weight, torch.float32, "weight")
     n, C, H, W = (int(v) for v in x.shape)
     bias = _need_bias(bias, C, "grouped_conv3x3")
     Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
-    y = torch.empty((n, C, Ho, Wo), dtype=torch.float32, device=x.device)
+    y = _out_or_empty(None, (n, C, Ho, Wo), x.device, "grouped_conv3x3")
     cg = C // groups
     mode = switches.get("HEAL_GCONV_MFMA")
     if C % 16 == 0 and W % 4 == 0 and Wo % 4 == 0 and mode in ("1", "s") and cg in (4, 8, 16):
         frag = grouped_small_fragments(weight, cg)
+        table = _roi_table(roi, n, Ho, Wo, "grouped_conv3x3") if roi is not None else None
         with _Timed(f"grouped_conv3x3_c{C}" + ("_s2" if stride == 2 else ""), 2.0 * 9 * n * C * cg * Ho * Wo,
                     4.0 * n * C * (H * W + Ho * Wo), kernel_events=True):
-            _capi.call("heal_grouped_small_conv3x3", _ptr(x), _ptr(frag), _ptr(bias), n, C, cg, H, W, int(stride),
-                       int(bool(relu)), _ptr(y), _stream())
+            if table is not None:
+                _capi.call("heal_grouped_small_conv3x3_roi", _ptr(x), _ptr(frag), _ptr(bias), n, C, cg, H, W, int(stride),
+                           int(bool(relu)), ctypes.c_void_p(table.ctypes.data), _ptr(y), _stream())
+            else:
+                _capi.call("heal_grouped_small_conv3x3", _ptr(x), _ptr(frag), _ptr(bias), n, C, cg, H, W, int(stride),
+                           int(bool(relu)), _ptr(y), _stream())
         return y
     if stride == 1 and C % 16 == 0 and W % 4 == 0 and ((cg == 16 and mode != "0") or (cg == 8 and mode == "8")):   # mode "16" | "8"
         frag = grouped16_fragments(weight, cg)
@@ -3272,11 +3296,14 @@ def _out_like(out, shape, device, who, name="out"):
     return _out_or_empty(out, shape, device, f"{who} ({name})" if name != "out" else who)
 
 
-def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixel_major=False, out=None):
+def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixel_major=False, out=None, roi=None):
     """Pointwise convolution with fused prologue / epilogue: act(W (in_scale . x) + bias (+ residual));
     act 0 none | 1 ReLU | 2 SiLU; stride 1 | 2.  x [n,Cin,H,W] f32 cuda, w [Cout,Cin,1,1], in_scale [n,Cin].
     pixel_major=True: the result comes back as [n, Ho*Wo, Cout] (a pixel's channels contiguous) instead of NCHW.
-    out: optional destination (NCHW result only), e.g. the batch slice of a stage's output that an agent chunk fills."""
+    out: optional destination (NCHW result only), e.g. the batch slice of a stage's output that an agent chunk fills.
+    roi: per-image output boxes [(y0, y1, x0, x1)] * n (heal_conv1x1_roi; NCHW result only): 64-pixel tiles that hold no pixel of
+    their image's box are not computed and their part of the result keeps what the buffer held (uninitialised memory for a new
+    one).  The split-K and the opt-in kernels take no ROI: they compute the whole map."""
     x = _need(x, torch.float32, "x")
     n, cin, H, W = (int(v) for v in x.shape)
     cout = int(w.shape[0])
@@ -3285,8 +3312,8 @@ def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixe
     hard_ok = stride in (1, 2) and ((Ho * Wo) % 4 == 0 if stride == 1 else Wo % 4 == 0)
     if int(w.shape[1]) != cin or not hard_ok:
         raise _capi.HealAmdError(f"conv1x1: unsupported shape Cin={cin} Cout={cout} HxW={H}x{W} stride={stride}")
-    if out is not None and pixel_major:
-        raise _capi.HealAmdError("conv1x1: `out` is for the NCHW result")
+    if (out is not None or roi is not None) and pixel_major:
+        raise _capi.HealAmdError("conv1x1: `out` and `roi` are for the NCHW result")
     nprod = arith_products()
     if (nprod and stride == 1 and not pixel_major and in_scale is None and w.dtype == torch.float32
             and _capi.query("heal_conv1x1_split_supported", cin, cout, H, W)):
@@ -3337,11 +3364,17 @@ def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixe
                        _ptr(residual) if residual is not None else None, _ptr(in_scale) if in_scale is not None else None,
                        n, cin, cout, H, W, int(act), ksplit, _ptr(y), _ptr(ws), ws.numel(), _stream())
         return y
+    table = _roi_table(roi, n, Ho, Wo, "conv1x1") if roi is not None else None
     with _Timed(f"conv1x1_{cin}_{cout}" + ("_s2" if stride == 2 else ""), 2.0 * n * cin * cout * Ho * Wo,
                 4.0 * n * (cin * Ho * Wo + cout * Ho * Wo * (2 if residual is not None else 1)), kernel_events=True):
-        _capi.call("heal_conv1x1", _ptr(x), _ptr(frag), _ptr(bias) if bias is not None else None,
-                   _ptr(residual) if residual is not None else None, _ptr(in_scale) if in_scale is not None else None,
-                   n, cin, cout, H, W, int(stride), int(act), int(bool(pixel_major)), _ptr(y), _stream())
+        if table is not None:
+            _capi.call("heal_conv1x1_roi", _ptr(x), _ptr(frag), _ptr(bias) if bias is not None else None,
+                       _ptr(residual) if residual is not None else None, _ptr(in_scale) if in_scale is not None else None,
+                       n, cin, cout, H, W, int(stride), int(act), 0, ctypes.c_void_p(table.ctypes.data), _ptr(y), _stream())
+        else:
+            _capi.call("heal_conv1x1", _ptr(x), _ptr(frag), _ptr(bias) if bias is not None else None,
+                       _ptr(residual) if residual is not None else None, _ptr(in_scale) if in_scale is not None else None,
+                       n, cin, cout, H, W, int(stride), int(act), int(bool(pixel_major)), _ptr(y), _stream())
     return y
 
 
