@@ -23,6 +23,9 @@
 // partial[term][tile] -> fixed-order fp64 sum.  No path depends on an address: two launches on the same values are bit-equal
 // wherever the data lies.  fp32 arithmetic (the library is built with -ffp-contract=off); the direction bin is computed in double
 // from the label as stored, as the reference does whatever the label type (its anchor_yaw_map is a float64 tensor).
+//
+// loss_common.h holds what this file shares with unc_loss.hip and kd_loss.hip: the per-anchor cls / smooth-L1 / dir blocks
+// k_dl_det calls, k_dl_count, k_dl_finish and the host side of the anchor-head entry points (dl_head_*).
 #include "loss_common.h"
 
 namespace heal {
@@ -98,20 +101,10 @@ __global__ __launch_bounds__(256) void k_dl_det(const float* __restrict__ cls, c
         const float pv = live ? (float)pos[lab0 + a] : 0.f;
         const float nv = live ? (float)neg[lab0 + a] : 0.f;
         const bool is_pos = pv > 0.f;
-        // cls
-        {
-            const size_t at = ((size_t)n * A + a) * HW + (size_t)pix;
-            const float x = live ? cls[at] : 0.f;
-            const float w = ((is_pos ? prm.pos_cls_weight : 0.f) + (nv > 0.f ? 1.0f : 0.f)) / nrm;
-            float l, dx;
-            dl_focal(x, pv, w, prm.alpha, l, dx);
-            if (w == 0.f) { l = 0.f; dx = 0.f; }          // pos = neg = 0: exactly nothing, whatever the logit
-            s_cls += l;
-            if (gcls != nullptr && live) gcls[at] = dx * prm.scale[0];
-        }
+        dl_cls_block(cls, gcls, ((size_t)n * A + a) * HW + (size_t)pix, live, pv, nv, is_pos, nrm, prm, s_cls);
         const float wr = 1.0f / nrm;
         const size_t t0 = (lab0 + a) * 7;
-        // reg: seven smooth-L1 terms, the yaw as sin(a) cos(b) against cos(a) sin(b)
+        // reg: seven smooth-L1 terms, each gradient stored at once
         float tyaw_f = 0.f;
         double tyaw = 0.0;
         if (is_pos) {
@@ -122,48 +115,12 @@ __global__ __launch_bounds__(256) void k_dl_det(const float* __restrict__ cls, c
         for (int k = 0; k < 7; ++k) {
             const size_t at = ((size_t)n * 7 * A + (size_t)a * 7 + k) * HW + (size_t)pix;
             float g = 0.f;
-            if (is_pos) {
-                const float x = reg[at];
-                float d, chain = 1.0f;
-                if (k == 6) {
-                    const float sa = sinf(x), ca = cosf(x), sb = sinf(tyaw_f), cb = cosf(tyaw_f);
-                    d = sa * cb - ca * sb;
-                    chain = ca * cb + sa * sb;
-                } else {
-                    d = x - (float)tgt[t0 + k];
-                }
-                const float ad = fabsf(d);
-                const bool small = ad <= prm.inv_sigma2;
-                const float l = small ? 0.5f * (ad * ad) * prm.sigma2 : ad - 0.5f * prm.inv_sigma2;
-                const float dl = small ? d * prm.sigma2 : (d > 0.f ? 1.0f : -1.0f);
-                s_reg += l * wr;
-                g = dl * chain * wr * prm.scale[1];
-            }
+            if (is_pos) s_reg += dl_smooth_l1(k == 6, reg[at], k == 6 ? tyaw_f : (float)tgt[t0 + k], wr, prm, g);
             if (greg != nullptr && live) greg[at] = g;
         }
-        // dir: two-bin cross-entropy = softplus(other - chosen)
-        if (dir != nullptr) {
-            const size_t at0 = ((size_t)n * 2 * A + (size_t)a * 2) * HW + (size_t)pix;
-            float g0 = 0.f, g1 = 0.f;
-            if (is_pos) {
-                const double two_pi = 6.283185307179586476925286766559, pi = 3.141592653589793238462643383279;
-                const double v = (tyaw + prm.yaw[a]) - prm.dir_offset;
-                const double off = v - floor(v / two_pi) * two_pi;
-                const int bin = min(max((int)floor(off / pi), 0), 1);
-                const float l0 = dir[at0], l1 = dir[at0 + HW];
-                const float z = bin == 0 ? l1 - l0 : l0 - l1;          // other - chosen
-                float p, q, e;
-                dl_sigmoid(z, p, q, e);
-                s_dir += (fmaxf(z, 0.f) + log1pf(e)) * wr;
-                const float go = p * wr * prm.scale[2];                // d / d other; chosen gets the negative
-                g0 = bin == 0 ? -go : go;
-                g1 = bin == 0 ? go : -go;
-            }
-            if (gdir != nullptr && live) {
-                gdir[at0] = g0;
-                gdir[at0 + HW] = g1;
-            }
-        }
+        if (dir != nullptr)
+            dl_dir_block(dir, gdir, ((size_t)n * 2 * A + (size_t)a * 2) * HW + (size_t)pix, HW, live, is_pos, tyaw, prm.yaw[a], wr, prm,
+                         s_dir);
     }
     s_cls = wave_sum(s_cls);
     s_reg = wave_sum(s_reg);
@@ -174,6 +131,15 @@ __global__ __launch_bounds__(256) void k_dl_det(const float* __restrict__ cls, c
         partials[(size_t)2 * total_tiles + tile] = s_dir;
     }
 }
+
+struct DetLaunch : HeadLaunch {
+    DetParams prm;
+    template <typename T, int A>
+    void launch() const {
+        hipLaunchKernelGGL((k_dl_det<T, A>), grid, dim3(256), 0, s, cls, reg, dir, (const T*)pos, (const T*)neg, (const T*)tgt,
+                           (const int*)counts, HW, tiles, total, prm, gcls, greg, gdir, partials);
+    }
+};
 
 // ---------------------------------------------------------------------------------------------------------- occupancy
 template <typename T>
@@ -334,74 +300,23 @@ static bool occ_layout(int n, int H, int W, int levels, const int* ks, OccLevels
 
 using namespace heal;
 
-extern "C" size_t heal_det_loss_workspace(int n, int anchors, int H, int W) {
-    long long tiles;
-    if (anchors > DL_MAX_A || !dl_map_ok(n, 7 * anchors, H, W, &tiles)) return 0;
-    return align_up((size_t)n * DL_CB * sizeof(int)) + align_up((size_t)3 * tiles * sizeof(float));
-}
+extern "C" size_t heal_det_loss_workspace(int n, int anchors, int H, int W) { return dl_head_workspace(n, anchors, H, W, 3); }
 
 extern "C" int heal_det_loss(const float* cls_preds, const float* reg_preds, const float* dir_preds, const void* pos_equal_one,
                              const void* neg_equal_one, const void* targets, int labels_f64, int n, int anchors, int H, int W,
                              float pos_cls_weight, float alpha, float sigma, float cls_weight, float reg_weight, float dir_weight,
                              const double* anchor_yaw, double dir_offset, float* terms, float* grad_cls, float* grad_reg,
                              float* grad_dir, void* ws, size_t ws_bytes, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    long long tiles_ll;
-    HEAL_REQUIRE(anchors >= 1 && anchors <= DL_MAX_A && dl_map_ok(n, 7 * anchors, H, W, &tiles_ll),
-                 "det_loss: bad shape n=%d anchors=%d (1..%d) H=%d W=%d", n, anchors, DL_MAX_A, H, W);
-    HEAL_REQUIRE(cls_preds && reg_preds && pos_equal_one && neg_equal_one && targets && terms,
-                 "det_loss: cls_preds, reg_preds, the three labels and terms must be set");
-    HEAL_REQUIRE(dir_preds == nullptr || anchor_yaw != nullptr, "det_loss: dir_preds needs anchor_yaw[anchors]");
-    HEAL_REQUIRE(dir_preds != nullptr || grad_dir == nullptr, "det_loss: grad_dir without dir_preds");
-    HEAL_REQUIRE(sigma > 0.f, "det_loss: sigma must be positive, got %g", (double)sigma);
-    const size_t need = heal_det_loss_workspace(n, anchors, H, W);
-    HEAL_REQUIRE(ws != nullptr && ws_bytes >= need, "det_loss: workspace of %zu bytes, need %zu (heal_det_loss_workspace)", ws_bytes,
-                 need);
-    Arena arena(ws, ws_bytes);
-    int* counts = arena.take<int>((size_t)n * DL_CB);
-    float* partials = arena.take<float>((size_t)3 * tiles_ll);
-    const int HW = H * W, tiles = ceil_div(HW, DL_TILE), total = (int)tiles_ll;
-    DetParams prm;
-    prm.pos_cls_weight = pos_cls_weight;
-    prm.alpha = alpha;
-    prm.sigma2 = sigma * sigma;
-    prm.inv_sigma2 = 1.0f / (sigma * sigma);
-    prm.scale[0] = (float)((double)cls_weight / n);
-    prm.scale[1] = (float)((double)reg_weight / n);
-    prm.scale[2] = (float)((double)dir_weight / n);
-    for (int a = 0; a < DL_MAX_A; ++a) prm.yaw[a] = (anchor_yaw != nullptr && a < anchors) ? anchor_yaw[a] : 0.0;
-    prm.dir_offset = dir_offset;
-    const long long per_sample = (long long)HW * anchors;
-    const dim3 block(256), grid((unsigned)ceil_div(total, DL_WAVES));
-    const LaunchEvents ev = take_launch_events();
-    const dim3 cgrid(DL_CB, n);
-#define DL_DET_LAUNCH(T, A_)                                                                                                       \
-    hipLaunchKernelGGL((k_dl_det<T, A_>), grid, block, 0, s, cls_preds, reg_preds, dir_preds, (const T*)pos_equal_one,               \
-                       (const T*)neg_equal_one, (const T*)targets, (const int*)counts, HW, tiles, total, prm, grad_cls, grad_reg,    \
-                       grad_dir, partials)
-#define DL_DET_DISPATCH(T)                                                                                                         \
-    do {                                                                                                                           \
-        HEAL_LAUNCH_EV2(k_dl_count<T>, cgrid, block, 0, s, ev.start, nullptr, (const T*)pos_equal_one, per_sample, counts);         \
-        HEAL_LAUNCH_CHECK();                                                                                                       \
-        switch (anchors) {                                                                                                         \
-            case 1: DL_DET_LAUNCH(T, 1); break;                                                                                    \
-            case 2: DL_DET_LAUNCH(T, 2); break;                                                                                    \
-            case 3: DL_DET_LAUNCH(T, 3); break;                                                                                    \
-            default: DL_DET_LAUNCH(T, 4); break;                                                                                   \
-        }                                                                                                                          \
-    } while (0)
-    if (labels_f64) DL_DET_DISPATCH(double); else DL_DET_DISPATCH(float);
-#undef DL_DET_DISPATCH
-#undef DL_DET_LAUNCH
-    HEAL_LAUNCH_CHECK();
-    FinishScales sc;
-    sc.s[0] = (double)prm.scale[0];
-    sc.s[1] = (double)prm.scale[1];
-    sc.s[2] = dir_preds != nullptr ? (double)prm.scale[2] : 0.0;
-    sc.s[3] = 0.0;
-    HEAL_LAUNCH_EV2(k_dl_finish, dim3(1), block, 0, s, nullptr, ev.stop, (const float*)partials, total, 3, sc, terms);
-    HEAL_LAUNCH_CHECK();
-    return 0;
+    HEAL_REQUIRE(dl_head_shape_ok(n, anchors, H, W), "det_loss: bad shape n=%d anchors=%d (1..%d) H=%d W=%d", n, anchors, DL_MAX_A, H,
+                 W);
+    DetLaunch l{{cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targets, grad_cls, grad_reg, grad_dir,
+                 (hipStream_t)stream}};
+    if (dl_head_setup("det_loss", "cls_preds, reg_preds", cls_preds && reg_preds && pos_equal_one && neg_equal_one && targets && terms,
+                      anchor_yaw, sigma, ws, ws_bytes, n, anchors, H, W, 3, l))
+        return 1;
+    dl_det_params(l.prm, pos_cls_weight, alpha, sigma, cls_weight, reg_weight, dir_weight, n, anchor_yaw, anchors, dir_offset);
+    const FinishScales sc{{(double)l.prm.scale[0], (double)l.prm.scale[1], dir_preds != nullptr ? (double)l.prm.scale[2] : 0.0, 0.0}};
+    return dl_head_run(l, labels_f64, n, anchors, 3, sc, terms);
 }
 
 extern "C" size_t heal_occ_loss_workspace(int n, int H, int W, int levels, const int* relative_downsample) {

@@ -20,10 +20,10 @@
 // product's rounding moves p by less than |d| * 2^-23 * p <= 5e-8.
 //
 // Reduction: no floating-point atomics.  Lane sums over channels in index order -> the waves' sums in wave order -> xor
-// tree over the 64 lanes -> partial[block] (already divided by the element count); k_kd_finish (one block) adds the partials in a fixed order in fp64.  Two
-// launches on the same values are bit-equal wherever the data lies: no path depends on an address.
-#include "common.h"
-#include "../../include/heal_amd.h"
+// tree over the 64 lanes -> partial[block] (already divided by the element count); k_dl_finish (loss_common.h: one block, one term,
+// scale 1) adds the partials in a fixed order in fp64.  Two launches on the same values are bit-equal wherever the data lies: no
+// path depends on an address.
+#include "loss_common.h"
 
 namespace heal {
 
@@ -163,20 +163,6 @@ __global__ __launch_bounds__(256) void k_kd_generic(const float* __restrict__ st
     kd_block_partial<KD_WAVES>(live ? kl : 0.f, skl, wave, lane, partials);
 }
 
-// loss <- sum of the partials in a fixed order: thread t adds partials t, t + 256, ... in fp64, then a fixed LDS tree
-__global__ __launch_bounds__(256) void k_kd_finish(const float* __restrict__ partials, int n_partials, float* __restrict__ loss) {
-    __shared__ double acc[256];
-    double v = 0.0;
-    for (int i = threadIdx.x; i < n_partials; i += 256) v += (double)partials[i];
-    acc[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) acc[threadIdx.x] += acc[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = (float)acc[0];
-}
-
 static bool kd_shape_ok(int n, int channels, int H, int W, long long* blocks) {
     if (n < 1 || channels < 1 || H < 1 || W < 1) return false;
     const long long hw = (long long)H * W;
@@ -219,7 +205,8 @@ extern "C" int heal_kd_kl_loss(const float* student, const float* teacher, int n
         default: HEAL_LAUNCH_EV2(k_kd_generic, grid, block, 0, s, ev.start, nullptr, student, teacher, channels, HW, tiles, inv_count, grad, partials); break;
     }
     HEAL_LAUNCH_CHECK();
-    HEAL_LAUNCH_EV2(k_kd_finish, dim3(1), block, 0, s, nullptr, ev.stop, (const float*)partials, (int)blocks, loss);
+    const FinishScales sc{{1.0, 0.0, 0.0, 0.0}};            // one term; (float)(acc * 1.0) == (float)acc
+    HEAL_LAUNCH_EV2(k_dl_finish, dim3(1), block, 0, s, nullptr, ev.stop, (const float*)partials, (int)blocks, 1, sc, loss);
     HEAL_LAUNCH_CHECK();
     return 0;
 }

@@ -8,9 +8,10 @@
 // tile is one 256-B access, the labels are read where they lie, no LDS, no barrier, no floating-point atomic.  Phases: k_dl_count
 // (integer positives per sample), k_ul_unc (gradients + one partial per tile and term), k_dl_finish (fixed-order fp64 sums).
 //
-// The cls, reg and dir blocks of k_ul_unc are k_dl_det's, statement by statement: on the same inputs their partials, and with
-// them the finished terms and grad_cls / grad_dir, are bit-equal to heal_det_loss's (tests/test_gpu_unc_loss.py holds them to it).
-// The unc block reads the seven regression values and targets the reg block has loaded.
+// The cls, reg and dir blocks of k_ul_unc are the same functions k_dl_det calls (dl_cls_block, dl_smooth_l1, dl_dir_block of
+// loss_common.h): on the same inputs their partials, and with them the finished terms and grad_cls / grad_dir, are bit-equal to
+// heal_det_loss's (tests/test_gpu_unc_loss.py holds them to it).  The unc block reads the seven regression values and targets the
+// reg block has loaded.  The host side -- checks, DetParams, count -> pass -> finish -- is heal_det_loss's too (dl_head_*).
 #include "loss_common.h"
 #include "../../include/heal_amd_unc.h"
 
@@ -119,20 +120,10 @@ __global__ __launch_bounds__(256) void k_ul_unc(const float* __restrict__ cls, c
         const float pv = live ? (float)pos[lab0 + a] : 0.f;
         const float nv = live ? (float)neg[lab0 + a] : 0.f;
         const bool is_pos = pv > 0.f;
-        // cls (k_dl_det)
-        {
-            const size_t at = ((size_t)n * A + a) * HW + (size_t)pix;
-            const float x = live ? cls[at] : 0.f;
-            const float w = ((is_pos ? prm.pos_cls_weight : 0.f) + (nv > 0.f ? 1.0f : 0.f)) / nrm;
-            float l, dx;
-            dl_focal(x, pv, w, prm.alpha, l, dx);
-            if (w == 0.f) { l = 0.f; dx = 0.f; }          // pos = neg = 0: exactly nothing, whatever the logit
-            s_cls += l;
-            if (gcls != nullptr && live) gcls[at] = dx * prm.scale[0];
-        }
+        dl_cls_block(cls, gcls, ((size_t)n * A + a) * HW + (size_t)pix, live, pv, nv, is_pos, nrm, prm, s_cls);
         const float wr = 1.0f / nrm;
         const size_t t0 = (lab0 + a) * 7;
-        // reg (k_dl_det): seven smooth-L1 terms, the yaw as sin(a) cos(b) against cos(a) sin(b); the values stay for the unc term
+        // reg: seven smooth-L1 terms; the gradients and residuals stay for the unc term
         float tyaw_f = 0.f;
         double tyaw = 0.0;
         if (is_pos) {
@@ -148,20 +139,7 @@ __global__ __launch_bounds__(256) void k_ul_unc(const float* __restrict__ cls, c
             if (is_pos) {
                 const float x = reg[at];
                 const float tk = k == 6 ? tyaw_f : (float)tgt[t0 + k];
-                float d, chain = 1.0f;
-                if (k == 6) {
-                    const float sa = sinf(x), ca = cosf(x), sb = sinf(tyaw_f), cb = cosf(tyaw_f);
-                    d = sa * cb - ca * sb;
-                    chain = ca * cb + sa * sb;
-                } else {
-                    d = x - tk;
-                }
-                const float ad = fabsf(d);
-                const bool small = ad <= prm.inv_sigma2;
-                const float l = small ? 0.5f * (ad * ad) * prm.sigma2 : ad - 0.5f * prm.inv_sigma2;
-                const float dl = small ? d * prm.sigma2 : (d > 0.f ? 1.0f : -1.0f);
-                s_reg += l * wr;
-                g[k] = dl * chain * wr * prm.scale[1];
+                s_reg += dl_smooth_l1(k == 6, x, tk, wr, prm, g[k]);
                 diff[k] = tk != tk ? 0.f : x - tk;
             }
         }
@@ -194,29 +172,9 @@ __global__ __launch_bounds__(256) void k_ul_unc(const float* __restrict__ cls, c
 #pragma unroll
             for (int k = 0; k < 7; ++k) greg[((size_t)n * 7 * A + (size_t)a * 7 + k) * HW + (size_t)pix] = g[k];
         }
-        // dir (k_dl_det): two-bin cross-entropy = softplus(other - chosen)
-        if (dir != nullptr) {
-            const size_t at0 = ((size_t)n * 2 * A + (size_t)a * 2) * HW + (size_t)pix;
-            float g0 = 0.f, g1 = 0.f;
-            if (is_pos) {
-                const double two_pi = 6.283185307179586476925286766559, pi = 3.141592653589793238462643383279;
-                const double v = (tyaw + prm.yaw[a]) - prm.dir_offset;
-                const double off = v - floor(v / two_pi) * two_pi;
-                const int bin = min(max((int)floor(off / pi), 0), 1);
-                const float l0 = dir[at0], l1 = dir[at0 + HW];
-                const float z = bin == 0 ? l1 - l0 : l0 - l1;          // other - chosen
-                float p, q, e;
-                dl_sigmoid(z, p, q, e);
-                s_dir += (fmaxf(z, 0.f) + log1pf(e)) * wr;
-                const float go = p * wr * prm.scale[2];                // d / d other; chosen gets the negative
-                g0 = bin == 0 ? -go : go;
-                g1 = bin == 0 ? go : -go;
-            }
-            if (gdir != nullptr && live) {
-                gdir[at0] = g0;
-                gdir[at0 + HW] = g1;
-            }
-        }
+        if (dir != nullptr)
+            dl_dir_block(dir, gdir, ((size_t)n * 2 * A + (size_t)a * 2) * HW + (size_t)pix, HW, live, is_pos, tyaw, prm.yaw[a], wr, prm,
+                         s_dir);
     }
     s_cls = wave_sum(s_cls);
     s_reg = wave_sum(s_reg);
@@ -230,42 +188,25 @@ __global__ __launch_bounds__(256) void k_ul_unc(const float* __restrict__ cls, c
     }
 }
 
-struct UncLaunch {
-    const float *cls, *reg, *unc, *dir;
-    const void *pos, *neg, *tgt;
-    const int* counts;
-    int HW, tiles, total;
+struct UncLaunch : HeadLaunch {
+    const float* unc;
+    float* gunc;
+    int dim;
     UncParams prm;
-    float *gcls, *greg, *gunc, *gdir, *partials;
-    dim3 grid;
-    hipStream_t s;
+    template <typename T, int A, int DIM>
+    void launch_dim() const {
+        hipLaunchKernelGGL((k_ul_unc<T, A, DIM>), grid, dim3(256), 0, s, cls, reg, unc, dir, (const T*)pos, (const T*)neg,
+                           (const T*)tgt, (const int*)counts, HW, tiles, total, prm, gcls, greg, gunc, gdir, partials);
+    }
+    template <typename T, int A>
+    void launch() const {
+        switch (dim) {
+            case 2: launch_dim<T, A, 2>(); break;
+            case 3: launch_dim<T, A, 3>(); break;
+            default: launch_dim<T, A, 7>(); break;
+        }
+    }
 };
-
-template <typename T, int A, int DIM>
-static void ul_launch(const UncLaunch& u) {
-    hipLaunchKernelGGL((k_ul_unc<T, A, DIM>), u.grid, dim3(256), 0, u.s, u.cls, u.reg, u.unc, u.dir, (const T*)u.pos,
-                       (const T*)u.neg, (const T*)u.tgt, u.counts, u.HW, u.tiles, u.total, u.prm, u.gcls, u.greg, u.gunc, u.gdir,
-                       u.partials);
-}
-
-template <typename T, int A>
-static void ul_launch_dim(const UncLaunch& u, int dim) {
-    switch (dim) {
-        case 2: ul_launch<T, A, 2>(u); break;
-        case 3: ul_launch<T, A, 3>(u); break;
-        default: ul_launch<T, A, 7>(u); break;
-    }
-}
-
-template <typename T>
-static void ul_launch_anchors(const UncLaunch& u, int anchors, int dim) {
-    switch (anchors) {
-        case 1: ul_launch_dim<T, 1>(u, dim); break;
-        case 2: ul_launch_dim<T, 2>(u, dim); break;
-        case 3: ul_launch_dim<T, 3>(u, dim); break;
-        default: ul_launch_dim<T, 4>(u, dim); break;
-    }
-}
 
 }  // namespace heal
 
@@ -278,11 +219,7 @@ extern "C" int heal_unc_loss_supported(int anchors, int dim, int xy_type, int an
     return (with_dir && anchors != 2) ? 0 : 1;
 }
 
-extern "C" size_t heal_unc_loss_workspace(int n, int anchors, int H, int W) {
-    long long tiles;
-    if (anchors > DL_MAX_A || !dl_map_ok(n, 7 * anchors, H, W, &tiles)) return 0;
-    return align_up((size_t)n * DL_CB * sizeof(int)) + align_up((size_t)4 * tiles * sizeof(float));
-}
+extern "C" size_t heal_unc_loss_workspace(int n, int anchors, int H, int W) { return dl_head_workspace(n, anchors, H, W, 4); }
 
 extern "C" int heal_unc_loss(const float* cls_preds, const float* reg_preds, const float* unc_preds, const float* dir_preds,
                              const void* pos_equal_one, const void* neg_equal_one, const void* targets, int labels_f64, int n,
@@ -291,38 +228,19 @@ extern "C" int heal_unc_loss(const float* cls_preds, const float* reg_preds, con
                              float angle_weight, float lambda_V, float s0, int limit_period, const double* anchor_yaw,
                              double dir_offset, float* terms, float* grad_cls, float* grad_reg, float* grad_unc, float* grad_dir,
                              void* ws, size_t ws_bytes, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    long long tiles_ll;
-    HEAL_REQUIRE(anchors >= 1 && anchors <= DL_MAX_A && dl_map_ok(n, 7 * anchors, H, W, &tiles_ll),
-                 "unc_loss: bad shape n=%d anchors=%d (1..%d) H=%d W=%d", n, anchors, DL_MAX_A, H, W);
+    HEAL_REQUIRE(dl_head_shape_ok(n, anchors, H, W), "unc_loss: bad shape n=%d anchors=%d (1..%d) H=%d W=%d", n, anchors, DL_MAX_A, H,
+                 W);
     HEAL_REQUIRE(heal_unc_loss_supported(anchors, dim, xy_type, angle_type, dir_preds != nullptr),
                  "unc_loss: dim=%d (2, 3, 7) xy_type=%d angle_type=%d anchors=%d%s is not supported", dim, xy_type, angle_type,
                  anchors, dir_preds ? " with a direction map (2 anchors)" : "");
-    HEAL_REQUIRE(cls_preds && reg_preds && unc_preds && pos_equal_one && neg_equal_one && targets && terms,
-                 "unc_loss: cls_preds, reg_preds, unc_preds, the three labels and terms must be set");
-    HEAL_REQUIRE(dir_preds == nullptr || anchor_yaw != nullptr, "unc_loss: dir_preds needs anchor_yaw[anchors]");
-    HEAL_REQUIRE(dir_preds != nullptr || grad_dir == nullptr, "unc_loss: grad_dir without dir_preds");
-    HEAL_REQUIRE(sigma > 0.f, "unc_loss: sigma must be positive, got %g", (double)sigma);
-    const size_t need = heal_unc_loss_workspace(n, anchors, H, W);
-    HEAL_REQUIRE(ws != nullptr && ws_bytes >= need, "unc_loss: workspace of %zu bytes, need %zu (heal_unc_loss_workspace)", ws_bytes,
-                 need);
-    Arena arena(ws, ws_bytes);
-    int* counts = arena.take<int>((size_t)n * DL_CB);
-    float* partials = arena.take<float>((size_t)4 * tiles_ll);
-    UncLaunch u;
-    u.HW = H * W;
-    u.tiles = ceil_div(u.HW, DL_TILE);
-    u.total = (int)tiles_ll;
-    DetParams& prm = u.prm.det;
-    prm.pos_cls_weight = pos_cls_weight;
-    prm.alpha = alpha;
-    prm.sigma2 = sigma * sigma;
-    prm.inv_sigma2 = 1.0f / (sigma * sigma);
-    prm.scale[0] = (float)((double)cls_weight / n);
-    prm.scale[1] = (float)((double)reg_weight / n);
-    prm.scale[2] = (float)((double)dir_weight / n);
-    for (int a = 0; a < DL_MAX_A; ++a) prm.yaw[a] = (anchor_yaw != nullptr && a < anchors) ? anchor_yaw[a] : 0.0;
-    prm.dir_offset = dir_offset;
+    UncLaunch u{{cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targets, grad_cls, grad_reg, grad_dir,
+                 (hipStream_t)stream}, unc_preds, grad_unc, dim};
+    if (dl_head_setup("unc_loss", "cls_preds, reg_preds, unc_preds",
+                      cls_preds && reg_preds && unc_preds && pos_equal_one && neg_equal_one && targets && terms, anchor_yaw, sigma, ws,
+                      ws_bytes, n, anchors, H, W, 4, u))
+        return 1;
+    const DetParams& prm = u.prm.det;
+    dl_det_params(u.prm.det, pos_cls_weight, alpha, sigma, cls_weight, reg_weight, dir_weight, n, anchor_yaw, anchors, dir_offset);
     u.prm.scale_unc = (float)((double)unc_weight / n);
     u.prm.angle_weight = angle_weight;
     u.prm.lambda_v = lambda_V;
@@ -330,32 +248,7 @@ extern "C" int heal_unc_loss(const float* cls_preds, const float* reg_preds, con
     u.prm.xy_l1 = xy_type == HEAL_UNC_L1;
     u.prm.angle_vm = angle_type == HEAL_UNC_VON_MISES;
     u.prm.limit_period = limit_period != 0;
-    u.cls = cls_preds; u.reg = reg_preds; u.unc = unc_preds; u.dir = dir_preds;
-    u.pos = pos_equal_one; u.neg = neg_equal_one; u.tgt = targets;
-    u.counts = counts;
-    u.gcls = grad_cls; u.greg = grad_reg; u.gunc = grad_unc; u.gdir = grad_dir;
-    u.partials = partials;
-    u.grid = dim3((unsigned)ceil_div(u.total, DL_WAVES));
-    u.s = s;
-    const long long per_sample = (long long)u.HW * anchors;
-    const dim3 block(256), cgrid(DL_CB, n);
-    const LaunchEvents ev = take_launch_events();
-    if (labels_f64) {
-        HEAL_LAUNCH_EV2(k_dl_count<double>, cgrid, block, 0, s, ev.start, nullptr, (const double*)pos_equal_one, per_sample, counts);
-        HEAL_LAUNCH_CHECK();
-        ul_launch_anchors<double>(u, anchors, dim);
-    } else {
-        HEAL_LAUNCH_EV2(k_dl_count<float>, cgrid, block, 0, s, ev.start, nullptr, (const float*)pos_equal_one, per_sample, counts);
-        HEAL_LAUNCH_CHECK();
-        ul_launch_anchors<float>(u, anchors, dim);
-    }
-    HEAL_LAUNCH_CHECK();
-    FinishScales sc;
-    sc.s[0] = (double)prm.scale[0];
-    sc.s[1] = (double)prm.scale[1];
-    sc.s[2] = (double)u.prm.scale_unc;
-    sc.s[3] = dir_preds != nullptr ? (double)prm.scale[2] : 0.0;
-    HEAL_LAUNCH_EV2(k_dl_finish, dim3(1), block, 0, s, nullptr, ev.stop, (const float*)partials, u.total, 4, sc, terms);
-    HEAL_LAUNCH_CHECK();
-    return 0;
+    const FinishScales sc{{(double)prm.scale[0], (double)prm.scale[1], (double)u.prm.scale_unc,
+                           dir_preds != nullptr ? (double)prm.scale[2] : 0.0}};
+    return dl_head_run(u, labels_f64, n, anchors, 4, sc, terms);
 }

@@ -2320,47 +2320,54 @@ def kd_kl_loss(student, teacher, need_grad=True, grad_out=None):
     distillation, mean over the N*C*H*W elements, and d loss / d student = (softmax(student) - softmax(teacher)) / (N*C*H*W).
     need_grad=False passes a NULL gradient: the kernel only reads.  grad_out: a contiguous f32 buffer of the student's shape to
     write the gradient into.  Two launches, no host synchronisation, no atomics (bit-equal from run to run)."""
-    for t, name in ((student, "student"), (teacher, "teacher")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _capi.HealAmdError(f"kd_kl_loss: {name} must be a CUDA/HIP tensor (heal_amd has no CPU path)")
-        if t.dtype != torch.float32:
-            raise _capi.HealAmdError(f"kd_kl_loss: {name} must have dtype torch.float32, got {t.dtype}")
-    if student.dim() != 4 or student.shape != teacher.shape or student.numel() == 0:
-        raise _capi.HealAmdError(f"kd_kl_loss: student {tuple(student.shape)} and teacher {tuple(teacher.shape)} must be equal, "
+    who = "kd_kl_loss"
+    (student, teacher), _ = _loss_inputs(who, (("student", student), ("teacher", teacher)), ())
+    if student.shape != teacher.shape:
+        raise _capi.HealAmdError(f"{who}: student {tuple(student.shape)} and teacher {tuple(teacher.shape)} must be equal, "
                                  "non-empty [N, C, H, W] maps")
-    student, teacher = student.detach().contiguous(), teacher.detach().contiguous()
     N, C, H, W = (int(v) for v in student.shape)
-    grad = None
-    if need_grad:
-        grad = grad_out if grad_out is not None else torch.empty_like(student)
-        if (not grad.is_cuda or grad.dtype != torch.float32 or grad.shape != student.shape or not grad.is_contiguous()):
-            raise _capi.HealAmdError("kd_kl_loss: grad_out must be a contiguous f32 CUDA tensor of the student's shape")
-    nbytes = _capi.query("heal_kd_kl_loss_workspace", N, C, H, W)
-    if nbytes == 0:
-        raise _capi.HealAmdError(f"kd_kl_loss: shape {(N, C, H, W)} is out of range")
-    ws = _workspace("kd_kl", nbytes, student.device)
-    loss = torch.empty(1, dtype=torch.float32, device=student.device)
+    (grad,) = _loss_grad_buffers(who, (student,), bool(need_grad), None if grad_out is None else (grad_out,))
+    nbytes, ws, loss = _loss_workspace(who, "kd_kl", "heal_kd_kl_loss_workspace", (N, C, H, W), f"shape {(N, C, H, W)} is", 1,
+                                       student.device)
     with _Timed(f"kd_kl_loss_c{C}", nbytes=4.0 * student.numel() * (3 if need_grad else 2)):
         _capi.call("heal_kd_kl_loss", _ptr(student), _ptr(teacher), N, C, H, W, _ptr(loss), _ptr(grad), _ptr(ws),
                    ctypes.c_size_t(nbytes), _stream())
     return loss, grad
 
 
-class KdKlLoss(torch.autograd.Function):
-    """kd_kl_loss under autograd: forward = heal_kd_kl_loss, which also writes d loss / d student (saved); backward scales it by
-    the incoming gradient.  The teacher receives none."""
+class _FusedLoss(torch.autograd.Function):
+    """The fused criteria under autograd.  run(need) is the raw operator with everything but need_grad bound: it runs the kernel,
+    which also writes d loss / d map for the maps that need one.  forward saves those; backward multiplies each by the incoming
+    gradient -- per_term: of the map's own term (det, center: out = terms [k], map i belongs to term i), otherwise of the one scalar
+    (kd, occ, depth: out = loss [1], returned 0-d).  Only `maps` are differentiable; labels and settings travel inside run.  An
+    operator whose maps share terms (unc) returns out = (total, terms): the terms ride along without a gradient."""
 
     @staticmethod
-    def forward(ctx, student, teacher):
-        loss, grad = kd_kl_loss(student, teacher, need_grad=ctx.needs_input_grad[0])
-        if grad is not None:
-            ctx.save_for_backward(grad)
-        return loss.reshape(())
+    def forward(ctx, run, per_term, need, *maps):
+        out, grads = run(need)
+        if not isinstance(grads, (tuple, list)):            # the one map's gradient (kd, depth), or None: no map needed one
+            grads = [grads] * len(maps)
+        ctx.per_term, ctx.have = per_term, tuple(g is not None for g in grads)
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        if isinstance(out, tuple):
+            ctx.mark_non_differentiable(*out[1:])
+            return out
+        return out if per_term else out.reshape(())
 
     @staticmethod
-    def backward(ctx, grad_out):
-        (grad,) = ctx.saved_tensors
-        return grad_out * grad, None
+    def backward(ctx, grad, *_):
+        saved = iter(ctx.saved_tensors)
+        return (None, None, None,
+                *[(grad[i] if ctx.per_term else grad) * next(saved) if have else None for i, have in enumerate(ctx.have)])
+
+
+class KdKlLoss:
+    """kd_kl_loss under autograd, KdKlLoss.apply(student, teacher) as the loss module calls it: -> the 0-d loss with the gradient
+    for the student; the teacher receives none."""
+
+    @staticmethod
+    def apply(student, teacher):
+        return _FusedLoss.apply(lambda need: kd_kl_loss(student, teacher, need_grad=need[0]), False, (_wants_grad(student),), student)
 
 
 # ------------------------------------------------------------------------------------------------ DL
@@ -2451,6 +2458,46 @@ def _loss_grad_buffers(who, maps, need_grad, grad_out):
     return grads
 
 
+def _loss_workspace(who, key, query, args, what, n_out, device, given=None):
+    """Workspace query (raises where it answers 0: `what` out of range), the operator's workspace `key` -- or `given`, a caller's
+    buffer, checked -- and the uninitialised f32 result [n_out].  -> (bytes, workspace, result)."""
+    nbytes = _capi.query(query, *args)
+    if nbytes == 0:
+        raise _capi.HealAmdError(f"{who}: {what} out of range")
+    if given is not None and not (given.is_cuda and given.dtype == torch.uint8 and given.is_contiguous() and given.numel() >= nbytes
+                                  and given.data_ptr() % 256 == 0):
+        raise _capi.HealAmdError(f"{who}: workspace must be a contiguous 256-B aligned uint8 CUDA tensor of >= {nbytes} bytes")
+    ws = given if given is not None else _workspace(key, nbytes, device)
+    return nbytes, ws, torch.empty(n_out, dtype=torch.float32, device=device)
+
+
+def _anchor_head_inputs(who, maps, labels, dim, anchor_yaw, weights, sigma, need_grad, grad_out):
+    """What det_loss and unc_loss do before their call.  maps: (name, tensor) of cls_preds, reg_preds, (unc_preds with dim set,)
+    dir_preds | None; labels: (name, tensor) of pos_equal_one, neg_equal_one, targets.  -> (checked contiguous maps, labels,
+    (N, A, H, W), the ctypes yaw array | NULL, grad buffers, bytes moved)."""
+    names = ", ".join(name[:-len("_preds")] for name, _ in maps)
+    maps, (pos, neg, tgt) = _loss_inputs(who, maps, labels)
+    N, A, H, W = (int(v) for v in maps[0].shape)
+    per_anchor = (1, 7, 2) if dim is None else (1, 7, dim, 2)
+    if A > LOSS_MAX_ANCHORS or any(m is not None and tuple(m.shape) != (N, c * A, H, W) for m, c in zip(maps, per_anchor)):
+        raise _capi.HealAmdError(f"{who}: maps {', '.join(str(tuple(m.shape)) for m in maps if m is not None)} are not [N, A, H, W], "
+                                 f"[N, 7A, H, W]{'' if dim is None else f', [N, {dim}A, H, W]'} (, [N, 2A, H, W]) with at most "
+                                 f"{LOSS_MAX_ANCHORS} anchors")
+    if pos.numel() != N * H * W * A or neg.numel() != N * H * W * A or tgt.numel() != 7 * N * H * W * A:
+        raise _capi.HealAmdError(f"{who}: labels of {pos.numel()}, {neg.numel()}, {tgt.numel()} elements for N*H*W*A = {N * H * W * A}")
+    yaw = ctypes.c_void_p(0)
+    if maps[-1] is not None:
+        if anchor_yaw is None or len(anchor_yaw) != A:
+            raise _capi.HealAmdError(f"{who}: dir_preds needs anchor_yaw with {A} angles (radians)")
+        yaw = ctypes.cast((ctypes.c_double * A)(*[float(v) for v in anchor_yaw]), ctypes.c_void_p)
+    if len(weights) != len(maps) or not float(sigma) > 0:
+        raise _capi.HealAmdError(f"{who}: weights must be ({names}) and sigma positive")
+    grads = _loss_grad_buffers(who, maps, need_grad, grad_out)
+    moved = sum(4.0 * m.numel() for m in maps if m is not None) + sum(4.0 * g.numel() for g in grads if g is not None) \
+        + float(pos.element_size()) * (2 * pos.numel() + tgt.numel())
+    return maps, (pos, neg, tgt), (N, A, H, W), yaw, grads, moved
+
+
 def det_loss(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targets, pos_cls_weight, alpha, sigma, weights,
              anchor_yaw=None, dir_offset=0.0, need_grad=True, grad_out=None):
     """DL.  PointPillarLoss's three terms and their gradients in one pass: cls_preds [N, A, H, W], reg_preds [N, 7A, H, W],
@@ -2459,39 +2506,16 @@ def det_loss(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targ
     direction bins.  -> (terms [3] = cls, reg, dir loss, each x weight / N, (grad_cls, grad_reg, grad_dir) | None).
     need_grad: bool or one per map; False passes NULL gradients: the kernels only read.  grad_out: buffers to write into."""
     who = "det_loss"
-    (cls_preds, reg_preds, dir_preds), (pos, neg, tgt) = _loss_inputs(
+    maps, (pos, neg, tgt), (N, A, H, W), yaw, grads, moved = _anchor_head_inputs(
         who, (("cls_preds", cls_preds), ("reg_preds", reg_preds), ("dir_preds", dir_preds)),
-        (("pos_equal_one", pos_equal_one), ("neg_equal_one", neg_equal_one), ("targets", targets)))
-    N, A, H, W = (int(v) for v in cls_preds.shape)
-    if (A > LOSS_MAX_ANCHORS or tuple(reg_preds.shape) != (N, 7 * A, H, W)
-            or (dir_preds is not None and tuple(dir_preds.shape) != (N, 2 * A, H, W))):
-        raise _capi.HealAmdError(f"{who}: maps {tuple(cls_preds.shape)}, {tuple(reg_preds.shape)}"
-                                 f"{'' if dir_preds is None else ', ' + str(tuple(dir_preds.shape))} are not [N, A, H, W], "
-                                 f"[N, 7A, H, W] (, [N, 2A, H, W]) with at most {LOSS_MAX_ANCHORS} anchors")
-    if pos.numel() != N * H * W * A or neg.numel() != N * H * W * A or tgt.numel() != 7 * N * H * W * A:
-        raise _capi.HealAmdError(f"{who}: labels of {pos.numel()}, {neg.numel()}, {tgt.numel()} elements for N*H*W*A = {N * H * W * A}")
-    yaw = None
-    if dir_preds is not None:
-        if anchor_yaw is None or len(anchor_yaw) != A:
-            raise _capi.HealAmdError(f"{who}: dir_preds needs anchor_yaw with {A} angles (radians)")
-        yaw = (ctypes.c_double * A)(*[float(v) for v in anchor_yaw])
-    if len(weights) != 3 or not float(sigma) > 0:
-        raise _capi.HealAmdError(f"{who}: weights must be (cls, reg, dir) and sigma positive")
-    maps = (cls_preds, reg_preds, dir_preds)
-    grads = _loss_grad_buffers(who, maps, need_grad, grad_out)
-    nbytes = _capi.query("heal_det_loss_workspace", N, A, H, W)
-    if nbytes == 0:
-        raise _capi.HealAmdError(f"{who}: shape {(N, A, H, W)} is out of range")
-    ws = _workspace("det_loss", nbytes, cls_preds.device)
-    terms = torch.empty(3, dtype=torch.float32, device=cls_preds.device)
-    moved = sum(4.0 * m.numel() for m in maps if m is not None) + sum(4.0 * g.numel() for g in grads if g is not None) \
-        + float(pos.element_size()) * (2 * pos.numel() + tgt.numel())
+        (("pos_equal_one", pos_equal_one), ("neg_equal_one", neg_equal_one), ("targets", targets)), None, anchor_yaw, weights, sigma,
+        need_grad, grad_out)
+    nbytes, ws, terms = _loss_workspace(who, "det_loss", "heal_det_loss_workspace", (N, A, H, W), f"shape {(N, A, H, W)} is", 3,
+                                        maps[0].device)
     with _Timed(f"det_loss_a{A}", nbytes=moved):
-        _capi.call("heal_det_loss", _ptr(cls_preds), _ptr(reg_preds), _ptr(dir_preds), _ptr(pos), _ptr(neg), _ptr(tgt),
-                   int(pos.dtype == torch.float64), N, A, H, W, float(pos_cls_weight), float(alpha), float(sigma),
-                   float(weights[0]), float(weights[1]), float(weights[2]),
-                   ctypes.cast(yaw, ctypes.c_void_p) if yaw is not None else ctypes.c_void_p(0), float(dir_offset), _ptr(terms),
-                   _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(ws), ctypes.c_size_t(nbytes), _stream())
+        _capi.call("heal_det_loss", *(_ptr(m) for m in maps), _ptr(pos), _ptr(neg), _ptr(tgt), int(pos.dtype == torch.float64),
+                   N, A, H, W, float(pos_cls_weight), float(alpha), float(sigma), *(float(w) for w in weights), yaw,
+                   float(dir_offset), _ptr(terms), *(_ptr(g) for g in grads), _ptr(ws), ctypes.c_size_t(nbytes), _stream())
     return terms, (tuple(grads) if any(g is not None for g in grads) else None)
 
 
@@ -2499,29 +2523,15 @@ def _wants_grad(t):
     return bool(t is not None and t.requires_grad and torch.is_grad_enabled())
 
 
-class DetLoss(torch.autograd.Function):
-    """det_loss under autograd: forward = heal_det_loss, which also writes d term / d map (saved); backward scales each by the
-    incoming gradient of its term.  Labels receive none."""
-
-    @staticmethod
-    def forward(ctx, cls_preds, reg_preds, dir_preds, pos, neg, targets, cfg, need):
-        terms, grads = det_loss(cls_preds, reg_preds, dir_preds, pos, neg, targets, need_grad=need, **cfg)
-        grads = grads if grads is not None else (None, None, None)
-        ctx.have = tuple(g is not None for g in grads)
-        ctx.save_for_backward(*[g for g in grads if g is not None])
-        return terms
-
-    @staticmethod
-    def backward(ctx, grad_terms):
-        saved = list(ctx.saved_tensors)
-        out = [grad_terms[i] * saved.pop(0) if have else None for i, have in enumerate(ctx.have)]
-        return (*out, None, None, None, None, None)
+def _loss_terms(op, per_term, maps, *rest, **cfg):
+    """op(*maps, *rest, **cfg) under autograd (_FusedLoss), with a gradient for each of `maps` that requires one."""
+    return _FusedLoss.apply(lambda need: op(*maps, *rest, need_grad=need, **cfg), per_term, tuple(_wants_grad(t) for t in maps),
+                            *maps)
 
 
 def det_loss_terms(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targets, **cfg):
     """The differentiable form of det_loss: -> terms [3] (cls, reg, dir), gradients for the maps that require one."""
-    need = tuple(_wants_grad(t) for t in (cls_preds, reg_preds, dir_preds))
-    return DetLoss.apply(cls_preds, reg_preds, dir_preds, pos_equal_one, neg_equal_one, targets, cfg, need)
+    return _loss_terms(det_loss, True, (cls_preds, reg_preds, dir_preds), pos_equal_one, neg_equal_one, targets, **cfg)
 
 
 _UNC_XY = {"l2": 0, "l1": 1}              # HEAL_UNC_L2 / HEAL_UNC_L1 of include/heal_amd_unc.h
@@ -2554,73 +2564,37 @@ def unc_loss(cls_preds, reg_preds, unc_preds, dir_preds, pos_equal_one, neg_equa
     (grad_cls, grad_reg, grad_unc, grad_dir) | None); grad_reg carries the reg term's and the unc term's gradient.
     need_grad: bool or one per map; False passes NULL gradients: the kernels only read.  grad_out: buffers to write into."""
     who = "unc_loss"
-    (cls_preds, reg_preds, unc_preds, dir_preds), (pos, neg, tgt) = _loss_inputs(
+    dim = int(dim)
+    maps, (pos, neg, tgt), (N, A, H, W), yaw, grads, moved = _anchor_head_inputs(
         who, (("cls_preds", cls_preds), ("reg_preds", reg_preds), ("unc_preds", unc_preds), ("dir_preds", dir_preds)),
-        (("pos_equal_one", pos_equal_one), ("neg_equal_one", neg_equal_one), ("targets", targets)))
-    N, A, H, W = (int(v) for v in cls_preds.shape)
+        (("pos_equal_one", pos_equal_one), ("neg_equal_one", neg_equal_one), ("targets", targets)), dim, anchor_yaw, weights, sigma,
+        need_grad, grad_out)
     if xy_loss_type not in _UNC_XY or angle_loss_type not in _UNC_ANGLE:
         raise _capi.HealAmdError(f"{who}: xy_loss_type {xy_loss_type!r} (l2 | l1), angle_loss_type {angle_loss_type!r} (l2 | von-mise)")
-    dim = int(dim)
-    if (A > LOSS_MAX_ANCHORS or tuple(reg_preds.shape) != (N, 7 * A, H, W) or tuple(unc_preds.shape) != (N, dim * A, H, W)
-            or (dir_preds is not None and tuple(dir_preds.shape) != (N, 2 * A, H, W))):
-        raise _capi.HealAmdError(f"{who}: maps {tuple(cls_preds.shape)}, {tuple(reg_preds.shape)}, {tuple(unc_preds.shape)}"
-                                 f"{'' if dir_preds is None else ', ' + str(tuple(dir_preds.shape))} are not [N, A, H, W], "
-                                 f"[N, 7A, H, W], [N, {dim}A, H, W] (, [N, 2A, H, W]) with at most {LOSS_MAX_ANCHORS} anchors")
-    if pos.numel() != N * H * W * A or neg.numel() != N * H * W * A or tgt.numel() != 7 * N * H * W * A:
-        raise _capi.HealAmdError(f"{who}: labels of {pos.numel()}, {neg.numel()}, {tgt.numel()} elements for N*H*W*A = {N * H * W * A}")
-    yaw = None
-    if dir_preds is not None:
-        if anchor_yaw is None or len(anchor_yaw) != A:
-            raise _capi.HealAmdError(f"{who}: dir_preds needs anchor_yaw with {A} angles (radians)")
-        yaw = (ctypes.c_double * A)(*[float(v) for v in anchor_yaw])
-    if len(weights) != 4 or not float(sigma) > 0:
-        raise _capi.HealAmdError(f"{who}: weights must be (cls, reg, unc, dir) and sigma positive")
-    maps = (cls_preds, reg_preds, unc_preds, dir_preds)
-    grads = _loss_grad_buffers(who, maps, need_grad, grad_out)
-    nbytes = _capi.query("heal_unc_loss_workspace", N, A, H, W)
-    if nbytes == 0:
-        raise _capi.HealAmdError(f"{who}: shape {(N, A, H, W)} is out of range")
-    ws = _workspace("unc_loss", nbytes, cls_preds.device)
-    terms = torch.empty(4, dtype=torch.float32, device=cls_preds.device)
-    moved = sum(4.0 * m.numel() for m in maps if m is not None) + sum(4.0 * g.numel() for g in grads if g is not None) \
-        + float(pos.element_size()) * (2 * pos.numel() + tgt.numel())
+    nbytes, ws, terms = _loss_workspace(who, "unc_loss", "heal_unc_loss_workspace", (N, A, H, W), f"shape {(N, A, H, W)} is", 4,
+                                        maps[0].device)
     with _Timed(f"unc_loss_a{A}_d{dim}", nbytes=moved):
-        _capi.call("heal_unc_loss", _ptr(cls_preds), _ptr(reg_preds), _ptr(unc_preds), _ptr(dir_preds), _ptr(pos), _ptr(neg),
-                   _ptr(tgt), int(pos.dtype == torch.float64), N, A, H, W, dim, float(pos_cls_weight), float(alpha), float(sigma),
-                   float(weights[0]), float(weights[1]), float(weights[2]), float(weights[3]), _UNC_XY[xy_loss_type],
-                   _UNC_ANGLE[angle_loss_type], float(angle_weight), float(lambda_V), float(s0), int(bool(limit_period)),
-                   ctypes.cast(yaw, ctypes.c_void_p) if yaw is not None else ctypes.c_void_p(0), float(dir_offset), _ptr(terms),
-                   _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(ws), ctypes.c_size_t(nbytes), _stream())
+        _capi.call("heal_unc_loss", *(_ptr(m) for m in maps), _ptr(pos), _ptr(neg), _ptr(tgt), int(pos.dtype == torch.float64),
+                   N, A, H, W, dim, float(pos_cls_weight), float(alpha), float(sigma), *(float(w) for w in weights),
+                   _UNC_XY[xy_loss_type], _UNC_ANGLE[angle_loss_type], float(angle_weight), float(lambda_V), float(s0),
+                   int(bool(limit_period)), yaw, float(dir_offset), _ptr(terms), *(_ptr(g) for g in grads), _ptr(ws),
+                   ctypes.c_size_t(nbytes), _stream())
     return terms, (tuple(grads) if any(g is not None for g in grads) else None)
 
 
-class UncLoss(torch.autograd.Function):
-    """unc_loss under autograd.  grad_reg is the sum of two terms' gradients (reg and unc), so the differentiable output is the
-    TOTAL, added in the loss module's order (dir + ((reg + cls) + unc)); the four terms come along for the bookkeeping and carry
-    no gradient.  The forward writes d total / d map (saved); backward scales each by the incoming gradient."""
-
-    @staticmethod
-    def forward(ctx, cls_preds, reg_preds, unc_preds, dir_preds, pos, neg, targets, cfg, need):
-        terms, grads = unc_loss(cls_preds, reg_preds, unc_preds, dir_preds, pos, neg, targets, need_grad=need, **cfg)
-        grads = grads if grads is not None else (None, None, None, None)
-        ctx.have = tuple(g is not None for g in grads)
-        ctx.save_for_backward(*[g for g in grads if g is not None])
-        ctx.mark_non_differentiable(terms)
-        total = (terms[1] + terms[0]) + terms[2]
-        return (terms[3] + total if dir_preds is not None else total), terms
-
-    @staticmethod
-    def backward(ctx, grad_total, _):
-        saved = list(ctx.saved_tensors)
-        out = [grad_total * saved.pop(0) if have else None for have in ctx.have]
-        return (*out, None, None, None, None, None)
+def _unc_loss_total(*args, **cfg):
+    """unc_loss for _FusedLoss: grad_reg is the sum of two terms' gradients (reg and unc), so the differentiable output is the
+    TOTAL, added in the loss module's order (dir + ((reg + cls) + unc)); the four terms come along for the bookkeeping."""
+    terms, grads = unc_loss(*args, **cfg)
+    total = (terms[1] + terms[0]) + terms[2]
+    return ((terms[3] + total if args[3] is not None else total), terms), grads
 
 
 def unc_loss_terms(cls_preds, reg_preds, unc_preds, dir_preds, pos_equal_one, neg_equal_one, targets, **cfg):
     """The differentiable form of unc_loss: -> (total, terms [4] = cls, reg, unc, dir); the total carries the gradients for the
     maps that require one, the terms are detached."""
-    need = tuple(_wants_grad(t) for t in (cls_preds, reg_preds, unc_preds, dir_preds))
-    return UncLoss.apply(cls_preds, reg_preds, unc_preds, dir_preds, pos_equal_one, neg_equal_one, targets, cfg, need)
+    return _loss_terms(_unc_loss_total, False, (cls_preds, reg_preds, unc_preds, dir_preds), pos_equal_one, neg_equal_one, targets,
+                       **cfg)
 
 
 def occ_loss_supported(occ_list, pos_equal_one, neg_equal_one, relative_downsample, gamma=2.0):
@@ -2669,11 +2643,8 @@ def occ_loss(occ_list, pos_equal_one, neg_equal_one, relative_downsample, level_
     w_arr = (ctypes.c_float * L)(*[float(v) for v in level_weight[:L]])
     o_arr = (ctypes.c_void_p * L)(*[o.data_ptr() for o in occ])
     g_arr = (ctypes.c_void_p * L)(*[g.data_ptr() if g is not None else None for g in grads])
-    nbytes = _capi.query("heal_occ_loss_workspace", N, H, W, L, ctypes.cast(k_arr, ctypes.c_void_p))
-    if nbytes == 0:
-        raise _capi.HealAmdError(f"{who}: labels {(N, H, W, A)} with levels {ks} are out of range")
-    ws = _workspace("occ_loss", nbytes, pos.device)
-    loss = torch.empty(1, dtype=torch.float32, device=pos.device)
+    nbytes, ws, loss = _loss_workspace(who, "occ_loss", "heal_occ_loss_workspace", (N, H, W, L, ctypes.cast(k_arr, ctypes.c_void_p)),
+                                       f"labels {(N, H, W, A)} with levels {ks} are", 1, pos.device)
     moved = sum(4.0 * o.numel() for o in occ) + sum(4.0 * g.numel() for g in grads if g is not None) \
         + float(pos.element_size()) * 2 * pos.numel() * (L + 1)
     with _Timed(f"occ_loss_l{L}", nbytes=moved):
@@ -2683,26 +2654,10 @@ def occ_loss(occ_list, pos_equal_one, neg_equal_one, relative_downsample, level_
     return loss, (grads if any(g is not None for g in grads) else None)
 
 
-class OccLoss(torch.autograd.Function):
-    """occ_loss under autograd; the per-level gradients written by the forward are saved and scaled in backward."""
-
-    @staticmethod
-    def forward(ctx, pos, neg, cfg, need, *occ_list):
-        loss, grads = occ_loss(list(occ_list), pos, neg, need_grad=need, **cfg)
-        grads = grads if grads is not None else [None] * len(occ_list)
-        ctx.have = tuple(g is not None for g in grads)
-        ctx.save_for_backward(*[g for g in grads if g is not None])
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        saved = list(ctx.saved_tensors)
-        return (None, None, None, None, *[grad_out * saved.pop(0) if have else None for have in ctx.have])
-
-
 def occ_loss_term(occ_list, pos_equal_one, neg_equal_one, **cfg):
-    need = tuple(_wants_grad(o) for o in occ_list)
-    return OccLoss.apply(pos_equal_one, neg_equal_one, cfg, need, *occ_list)
+    """occ_loss under autograd: -> the 0-d loss, gradients for the levels that require one."""
+    return _FusedLoss.apply(lambda need: occ_loss(list(occ_list), pos_equal_one, neg_equal_one, need_grad=need, **cfg), False,
+                            tuple(_wants_grad(o) for o in occ_list), *occ_list)
 
 
 def depth_focal_loss_supported(depth_logit, depth_gt_indices, fg_mask=None, gamma=2.0, smooth_target=False):
@@ -2739,11 +2694,8 @@ def depth_focal_loss(depth_logit, depth_gt_indices, fg_mask=None, alpha=0.25, we
     idx = depth_gt_indices.contiguous()
     mask = fg_mask.detach().contiguous() if fg_mask is not None else None
     (grad,) = _loss_grad_buffers(who, (depth_logit,), bool(need_grad), None if grad_out is None else (grad_out,))
-    nbytes = _capi.query("heal_depth_focal_loss_workspace", M, D, h, w)
-    if nbytes == 0:
-        raise _capi.HealAmdError(f"{who}: shape {(M, D, h, w)} is out of range")
-    ws = _workspace("depth_focal_loss", nbytes, dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    nbytes, ws, loss = _loss_workspace(who, "depth_focal_loss", "heal_depth_focal_loss_workspace", (M, D, h, w),
+                                       f"shape {(M, D, h, w)} is", 1, dev)
     moved = 4.0 * depth_logit.numel() * (2 if grad is not None else 1) + 8.0 * idx.numel() + (4.0 * idx.numel() if mask is not None else 0)
     with _Timed(f"depth_focal_loss_d{D}", nbytes=moved):
         _capi.call("heal_depth_focal_loss", _ptr(depth_logit), _ptr(idx), _ptr(mask), M, D, h, w, float(alpha), float(weight),
@@ -2751,24 +2703,10 @@ def depth_focal_loss(depth_logit, depth_gt_indices, fg_mask=None, alpha=0.25, we
     return loss, grad
 
 
-class DepthFocalLoss(torch.autograd.Function):
-    """depth_focal_loss under autograd; the indices and the mask receive no gradient."""
-
-    @staticmethod
-    def forward(ctx, depth_logit, depth_gt_indices, fg_mask, alpha, weight, need):
-        loss, grad = depth_focal_loss(depth_logit, depth_gt_indices, fg_mask, alpha, weight, need_grad=need)
-        ctx.have = grad is not None
-        if grad is not None:
-            ctx.save_for_backward(grad)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        return (grad_out * ctx.saved_tensors[0] if ctx.have else None, None, None, None, None, None)
-
-
 def depth_focal_loss_term(depth_logit, depth_gt_indices, fg_mask=None, alpha=0.25, weight=1.0):
-    return DepthFocalLoss.apply(depth_logit, depth_gt_indices, fg_mask, alpha, weight, _wants_grad(depth_logit))
+    """depth_focal_loss under autograd: -> the 0-d loss; the indices and the mask receive no gradient."""
+    return _FusedLoss.apply(lambda need: depth_focal_loss(depth_logit, depth_gt_indices, fg_mask, alpha, weight, need_grad=need[0]),
+                            False, (_wants_grad(depth_logit),), depth_logit)
 
 
 # ------------------------------------------------------------------------------------------------ CP
@@ -2844,15 +2782,8 @@ def center_loss(cls_preds, bbox_preds, object_bbx_center, object_bbx_mask, cav_l
         raise _capi.HealAmdError(f"{who}: maps {(B, H, W)} with max_objs {max_objs} (<= {CENTER_MAX_OBJS}) are out of range, or "
                                  "(H, W) is not the feature map of cav_lidar_range / voxel_size / out_size_factor")
     grads = _loss_grad_buffers(who, (cls_preds, bbox_preds), need_grad, grad_out)
-    nbytes = _capi.query("heal_center_loss_workspace", B, H, W, max_objs)
-    if workspace is not None:
-        if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= nbytes
-                and workspace.data_ptr() % 256 == 0):
-            raise _capi.HealAmdError(f"{who}: workspace must be a contiguous 256-B aligned uint8 CUDA tensor of >= {nbytes} bytes")
-        ws = workspace
-    else:
-        ws = _workspace("center_loss", nbytes, dev)
-    terms = torch.empty(2, dtype=torch.float32, device=dev)
+    nbytes, ws, terms = _loss_workspace(who, "center_loss", "heal_center_loss_workspace", (B, H, W, max_objs),
+                                        f"maps {(B, H, W)} with max_objs {max_objs} are", 2, dev, given=workspace)
     dbg = None
     if debug:
         dbg = {"heatmap": torch.empty((B, 1, H, W), dtype=torch.float32, device=dev),
@@ -2871,29 +2802,10 @@ def center_loss(cls_preds, bbox_preds, object_bbx_center, object_bbx_mask, cav_l
     return (terms, grads, dbg) if debug else (terms, grads)
 
 
-class CenterLoss(torch.autograd.Function):
-    """center_loss under autograd: forward = heal_center_loss, which also writes d term / d map (saved); backward scales each by
-    the incoming gradient of its term.  The boxes and the mask receive none."""
-
-    @staticmethod
-    def forward(ctx, cls_preds, bbox_preds, boxes, mask, cfg, need):
-        terms, grads = center_loss(cls_preds, bbox_preds, boxes, mask, need_grad=need, **cfg)
-        grads = grads if grads is not None else (None, None)
-        ctx.have = tuple(g is not None for g in grads)
-        ctx.save_for_backward(*[g for g in grads if g is not None])
-        return terms
-
-    @staticmethod
-    def backward(ctx, grad_terms):
-        saved = list(ctx.saved_tensors)
-        out = [grad_terms[i] * saved.pop(0) if have else None for i, have in enumerate(ctx.have)]
-        return (*out, None, None, None, None)
-
-
 def center_loss_terms(cls_preds, bbox_preds, object_bbx_center, object_bbx_mask, **cfg):
-    """The differentiable form of center_loss: -> terms [2] (cls, reg), gradients for the maps that require one."""
-    need = tuple(_wants_grad(t) for t in (cls_preds, bbox_preds))
-    return CenterLoss.apply(cls_preds, bbox_preds, object_bbx_center, object_bbx_mask, cfg, need)
+    """The differentiable form of center_loss: -> terms [2] (cls, reg), gradients for the maps that require one; the boxes and the
+    mask receive none."""
+    return _loss_terms(center_loss, True, (cls_preds, bbox_preds), object_bbx_center, object_bbx_mask, **cfg)
 
 
 def center_boxes(bbox_preds, cav_lidar_range, voxel_size, out_size_factor):
