@@ -415,8 +415,10 @@ __global__ __launch_bounds__(1024) void k_split_weights(const float* __restrict_
 using namespace heal;
 
 extern "C" int heal_ln_stats(const float* x, int n_tokens, int channels, float eps, float* stats, void* stream) {
-    HEAL_REQUIRE(channels % 4 == 0 && channels <= 512, "ln_stats: channels must be a multiple of 4, <= 512");
+    HEAL_REQUIRE(channels >= 4 && channels % 4 == 0 && channels <= 512, "ln_stats: channels must be a multiple of 4 in [4, 512]");
     if (n_tokens <= 0) return 0;
+    HEAL_REQUIRE(x && stats, "ln_stats: null x or stats");
+    HEAL_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)stats & 7) == 0, "ln_stats: x must be 16-B aligned, stats 8-B aligned");
     if (channels == 256)
         k_ln_stats256<<<ceil_div(n_tokens, 16), 256, 0, (hipStream_t)stream>>>(x, n_tokens, eps, reinterpret_cast<float2*>(stats));
     else
@@ -444,8 +446,20 @@ extern "C" int heal_linear(const float* x, int lda, int x_part_cols, long long x
     HEAL_REQUIRE(act >= 0 && act <= 2, "linear: act in {0,1,2}");
     if (n_tokens <= 0) return 0;
     LinearArgs a;
-    HEAL_REQUIRE(x_part_cols == 0 || (x_part_cols % LIN_BK == 0 && n_in % x_part_cols == 0 && !ln_stats),
+    HEAL_REQUIRE(x_part_cols == 0 || (x_part_cols > 0 && x_part_cols % LIN_BK == 0 && n_in % x_part_cols == 0 && !ln_stats),
                  "linear: x parts must be whole 32-channel chunks (and carry no LayerNorm)");
+    // everything below reaches the kernel as an address: the tiles move as float4, the statistics as float2, and a row stride
+    // below the row's width (or a negative one, widened to size_t) would send rows on top of each other or out of the tensor
+    HEAL_REQUIRE(x && weight && out, "linear: null x, weight or out");
+    HEAL_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)residual & 15) == 0 && ((uintptr_t)bias & 15) == 0 &&
+                     ((uintptr_t)ln_stats & 7) == 0,
+                 "linear: out, residual and bias must be 16-B aligned, ln_stats 8-B aligned");
+    HEAL_REQUIRE(x_part_cols == 0 || x_part_stride % 4 == 0, "linear: x_part_stride must be a multiple of 4 floats");
+    HEAL_REQUIRE(part_cols <= 0 || part_cols >= n_out || part_stride % 4 == 0, "linear: part_stride must be a multiple of 4 floats");
+    HEAL_REQUIRE(lda >= (x_part_cols > 0 ? x_part_cols : n_in), "linear: lda below the width of an x row");
+    HEAL_REQUIRE(ldo >= (part_cols > 0 && part_cols < n_out ? part_cols : n_out), "linear: ldo below the width of an output row");
+    HEAL_REQUIRE(!residual || ldr >= n_out, "linear: ldr below the width of a residual row");
+    HEAL_REQUIRE(group_rows >= 0, "linear: group_rows must not be negative");
     a.a_part_cols = x_part_cols; a.a_part_stride = x_part_stride;
     a.X = x; a.lda = lda; a.stats = reinterpret_cast<const float2*>(ln_stats); a.W = weight; a.bias = bias;
     a.colscale = colscale; a.res = residual; a.ldr = ldr; a.out = out; a.ldo = ldo; a.T = n_tokens; a.N = n_out; a.K = n_in;
@@ -464,7 +478,9 @@ extern "C" size_t heal_split_attn_workspace(int groups, int rows_per_group, int 
 
 static int split_attn_colsum(const float* branches, long long part_stride, int groups, int rows_per_group, int channels,
                             float* colsum, hipStream_t s) {
-    HEAL_REQUIRE(channels <= 256 && channels % 64 == 0, "split_attn_weights: channels must be 64, 128, 192 or 256");
+    HEAL_REQUIRE(channels >= 64 && channels <= 256 && channels % 64 == 0, "split_attn_weights: channels must be 64, 128, 192 or 256");
+    HEAL_REQUIRE(groups >= 1 && groups <= 65535 && rows_per_group >= 1, "split_attn_weights: groups in [1, 65535], rows_per_group >= 1");
+    HEAL_REQUIRE(branches && colsum, "split_attn_weights: null branches or column-sum buffer");
     HEAL_REQUIRE(part_stride % 4 == 0 && ((uintptr_t)branches & 15) == 0 && ((uintptr_t)colsum & 15) == 0,
                  "split_attn_weights: 16-B alignment");
     const int chunk = 512, chunks = ceil_div(rows_per_group, chunk);
@@ -483,8 +499,11 @@ extern "C" int heal_split_attn_weights_from_colsum(const float* colsum, int n_pa
                                                    const float* w_out, const float* b_out, const float* fc1,
                                                    const float* ln_gamma, const float* ln_beta, float eps, const float* fc2,
                                                    float* scale, float* bias, void* stream) {
-    HEAL_REQUIRE(channels <= 256 && channels % 64 == 0, "split_attn_weights: channels must be 64, 128, 192 or 256");
-    HEAL_REQUIRE(n_parts >= 1 && rows_per_part >= 1, "split_attn_weights: n_parts, rows_per_part >= 1");
+    HEAL_REQUIRE(channels >= 64 && channels <= 256 && channels % 64 == 0, "split_attn_weights: channels must be 64, 128, 192 or 256");
+    HEAL_REQUIRE(n_parts >= 1 && rows_per_part >= 1 && groups >= 1, "split_attn_weights: n_parts, groups, rows_per_part >= 1");
+    HEAL_REQUIRE(colsum && w_out && b_out && fc1 && ln_gamma && ln_beta && fc2 && scale && bias, "split_attn_weights: null operand");
+    HEAL_REQUIRE(((uintptr_t)w_out & 15) == 0 && ((uintptr_t)fc1 & 15) == 0 && ((uintptr_t)fc2 & 15) == 0,
+                 "split_attn_weights: w_out, fc1 and fc2 must be 16-B aligned");
     const int chunks = ceil_div(rows_per_part, 512);
     k_split_weights<<<groups, 1024, 0, (hipStream_t)stream>>>(colsum, chunks, n_parts, 1.0f / ((float)rows_per_part * (float)n_parts),
                                                             w_out, b_out, fc1, ln_gamma, ln_beta, eps, fc2, channels, scale, bias);
@@ -496,6 +515,10 @@ extern "C" int heal_split_attn_weights(const float* branches, long long part_str
                                        int channels, const float* w_out, const float* b_out, const float* fc1,
                                        const float* ln_gamma, const float* ln_beta, float eps, const float* fc2,
                                        float* colsum_ws, float* scale, float* bias, void* stream) {
+    // the second half's operands are checked BEFORE the first half is launched: a refused call leaves the device untouched
+    HEAL_REQUIRE(w_out && b_out && fc1 && ln_gamma && ln_beta && fc2 && scale && bias, "split_attn_weights: null operand");
+    HEAL_REQUIRE(((uintptr_t)w_out & 15) == 0 && ((uintptr_t)fc1 & 15) == 0 && ((uintptr_t)fc2 & 15) == 0,
+                 "split_attn_weights: w_out, fc1 and fc2 must be 16-B aligned");
     if (int rc = split_attn_colsum(branches, part_stride, groups, rows_per_group, channels, colsum_ws, (hipStream_t)stream)) return rc;
     return heal_split_attn_weights_from_colsum(colsum_ws, 1, groups, rows_per_group, channels, w_out, b_out, fc1, ln_gamma, ln_beta,
                                                eps, fc2, scale, bias, stream);

@@ -881,10 +881,15 @@ int heal_gru_zero_state(const float* gates, long long gates_stride, const float*
  *   the per-agent softmax weights as one K = 3 C GEMM); residual (or NULL) rows ldr apart, indexed like the output; act 0 none,
  *   1 GELU (erf), 2 ReLU (applied before the residual).  Output addressing: token t goes to row (t % map_inner) * map_outer +
  *   t / map_inner (map_inner = 0: row t), column c to out + (c / part_cols) * part_stride + row * ldo + c % part_cols.
- *   n_out multiple of 128, n_in multiple of 32, group_rows multiple of 128.
+ *   n_out multiple of 128, n_in multiple of 32, group_rows multiple of 128.  x, weight, bias, residual and out are 16-B aligned
+ *   and lda, ldo, ldr, part_cols, part_stride, x_part_stride multiples of 4 floats (the tiles move as 16-B pieces); a row stride
+ *   is at least the width of its row.  Every violation is an error before anything is launched.
  * heal_split_attn_weights: branches = the three window-attention outputs [3][groups * rows_per_group, channels] (part_stride
  *   floats apart), BEFORE their to_out projections w_out [3, C, C] / b_out [3, C]; -> scale [groups, 3, C] (softmax over the
- *   three branches of fc2(relu(LN(fc1(global average of the projected sum))))) and bias [groups, C] = sum scale * b_out.     */
+ *   three branches of fc2(relu(LN(fc1(global average of the projected sum))))) and bias [groups, C] = sum scale * b_out.
+ *   channels 64, 128, 192 or 256; 1 <= groups <= 65535; rows_per_group >= 1; branches, colsum, w_out, fc1 and fc2 16-B aligned,
+ *   part_stride a multiple of 4 floats; no operand may be NULL.  heal_ln_stats: channels a multiple of 4 in [4, 512], x 16-B
+ *   aligned.  As for heal_linear, a violated requirement is an error before anything is launched.                          */
 int heal_ln_stats(const float* x, int n_tokens, int channels, float eps, float* stats, void* stream);
 int heal_linear(const float* x, int lda, int x_part_cols, long long x_part_stride, const float* ln_stats,
                 const float* weight, const float* bias,
