@@ -47,39 +47,9 @@ struct DiscoParams {
     const float *b2, *w3, *b3, *w4, *b4;      // [32], [8, 32], [8], [8], [1]
     float* out;             // [C, H, W]
     float* scores;          // [n, H, W] post-ReLU logits, or null
-    const double* mdev;     // device copy of the affine rows (wins over `m` when non-null)
-    double m[WF_MAXA][6];
-    int C, H, W, grid_f64;
+    AffineRows rows;
+    int C, H, W;
 };
-
-__device__ __forceinline__ void disco_taps(const DiscoParams& P, int a, int h, int w, bool live, int (&off)[4], float (&wt)[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { off[k] = 0; wt[k] = 0.f; }
-    if (!live) return;
-    float gx, gy;
-    double m[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) m[k] = P.mdev ? P.mdev[a * 6 + k] : P.m[a][k];   // wave-uniform
-    if (P.grid_f64) grid_point<double>(m, h, w, P.H, P.W, gx, gy);
-    else grid_point<float>(m, h, w, P.H, P.W, gx, gy);
-    const Taps t = make_taps(gx, gy, P.H, P.W);
-    const int o4[4] = {t.off, t.off + 1, t.off + P.W, t.off + P.W + 1};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const bool ok = (t.ok >> k) & 1u;    // a tap outside the image: weight 0 on a valid address
-        off[k] = ok ? o4[k] : 0;
-        wt[k] = ok ? t.w[k] : 0.f;
-    }
-}
-
-__device__ __forceinline__ float disco_tap4(const float* __restrict__ src, const int (&off)[4], const float (&wt)[4]) {
-    // sample(): nw, ne, sw, se accumulated in that order
-    float v = src[off[0]] * wt[0];
-    v += src[off[1]] * wt[1];
-    v += src[off[2]] * wt[2];
-    v += src[off[3]] * wt[3];
-    return v;
-}
 
 template <int NA>
 __global__ __launch_bounds__(256, 2) void k_disco_fuse(const DiscoParams P) {
@@ -107,7 +77,7 @@ __global__ __launch_bounds__(256, 2) void k_disco_fuse(const DiscoParams P) {
             asm volatile("" : "+s"(e0p), "+s"(w2p));
             int off[4];
             float wt[4];
-            disco_taps(P, a, h, w, live, off, wt);
+            pixel_taps(P.rows, a, h, w, P.H, P.W, live, off, wt);
             // the four waves hold the same 64 pixels: the test is block-uniform, the barriers inside are met by every wave
             const bool any = __ballot((wt[0] != 0.f) | (wt[1] != 0.f) | (wt[2] != 0.f) | (wt[3] != 0.f)) != 0ull;
             f32x4 acc[2][4];
@@ -248,21 +218,16 @@ __global__ __launch_bounds__(256, 2) void k_disco_fuse(const DiscoParams P) {
     if (NA == 1) {
         prob[0] = 1.f;      // the softmax of one logit
     } else {
-        float mx = -INFINITY;
 #pragma unroll
-        for (int a = 0; a < NA; ++a) { prob[a] = s_logit[a][l]; mx = fmaxf(mx, prob[a]); }
-        float den = 0.f;
-#pragma unroll
-        for (int a = 0; a < NA; ++a) { prob[a] = expf(prob[a] - mx); den += prob[a]; }
-#pragma unroll
-        for (int a = 0; a < NA; ++a) prob[a] = prob[a] / den;
+        for (int a = 0; a < NA; ++a) prob[a] = s_logit[a][l];
+        softmax_agents(prob);
     }
     int off[NA][4];
     float wt[NA][4];
     unsigned reach = 0;      // bit a: some lane of this wave samples agent a inside its map
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
-        disco_taps(P, a, h, w, live, off[a], wt[a]);
+        pixel_taps(P.rows, a, h, w, P.H, P.W, live, off[a], wt[a]);
         const bool any = (wt[a][0] != 0.f) | (wt[a][1] != 0.f) | (wt[a][2] != 0.f) | (wt[a][3] != 0.f);
         reach |= __ballot(any) ? (1u << a) : 0u;
     }
@@ -273,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void k_disco_fuse(const DiscoParams P) {
         float acc = 0.f;
 #pragma unroll
         for (int a = 0; a < NA; ++a)
-            if ((reach >> a) & 1u) acc += prob[a] * disco_tap4(P.feats + ((size_t)a * C + c) * HW, off[a], wt[a]);
+            if ((reach >> a) & 1u) acc += prob[a] * tap4(P.feats + ((size_t)a * C + c) * HW, off[a], wt[a]);
         if (live) P.out[(size_t)c * HW + pix] = acc;
     }
 }
@@ -292,22 +257,16 @@ extern "C" int heal_disco_fuse(const float* feats, int n_agents, int channels, i
     HEAL_REQUIRE((long long)n_agents * channels * H * W < (1ll << 31) && (long long)DF_M1 * H * W < (1ll << 31),
                  "disco_fuse: more than 2^31 elements");
     HEAL_REQUIRE(feats && out, "disco_fuse: null feats / out");
-    HEAL_REQUIRE(affine_host != nullptr || affine_dev != nullptr, "disco_fuse: affine is NULL (host and device)");
+    DiscoParams P;
+    if (fill_affine_rows(P.rows, "disco_fuse", affine_host, affine_dev, n_agents, grid_f64)) return 1;
     HEAL_REQUIRE((n_agents == 1 && scores == nullptr) || (e0 && w1n_frag && w2_frag && b2 && w3 && b3 && w4 && b4),
                  "disco_fuse: null PixelWeightLayer operand");
-    DiscoParams P;
     P.feats = feats; P.e0 = e0; P.w1n = w1n_frag; P.w2f = w2_frag; P.b2 = b2; P.w3 = w3; P.b3 = b3; P.w4 = w4; P.b4 = b4;
-    P.out = out; P.scores = scores; P.mdev = affine_dev;
-    P.C = channels; P.H = H; P.W = W; P.grid_f64 = grid_f64;
-    for (int a = 0; a < WF_MAXA; ++a)
-        for (int k = 0; k < 6; ++k) P.m[a][k] = (a < n_agents && affine_host) ? affine_host[a * 6 + k] : 0.0;
+    P.out = out; P.scores = scores;
+    P.C = channels; P.H = H; P.W = W;
     const dim3 grid(ceil_div(W, DF_TW), ceil_div(H, DF_TH));
     hipStream_t st = (hipStream_t)stream;
-    switch (n_agents) {
-#define HEAL_DF(N) case N: HEAL_LAUNCH_EV(k_disco_fuse<N>, grid, dim3(256), 0, st, P); break;
-        HEAL_DF(1) HEAL_DF(2) HEAL_DF(3) HEAL_DF(4) HEAL_DF(5) HEAL_DF(6) HEAL_DF(7) HEAL_DF(8)
-#undef HEAL_DF
-    }
+    HEAL_FOR_AGENTS(n_agents, "disco_fuse", HEAL_LAUNCH_EV(k_disco_fuse<NA>, grid, dim3(256), 0, st, P));
     HEAL_LAUNCH_CHECK();
     return 0;
 }

@@ -22,9 +22,8 @@ constexpr int WAB_TW = 16, WAB_TH = 4;                     // backward: one wave
 constexpr int WAB_CCH = HEAL_WARP_BWD_CHANNELS;            // channels per thread: the candidates' taps are computed once per chunk
 
 struct WarpAffineParams {
-    const double* mdev;     // device copy of the rows [n][6] (wins over `m` when non-null, as in WarpParams of warp_fuse.hip)
-    double m[WF_MAXA][6];
-    int n, C, H, W, grid_f64, cchunks;
+    AffineRows rows;
+    int n, C, H, W, cchunks;
 };
 
 __global__ __launch_bounds__(256) void k_warp_affine_forward(const float* __restrict__ src, WarpAffineParams p,
@@ -35,13 +34,7 @@ __global__ __launch_bounds__(256) void k_warp_affine_forward(const float* __rest
     if (w >= p.W || h >= p.H) return;
     const int a = bk.z / p.cchunks, c0 = (bk.z - a * p.cchunks) * WAF_CCH;
     const int HW = p.H * p.W;
-    double m[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) m[k] = p.mdev ? p.mdev[a * 6 + k] : p.m[a][k];     // wave-uniform
-    float gx, gy;
-    if (p.grid_f64) grid_point<double>(m, h, w, p.H, p.W, gx, gy);
-    else grid_point<float>(m, h, w, p.H, p.W, gx, gy);
-    const Taps t = make_taps(gx, gy, p.H, p.W);
+    const Taps t = affine_taps(p.rows, a, h, w, p.H, p.W);
     const int pix = h * p.W + w;
     const float* __restrict__ s = src + ((size_t)a * p.C + c0) * HW;
     float* __restrict__ o = out + ((size_t)a * p.C + c0) * HW + pix;
@@ -137,13 +130,11 @@ extern "C" int heal_warp_affine_forward(const float* src, int n, int C, int H, i
     HEAL_REQUIRE(n >= 1 && n <= WF_MAXA, "warp_affine_forward: n must be in [1,%d] (got %d)", WF_MAXA, n);
     HEAL_REQUIRE(C >= 1 && H >= 1 && W >= 1 && (long long)H * W <= (1ll << 30), "warp_affine_forward: bad shape (%d, %d, %d)", C, H, W);
     HEAL_REQUIRE(src && out, "warp_affine_forward: null pointer");
-    HEAL_REQUIRE(affine_host != nullptr || affine_dev != nullptr, "warp_affine_forward: affine is NULL (host and device)");
     WarpAffineParams p;
-    p.mdev = affine_dev; p.n = n; p.C = C; p.H = H; p.W = W; p.grid_f64 = grid_f64; p.cchunks = ceil_div(C, WAF_CCH);
+    if (fill_affine_rows(p.rows, "warp_affine_forward", affine_host, affine_dev, n, grid_f64)) return 1;
+    p.n = n; p.C = C; p.H = H; p.W = W; p.cchunks = ceil_div(C, WAF_CCH);
     HEAL_REQUIRE((long long)n * p.cchunks <= 65535, "warp_affine_forward: n * ceil(C / %d) must not exceed 65535", WAF_CCH);
     HEAL_REQUIRE(ceil_div(H, WAF_TH) <= 65535, "warp_affine_forward: H must not exceed %d", 65535 * WAF_TH);
-    for (int a = 0; a < WF_MAXA; ++a)
-        for (int k = 0; k < 6; ++k) p.m[a][k] = (a < n && affine_host) ? affine_host[a * 6 + k] : 0.0;
     dim3 grid(ceil_div(W, WAF_TW), ceil_div(H, WAF_TH), n * p.cchunks);
     HEAL_LAUNCH_EV(k_warp_affine_forward, grid, dim3(256), 0, (hipStream_t)stream, src, p, out);
     HEAL_LAUNCH_CHECK();

@@ -28,19 +28,10 @@ namespace heal {
 constexpr int WF_TW = 32, WF_TH = 8;  // pixel tile per 256-thread block
 
 struct WarpParams {
-    const double* mdev;     // device copy of the affine rows [n_agents][6] (wins over `m` when non-null: a captured HIP
-                            // graph then follows the poses of the frame it is replayed on instead of the captured ones)
-    double m[WF_MAXA][6];   // rows of affine_matrix[b][0, a]: m00 m01 m02 m10 m11 m12
+    AffineRows rows;
     int crop[WF_MAXA][4];   // (h0,h1,w0,w1) window where the score is kept; h1<=h0: keep everything
     int n_agents, C, H, W;
-    int grid_f64;
 };
-
-__device__ __forceinline__ void load_affine(const WarpParams& p, int a, double (&m)[6]) {
-    // wave-uniform: six scalar loads from the kernel arguments or from the device buffer
-#pragma unroll
-    for (int k = 0; k < 6; ++k) m[k] = p.mdev ? p.mdev[a * 6 + k] : p.m[a][k];
-}
 
 __device__ __forceinline__ float score_at(const float* __restrict__ occ, int idx, int W, const int* crop) {
     // sigmoid(occ) + 1e-4, zero outside the camera crop window (pyramid_fuse.py:145-162)
@@ -101,25 +92,9 @@ __global__ __launch_bounds__(256, 4) void k_warp_fuse(const float* __restrict__ 
     for (int a = NA; a < WF_MAXA; ++a) prob[a] = 0.f;
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
-        prob[a] = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { off[a][k] = 0; wt[a][k] = 0.f; }
-        {
-            float gx, gy;
-            double m[6];
-            load_affine(p, a, m);
-            if (p.grid_f64) grid_point<double>(m, h, w, p.H, p.W, gx, gy);
-            else grid_point<float>(m, h, w, p.H, p.W, gx, gy);
-            const Taps t = make_taps(gx, gy, p.H, p.W);
-            prob[a] = sample_score(occ + (size_t)a * HW, t, p.W, p.crop[a]);
-            const int o4[4] = {t.off, t.off + 1, t.off + p.W, t.off + p.W + 1};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const bool ok = (t.ok >> k) & 1u;
-                off[a][k] = ok ? o4[k] : 0;
-                wt[a][k] = ok ? t.w[k] : 0.f;
-            }
-        }
+        const Taps t = affine_taps(p.rows, a, h, w, p.H, p.W);
+        prob[a] = sample_score(occ + (size_t)a * HW, t, p.W, p.crop[a]);
+        flat_taps(t, p.W, off[a], wt[a]);
     }
     agent_softmax(prob, NA);
     unsigned live = 0;       // bit a: some lane of this wave samples agent a inside its map (else every tap weight is zero)
@@ -204,9 +179,8 @@ struct WfLevel {
 };
 struct WfLevels {
     WfLevel lv[WL_MAXL];
-    int n_levels, n_agents, grid_f64, dbg;
-    const double* mdev;
-    double m[WF_MAXA][6];
+    int n_levels, n_agents, dbg;
+    AffineRows rows;
 };
 
 // sample_score on a source descriptor: tap k at (ty + (k >> 1), tx + (k & 1)); sigmoid(occ) + 1e-4 inside `keep`, exactly zero (and
@@ -268,22 +242,11 @@ __global__ __launch_bounds__(256) void k_warp_fuse_lds(const WfLevels P) {
         if (live) {
             float gx, gy;
             double m[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) m[k] = P.mdev ? P.mdev[a * 6 + k] : P.m[a][k];   // wave-uniform scalar loads
-            if (P.grid_f64) {      // grid_point<T> with the base coordinates taken from LDS (same operations, same order)
-                const double xs = s_base_d[0][tid & (WL_T - 1)], ys = s_base_d[1][tid >> 4];
-                gx = (float)((m[0] * xs + m[1] * ys) + m[2]);
-                gy = (float)((m[3] * xs + m[4] * ys) + m[5]);
-            } else {
-                const float xs = s_base_f[0][tid & (WL_T - 1)], ys = s_base_f[1][tid >> 4];
-                gx = (float)(((float)m[0] * xs + (float)m[1] * ys) + (float)m[2]);
-                gy = (float)(((float)m[3] * xs + (float)m[4] * ys) + (float)m[5]);
-            }
-            Taps t = make_taps(gx, gy, L.H, L.W);
-            // north-west tap coordinates: the clamps of make_taps on the coordinates themselves (t.off = y0 * W + x0)
-            const float ix = ((gx + 1.f) * (float)L.W - 1.f) / 2.f, iy = ((gy + 1.f) * (float)L.H - 1.f) / 2.f;
-            tx[a] = (int)fminf(fmaxf(floorf(ix), -2.f), (float)L.W);
-            ty[a] = (int)fminf(fmaxf(floorf(iy), -2.f), (float)L.H);
+            affine_row(P.rows, a, m);
+            // grid_point<T> with the base coordinates taken from LDS
+            if (P.rows.f64) grid_from_base<double>(m, s_base_d[0][tid & (WL_T - 1)], s_base_d[1][tid >> 4], gx, gy);
+            else grid_from_base<float>(m, s_base_f[0][tid & (WL_T - 1)], s_base_f[1][tid >> 4], gx, gy);
+            Taps t = make_taps(gx, gy, L.H, L.W, tx[a], ty[a]);
             // a tap outside the agent's box is a tap outside its map: feature 0, score 0, never dereferenced.  (With the host's
             // checks -- window +- 1 inside the box -- such a tap never carries weight: its pixel's score is zero anyway.)
             const WfSource& S = L.src[a];
@@ -416,12 +379,7 @@ __global__ __launch_bounds__(256) void k_warp_agent(const float* __restrict__ fe
     const int h = bk.y * WF_TH + (threadIdx.x / WF_TW);
     if (w >= p.W || h >= p.H) return;
     const int HW = p.H * p.W;
-    float gx, gy;
-    double m[6];
-    load_affine(p, 0, m);
-    if (p.grid_f64) grid_point<double>(m, h, w, p.H, p.W, gx, gy);
-    else grid_point<float>(m, h, w, p.H, p.W, gx, gy);
-    const Taps t = make_taps(gx, gy, p.H, p.W);
+    const Taps t = affine_taps(p.rows, 0, h, w, p.H, p.W);
     const int pix = h * p.W + w;
     if (bk.z == 0 && score_ego != nullptr) score_ego[pix] = sample_score(occ, t, p.W, p.crop[0]);
     const int c0 = bk.z * CCH;
@@ -446,12 +404,7 @@ __global__ __launch_bounds__(256) void k_warp_agents_pm(const float* __restrict_
     const int h = bk.y * WPM_TH + (pix_l / WPM_TW);
     const int HW = p.H * p.W;
     if (w < p.W && h < p.H) {
-        float gx, gy;
-        double m[6];
-        load_affine(p, a, m);
-        if (p.grid_f64) grid_point<double>(m, h, w, p.H, p.W, gx, gy);
-        else grid_point<float>(m, h, w, p.H, p.W, gx, gy);
-        const Taps t = make_taps(gx, gy, p.H, p.W);
+        const Taps t = affine_taps(p.rows, a, h, w, p.H, p.W);
         const float* src = feats + ((size_t)a * p.C + c0 + cg * 16) * HW;
 #pragma unroll 4
         for (int c = 0; c < 16; ++c)
@@ -522,20 +475,9 @@ __global__ __launch_bounds__(256) void k_warp_fuse_backward(const float* __restr
     for (int a = NA; a < WF_MAXA; ++a) prob[a] = 0.f;
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
-        float gx, gy;
-        double m[6];
-        load_affine(p, a, m);
-        if (p.grid_f64) grid_point<double>(m, h, w, p.H, p.W, gx, gy);
-        else grid_point<float>(m, h, w, p.H, p.W, gx, gy);
-        const Taps t = make_taps(gx, gy, p.H, p.W);
+        const Taps t = affine_taps(p.rows, a, h, w, p.H, p.W);
         prob[a] = sample_score(occ + (size_t)a * HW, t, p.W, p.crop[a]);
-        const int o4[4] = {t.off, t.off + 1, t.off + p.W, t.off + p.W + 1};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const bool ok = (t.ok >> k) & 1u;
-            off[a][k] = ok ? o4[k] : -1;
-            tw[a][k] = ok ? t.w[k] : 0.f;
-        }
+        flat_taps(t, p.W, off[a], tw[a], -1);      // an outside tap is skipped, not read with weight 0
         q[a] = 0.f;
     }
     agent_softmax(prob, NA);
@@ -610,9 +552,8 @@ struct WaLevel {
 };
 struct WaLevels {
     WaLevel lv[WL_MAXL];
-    int n_levels, n_agents, grid_f64, mode;   // mode 0: attention, 1: max
-    const double* mdev;
-    double m[WF_MAXA][6];
+    int n_levels, n_agents, mode;   // mode 0: attention, 1: max
+    AffineRows rows;
 };
 
 // The masked form (heal_warp_att_fuse_levels_masked, include/heal_amd_comm.h): one mask [n_agents, 1, H, W] per level.  A thread reads
@@ -642,24 +583,7 @@ __device__ __forceinline__ void warp_att_fuse_body(const WaLevels& P, const WaMa
     unsigned reach = 0;      // bit a: some lane of this wave samples agent a inside its map
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { off[a][k] = 0; wt[a][k] = 0.f; }
-        if (live) {
-            float gx, gy;
-            double m[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) m[k] = P.mdev ? P.mdev[a * 6 + k] : P.m[a][k];   // wave-uniform
-            if (P.grid_f64) grid_point<double>(m, h, w, L.H, L.W, gx, gy);
-            else grid_point<float>(m, h, w, L.H, L.W, gx, gy);
-            const Taps t = make_taps(gx, gy, L.H, L.W);
-            const int o4[4] = {t.off, t.off + 1, t.off + L.W, t.off + L.W + 1};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const bool ok = (t.ok >> k) & 1u;    // a tap outside the image: weight 0 on a valid address
-                off[a][k] = ok ? o4[k] : 0;
-                wt[a][k] = ok ? t.w[k] : 0.f;
-            }
-        }
+        pixel_taps(P.rows, a, h, w, L.H, L.W, live, off[a], wt[a]);
         if constexpr (MASKED) {
             const float* mp = M->m[lvl] + (size_t)a * HW;
 #pragma unroll
@@ -671,7 +595,7 @@ __device__ __forceinline__ void warp_att_fuse_body(const WaLevels& P, const WaMa
     const int cper = (L.C + n_cs - 1) / n_cs;
     const int c_lo = cs * cper, c_hi = min(c_lo + cper, L.C);
 
-    auto tap4 = [&](int a, int c) -> float {      // sample(): nw, ne, sw, se accumulated in that order
+    auto sampled = [&](int a, int c) -> float {      // sample(): nw, ne, sw, se accumulated in that order
         const float* src = L.feats + ((size_t)a * L.C + c) * HW;
         if constexpr (MASKED) {
             float v = (src[off[a][0]] * mk[a][0]) * wt[a][0];
@@ -680,11 +604,7 @@ __device__ __forceinline__ void warp_att_fuse_body(const WaLevels& P, const WaMa
             v += (src[off[a][3]] * mk[a][3]) * wt[a][3];
             return v;
         } else {
-            float v = src[off[a][0]] * wt[a][0];
-            v += src[off[a][1]] * wt[a][1];
-            v += src[off[a][2]] * wt[a][2];
-            v += src[off[a][3]] * wt[a][3];
-            return v;
+            return tap4(src, off[a], wt[a]);
         }
     };
 
@@ -696,29 +616,23 @@ __device__ __forceinline__ void warp_att_fuse_body(const WaLevels& P, const WaMa
         if (reach & 1u) {          // an ego that reaches no lane: every logit of the wave is 0
 #pragma unroll 2
             for (int c = c_lo; c < c_hi; ++c) {
-                const float x0 = tap4(0, c);
+                const float x0 = sampled(0, c);
                 dot[0] += x0 * x0;
 #pragma unroll
                 for (int a = 1; a < NA; ++a)
-                    if ((reach >> a) & 1u) dot[a] += x0 * tap4(a, c);
+                    if ((reach >> a) & 1u) dot[a] += x0 * sampled(a, c);
             }
         }
 #pragma unroll
         for (int a = 0; a < NA; ++a) s_dot[(cs * NA + a) * pix_n + lane] = dot[a];
         __syncthreads();
-        float mx = -INFINITY;
 #pragma unroll
         for (int a = 0; a < NA; ++a) {
             float d = s_dot[a * pix_n + lane];
             for (int s = 1; s < n_cs; ++s) d += s_dot[(s * NA + a) * pix_n + lane];
             prob[a] = d / L.sqrt_dim;
-            mx = fmaxf(mx, prob[a]);
         }
-        float den = 0.f;
-#pragma unroll
-        for (int a = 0; a < NA; ++a) { prob[a] = expf(prob[a] - mx); den += prob[a]; }
-#pragma unroll
-        for (int a = 0; a < NA; ++a) prob[a] = prob[a] / den;
+        softmax_agents(prob);
     } else {
 #pragma unroll
         for (int a = 0; a < NA; ++a) prob[a] = 0.f;
@@ -731,11 +645,11 @@ __device__ __forceinline__ void warp_att_fuse_body(const WaLevels& P, const WaMa
         if (P.mode == 0) {
 #pragma unroll
             for (int a = 0; a < NA; ++a)
-                if ((reach >> a) & 1u) acc += prob[a] * tap4(a, c);
+                if ((reach >> a) & 1u) acc += prob[a] * sampled(a, c);
         } else {
 #pragma unroll
             for (int a = 0; a < NA; ++a) {
-                const float v = ((reach >> a) & 1u) ? tap4(a, c) : 0.f;     // an agent out of reach is a zero map, and takes part
+                const float v = ((reach >> a) & 1u) ? sampled(a, c) : 0.f;     // an agent out of reach is a zero map, and takes part
                 acc = a == 0 ? v : fmaxf(acc, v);
             }
         }
@@ -760,13 +674,10 @@ static int fill_params(WarpParams& p, int n_agents, int C, int H, int W, const d
     HEAL_REQUIRE(n_agents >= 1 && n_agents <= WF_MAXA, "warp_fuse: n_agents must be in [1,%d] (got %d)",
                  WF_MAXA, n_agents);
     HEAL_REQUIRE(C >= 1 && H >= 1 && W >= 1, "warp_fuse: bad shape");
-    HEAL_REQUIRE(affine_host != nullptr || affine_dev != nullptr, "warp_fuse: affine is NULL (host and device)");
-    p.n_agents = n_agents; p.C = C; p.H = H; p.W = W; p.grid_f64 = grid_f64;
-    p.mdev = affine_dev;
-    for (int a = 0; a < WF_MAXA; ++a) {
-        for (int k = 0; k < 6; ++k) p.m[a][k] = (a < n_agents && affine_host) ? affine_host[a * 6 + k] : 0.0;
+    if (fill_affine_rows(p.rows, "warp_fuse", affine_host, affine_dev, n_agents, grid_f64)) return 1;
+    p.n_agents = n_agents; p.C = C; p.H = H; p.W = W;
+    for (int a = 0; a < WF_MAXA; ++a)
         for (int k = 0; k < 4; ++k) p.crop[a][k] = (a < n_agents && crop_host) ? crop_host[a * 4 + k] : 0;
-    }
     return 0;
 }
 
@@ -788,11 +699,7 @@ extern "C" int heal_warp_fuse(const float* feats, const float* occ, int n_agents
     if (cch > channels) cch = (channels + 3) / 4 * 4;
     dim3 grid(ceil_div(W, WF_TW), ceil_div(H, WF_TH), ceil_div(channels, cch));
     hipStream_t st = (hipStream_t)stream;
-    switch (n_agents) {
-#define HEAL_WF(N) case N: k_warp_fuse<N><<<grid, 256, 0, st>>>(feats, occ, p, cch, out); break;
-        HEAL_WF(1) HEAL_WF(2) HEAL_WF(3) HEAL_WF(4) HEAL_WF(5) HEAL_WF(6) HEAL_WF(7) HEAL_WF(8)
-#undef HEAL_WF
-    }
+    HEAL_FOR_AGENTS(n_agents, "warp_fuse", k_warp_fuse<NA><<<grid, 256, 0, st>>>(feats, occ, p, cch, out));
     HEAL_LAUNCH_CHECK();
     return 0;
 }
@@ -800,13 +707,10 @@ extern "C" int heal_warp_fuse(const float* feats, const float* occ, int n_agents
 // Fills the launch descriptor from per-(level, agent) sources and launches k_warp_fuse_lds.  `who` names the entry point in messages.
 static int launch_warp_fuse_levels(const char* who, int n_levels, const heal_k5_source* src_host, int n_agents,
                                    const int32_t* channels_host, const int32_t* h_host, const int32_t* w_host,
-                                   const double* affine_host, const double* affine_dev, int grid_f64, const int32_t* crop_host,
-                                   float* const* out_host, void* stream) {
+                                   const AffineRows& rows, const int32_t* crop_host, float* const* out_host, void* stream) {
     WfLevels P;
-    P.n_levels = n_levels; P.n_agents = n_agents; P.grid_f64 = grid_f64; P.mdev = affine_dev;
+    P.n_levels = n_levels; P.n_agents = n_agents; P.rows = rows;
     P.dbg = HEAL_DEBUG_ENV("HEAL_K5_DBG");   // timing experiments only (read once, announced on stderr)
-    for (int a = 0; a < WF_MAXA; ++a)
-        for (int k = 0; k < 6; ++k) P.m[a][k] = (a < n_agents && affine_host) ? affine_host[a * 6 + k] : 0.0;
     long long blocks = 0;
     for (int l = 0; l < WL_MAXL; ++l) {
         WfLevel& L = P.lv[l];
@@ -856,11 +760,7 @@ static int launch_warp_fuse_levels(const char* who, int n_levels, const heal_k5_
     }
     HEAL_REQUIRE(blocks < (1ll << 30), "%s: grid too large", who);
     hipStream_t st = (hipStream_t)stream;
-    switch (n_agents) {
-#define HEAL_WFL(N) case N: HEAL_LAUNCH_EV(k_warp_fuse_lds<N>, dim3((unsigned)blocks), dim3(256), 0, st, P); break;
-        HEAL_WFL(1) HEAL_WFL(2) HEAL_WFL(3) HEAL_WFL(4) HEAL_WFL(5) HEAL_WFL(6) HEAL_WFL(7) HEAL_WFL(8)
-#undef HEAL_WFL
-    }
+    HEAL_FOR_AGENTS(n_agents, who, HEAL_LAUNCH_EV(k_warp_fuse_lds<NA>, dim3((unsigned)blocks), dim3(256), 0, st, P));
     HEAL_LAUNCH_CHECK();
     return 0;
 }
@@ -871,7 +771,8 @@ extern "C" int heal_warp_fuse_levels(int n_levels, const float* const* feats_hos
                                      const int32_t* crop_host, float* const* out_host, void* stream) {
     HEAL_REQUIRE(n_levels >= 1 && n_levels <= WL_MAXL, "warp_fuse_levels: 1..%d levels per launch (got %d)", WL_MAXL, n_levels);
     HEAL_REQUIRE(n_agents >= 1 && n_agents <= WF_MAXA, "warp_fuse_levels: n_agents must be in [1,%d] (got %d)", WF_MAXA, n_agents);
-    HEAL_REQUIRE(affine_host != nullptr || affine_dev != nullptr, "warp_fuse_levels: affine is NULL (host and device)");
+    AffineRows rows;
+    if (fill_affine_rows(rows, "warp_fuse_levels", affine_host, affine_dev, n_agents, grid_f64)) return 1;
     // the stacked tensors as sources: agent a's full map at feats + a C HW
     heal_k5_source src[WL_MAXL * WF_MAXA];
     for (int l = 0; l < n_levels; ++l) {
@@ -886,8 +787,8 @@ extern "C" int heal_warp_fuse_levels(int n_levels, const float* const* feats_hos
             h.box[0] = 0; h.box[1] = h_host[l]; h.box[2] = 0; h.box[3] = w_host[l];
         }
     }
-    return launch_warp_fuse_levels("warp_fuse_levels", n_levels, src, n_agents, channels_host, h_host, w_host, affine_host, affine_dev,
-                                   grid_f64, crop_host, out_host, stream);
+    return launch_warp_fuse_levels("warp_fuse_levels", n_levels, src, n_agents, channels_host, h_host, w_host, rows, crop_host, out_host,
+                                   stream);
 }
 
 extern "C" int heal_warp_fuse_levels_src(int n_levels, const heal_k5_source* src_host, int n_agents, const int32_t* channels_host,
@@ -896,7 +797,8 @@ extern "C" int heal_warp_fuse_levels_src(int n_levels, const heal_k5_source* src
                                          void* stream) {
     HEAL_REQUIRE(n_levels >= 1 && n_levels <= WL_MAXL, "warp_fuse_levels_src: 1..%d levels per launch (got %d)", WL_MAXL, n_levels);
     HEAL_REQUIRE(n_agents >= 1 && n_agents <= WF_MAXA, "warp_fuse_levels_src: n_agents must be in [1,%d] (got %d)", WF_MAXA, n_agents);
-    HEAL_REQUIRE(affine_host != nullptr || affine_dev != nullptr, "warp_fuse_levels_src: affine is NULL (host and device)");
+    AffineRows rows;
+    if (fill_affine_rows(rows, "warp_fuse_levels_src", affine_host, affine_dev, n_agents, grid_f64)) return 1;
     HEAL_REQUIRE(src_host && channels_host && h_host && w_host && out_host, "warp_fuse_levels_src: null argument");
     for (int l = 0; l < n_levels; ++l) {
         const int H = h_host[l], W = w_host[l];
@@ -925,8 +827,8 @@ extern "C" int heal_warp_fuse_levels_src(int n_levels, const heal_k5_source* src
                          "of the map rows 16-byte aligned: pointer - 4 x0 bytes)", l, a);
         }
     }
-    return launch_warp_fuse_levels("warp_fuse_levels_src", n_levels, src_host, n_agents, channels_host, h_host, w_host, affine_host,
-                                   affine_dev, grid_f64, crop_host, out_host, stream);
+    return launch_warp_fuse_levels("warp_fuse_levels_src", n_levels, src_host, n_agents, channels_host, h_host, w_host, rows, crop_host,
+                                   out_host, stream);
 }
 
 // heal_warp_att_fuse_levels and its masked form: the same checks and launch descriptor; mask_host null = the unmasked kernel.
@@ -938,11 +840,9 @@ static int launch_warp_att_fuse_levels(int n_levels, const float* const* feats_h
     HEAL_REQUIRE(n_agents >= 1 && n_agents <= WF_MAXA, "warp_att_fuse_levels: n_agents must be in [1,%d] (got %d)", WF_MAXA, n_agents);
     HEAL_REQUIRE(mode == 0 || mode == 1, "warp_att_fuse_levels: mode must be 0 (attention) or 1 (max), got %d", mode);
     HEAL_REQUIRE(feats_host && out_host && channels_host && h_host && w_host, "warp_att_fuse_levels: null argument");
-    HEAL_REQUIRE(affine_host != nullptr || affine_dev != nullptr, "warp_att_fuse_levels: affine is NULL (host and device)");
     WaLevels P;
-    P.n_levels = n_levels; P.n_agents = n_agents; P.grid_f64 = grid_f64; P.mode = mode; P.mdev = affine_dev;
-    for (int a = 0; a < WF_MAXA; ++a)
-        for (int k = 0; k < 6; ++k) P.m[a][k] = (a < n_agents && affine_host) ? affine_host[a * 6 + k] : 0.0;
+    if (fill_affine_rows(P.rows, "warp_att_fuse_levels", affine_host, affine_dev, n_agents, grid_f64)) return 1;
+    P.n_levels = n_levels; P.n_agents = n_agents; P.mode = mode;
     long long blocks = 0;
     for (int l = 0; l < WL_MAXL; ++l) {
         WaLevel& L = P.lv[l];
@@ -968,18 +868,11 @@ static int launch_warp_att_fuse_levels(int n_levels, const float* const* feats_h
             M.m[l] = mask_host[l < n_levels ? l : 0];
             HEAL_REQUIRE(M.m[l], "warp_att_fuse_levels_masked: mask of level %d is NULL", l);
         }
-        switch (n_agents) {
-#define HEAL_WAF(N) case N: HEAL_LAUNCH_EV(k_warp_att_fuse_masked<N>, dim3((unsigned)blocks), dim3(WA_THREADS), 0, st, P, M); break;
-            HEAL_WAF(1) HEAL_WAF(2) HEAL_WAF(3) HEAL_WAF(4) HEAL_WAF(5) HEAL_WAF(6) HEAL_WAF(7) HEAL_WAF(8)
-#undef HEAL_WAF
-        }
-        HEAL_LAUNCH_CHECK();
-        return 0;
-    }
-    switch (n_agents) {
-#define HEAL_WAF(N) case N: HEAL_LAUNCH_EV(k_warp_att_fuse<N>, dim3((unsigned)blocks), dim3(WA_THREADS), 0, st, P); break;
-        HEAL_WAF(1) HEAL_WAF(2) HEAL_WAF(3) HEAL_WAF(4) HEAL_WAF(5) HEAL_WAF(6) HEAL_WAF(7) HEAL_WAF(8)
-#undef HEAL_WAF
+        HEAL_FOR_AGENTS(n_agents, "warp_att_fuse_levels_masked",
+                        HEAL_LAUNCH_EV(k_warp_att_fuse_masked<NA>, dim3((unsigned)blocks), dim3(WA_THREADS), 0, st, P, M));
+    } else {
+        HEAL_FOR_AGENTS(n_agents, "warp_att_fuse_levels",
+                        HEAL_LAUNCH_EV(k_warp_att_fuse<NA>, dim3((unsigned)blocks), dim3(WA_THREADS), 0, st, P));
     }
     HEAL_LAUNCH_CHECK();
     return 0;
@@ -1075,11 +968,8 @@ extern "C" int heal_warp_fuse_backward(const float* feats, const float* occ, int
     HEAL_REQUIRE(feats && occ && grad_out && grad_feats && grad_occ, "warp_fuse_backward: null pointer");
     dim3 grid(ceil_div(W, WF_TW), ceil_div(H, WF_TH));
     hipStream_t st = (hipStream_t)stream;
-    switch (n_agents) {
-#define HEAL_WFB(N) case N: k_warp_fuse_backward<N><<<grid, 256, 0, st>>>(feats, occ, p, grad_out, grad_feats, grad_occ); break;
-        HEAL_WFB(1) HEAL_WFB(2) HEAL_WFB(3) HEAL_WFB(4) HEAL_WFB(5) HEAL_WFB(6) HEAL_WFB(7) HEAL_WFB(8)
-#undef HEAL_WFB
-    }
+    HEAL_FOR_AGENTS(n_agents, "warp_fuse_backward",
+                    k_warp_fuse_backward<NA><<<grid, 256, 0, st>>>(feats, occ, p, grad_out, grad_feats, grad_occ));
     HEAL_LAUNCH_CHECK();
     return 0;
 }

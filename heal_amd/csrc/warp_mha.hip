@@ -44,20 +44,10 @@ struct WarpMhaParams {
     float* ctx;             // [C, H, W]
     float* ego_warped;      // [C, H, W]
     float* logits;          // [n, heads, H, W] or null
-    const double* mdev;     // device copy of the affine rows (wins over `m` when non-null)
-    double m[WF_MAXA][6];
-    int C, heads, H, W, grid_f64;
+    AffineRows rows;
+    int C, heads, H, W;
     float scale;
 };
-
-__device__ __forceinline__ float mha_tap4(const float* __restrict__ src, const int (&off)[4], const float (&wt)[4]) {
-    // sample(): nw, ne, sw, se accumulated in that order
-    float v = src[off[0]] * wt[0];
-    v += src[off[1]] * wt[1];
-    v += src[off[2]] * wt[2];
-    v += src[off[3]] * wt[3];
-    return v;
-}
 
 template <int NA>
 __global__ __launch_bounds__(HEAL_WAVE) void k_warp_mha_fuse(const WarpMhaParams P) {
@@ -73,24 +63,7 @@ __global__ __launch_bounds__(HEAL_WAVE) void k_warp_mha_fuse(const WarpMhaParams
     unsigned reach = 0;      // bit a: some lane of this wave samples agent a inside its map
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { off[a][k] = 0; wt[a][k] = 0.f; }
-        if (live) {
-            float gx, gy;
-            double m[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) m[k] = P.mdev ? P.mdev[a * 6 + k] : P.m[a][k];   // wave-uniform
-            if (P.grid_f64) grid_point<double>(m, h, w, P.H, P.W, gx, gy);
-            else grid_point<float>(m, h, w, P.H, P.W, gx, gy);
-            const Taps t = make_taps(gx, gy, P.H, P.W);
-            const int o4[4] = {t.off, t.off + 1, t.off + P.W, t.off + P.W + 1};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const bool ok = (t.ok >> k) & 1u;    // a tap outside the image: weight 0 on a valid address
-                off[a][k] = ok ? o4[k] : 0;
-                wt[a][k] = ok ? t.w[k] : 0.f;
-            }
-        }
+        pixel_taps(P.rows, a, h, w, P.H, P.W, live, off[a], wt[a]);
         const bool any = (wt[a][0] != 0.f) | (wt[a][1] != 0.f) | (wt[a][2] != 0.f) | (wt[a][3] != 0.f);
         reach |= __ballot(any) ? (1u << a) : 0u;
     }
@@ -98,7 +71,7 @@ __global__ __launch_bounds__(HEAL_WAVE) void k_warp_mha_fuse(const WarpMhaParams
     const bool ego_in = reach & 1u;
     // a map out of reach of the whole wave is a zero operand (its loads are skipped, never its term of the softmax)
     auto sample_k = [&](int a, int c) -> float {
-        return ((reach >> a) & 1u) ? mha_tap4(P.kv_map + ((size_t)a * 2 * C + c) * HW, off[a], wt[a]) : 0.f;
+        return ((reach >> a) & 1u) ? tap4(P.kv_map + ((size_t)a * 2 * C + c) * HW, off[a], wt[a]) : 0.f;
     };
 
     // ---- sweep 1: Q and K of this head, the ego's own map --------------------------------------------------------------------
@@ -107,10 +80,10 @@ __global__ __launch_bounds__(HEAL_WAVE) void k_warp_mha_fuse(const WarpMhaParams
     for (int a = 0; a < NA; ++a) prob[a] = 0.f;
 #pragma unroll 2
     for (int c = c_lo; c < c_hi; ++c) {
-        const float xe = ego_in ? mha_tap4(P.x_ego + (size_t)c * HW, off[0], wt[0]) : 0.f;
+        const float xe = ego_in ? tap4(P.x_ego + (size_t)c * HW, off[0], wt[0]) : 0.f;
         if (live) P.ego_warped[(size_t)c * HW + pix] = xe;
         if (NA > 1 || P.logits != nullptr) {
-            float q = ego_in ? mha_tap4(P.q_map + (size_t)c * HW, off[0], wt[0]) : 0.f;
+            float q = ego_in ? tap4(P.q_map + (size_t)c * HW, off[0], wt[0]) : 0.f;
             q = (q + P.bq[c]) * P.scale;      // F.multi_head_attention_forward scales q before the product
             const float bkc = P.bk[c];
 #pragma unroll
@@ -126,14 +99,7 @@ __global__ __launch_bounds__(HEAL_WAVE) void k_warp_mha_fuse(const WarpMhaParams
     if (NA == 1) {
         prob[0] = 1.f;      // the softmax of one logit: expf(0) / 1
     } else {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int a = 0; a < NA; ++a) mx = fmaxf(mx, prob[a]);
-        float den = 0.f;
-#pragma unroll
-        for (int a = 0; a < NA; ++a) { prob[a] = expf(prob[a] - mx); den += prob[a]; }
-#pragma unroll
-        for (int a = 0; a < NA; ++a) prob[a] = prob[a] / den;
+        softmax_agents(prob);
     }
 
     // ---- sweep 2: V of this head ---------------------------------------------------------------------------------------------
@@ -162,20 +128,14 @@ extern "C" int heal_warp_mha_fuse(const float* q_map, const float* kv_map, const
     HEAL_REQUIRE(2ll * n_agents * channels * H * W < (1ll << 31), "warp_mha_fuse: more than 2^31 elements");
     HEAL_REQUIRE(ceil_div(H, WM_TH) <= 65535, "warp_mha_fuse: H too large");
     HEAL_REQUIRE(q_map && kv_map && x_ego && bq && bk && bv && ctx && ego_warped, "warp_mha_fuse: null operand");
-    HEAL_REQUIRE(affine_host != nullptr || affine_dev != nullptr, "warp_mha_fuse: affine is NULL (host and device)");
     WarpMhaParams P;
+    if (fill_affine_rows(P.rows, "warp_mha_fuse", affine_host, affine_dev, n_agents, grid_f64)) return 1;
     P.q_map = q_map; P.kv_map = kv_map; P.x_ego = x_ego; P.bq = bq; P.bk = bk; P.bv = bv;
-    P.ctx = ctx; P.ego_warped = ego_warped; P.logits = logits; P.mdev = affine_dev;
-    P.C = channels; P.heads = heads; P.H = H; P.W = W; P.grid_f64 = grid_f64; P.scale = scale;
-    for (int a = 0; a < WF_MAXA; ++a)
-        for (int k = 0; k < 6; ++k) P.m[a][k] = (a < n_agents && affine_host) ? affine_host[a * 6 + k] : 0.0;
+    P.ctx = ctx; P.ego_warped = ego_warped; P.logits = logits;
+    P.C = channels; P.heads = heads; P.H = H; P.W = W; P.scale = scale;
     const dim3 grid(ceil_div(W, WM_TW), ceil_div(H, WM_TH), heads);
     hipStream_t st = (hipStream_t)stream;
-    switch (n_agents) {
-#define HEAL_WM(N) case N: HEAL_LAUNCH_EV(k_warp_mha_fuse<N>, grid, dim3(HEAL_WAVE), 0, st, P); break;
-        HEAL_WM(1) HEAL_WM(2) HEAL_WM(3) HEAL_WM(4) HEAL_WM(5) HEAL_WM(6) HEAL_WM(7) HEAL_WM(8)
-#undef HEAL_WM
-    }
+    HEAL_FOR_AGENTS(n_agents, "warp_mha_fuse", HEAL_LAUNCH_EV(k_warp_mha_fuse<NA>, grid, dim3(HEAL_WAVE), 0, st, P));
     HEAL_LAUNCH_CHECK();
     return 0;
 }

@@ -47,6 +47,12 @@ def _host_affine(affine_matrix):
     return a, a.dtype == np.float64
 
 
+def _torch_affine(affine_matrix, like):
+    """The affine matrix as a tensor on `like`'s device, in its own dtype (the torch compositions follow it as the reference does)."""
+    aff = affine_matrix if isinstance(affine_matrix, torch.Tensor) else torch.from_numpy(np.asarray(affine_matrix))
+    return aff.to(like.device)
+
+
 class _WarpThenFuse(nn.Module):
     """The operators share one shape: warp every agent of a scene into the ego frame (K5), then reduce the
     ego-frame stack with `fuse_warped` ([n,C,H,W] -> [C,H,W]).  The agent-sharded path (heal_amd/dist.py) warps on the
@@ -190,8 +196,7 @@ class CoBEVT(_WarpThenFuse):
             # the reference's arithmetic (fusion_in_one.py:412-430): Regroup's zero padding, warp_affine_simple of all L maps
             # (the grid built in the affine matrix's dtype, then cast; ops.WarpAffine in ops.warp_grad("kernel") mode unless a
             # padded agent's row is singular), the blocks on [B, L, C, H, W]
-            aff = affine_matrix if isinstance(affine_matrix, torch.Tensor) else torch.from_numpy(np.asarray(affine_matrix))
-            aff = aff.to(x.device)
+            aff = _torch_affine(affine_matrix, x)
             warped = []
             for b, feats in enumerate(regroup(x, lens)):
                 pad = torch.cat([feats, feats.new_zeros((L - feats.shape[0],) + tuple(feats.shape[1:]))])
@@ -241,8 +246,7 @@ class DiscoFusion(nn.Module):
         """fusion_in_one.py:175-201 as written (the CPU, gradient, training and unsupported-shape path)."""
         _, C, H, W = x.shape
         lens = record_len_to_list(record_len)
-        aff = affine_matrix if isinstance(affine_matrix, torch.Tensor) else torch.from_numpy(np.asarray(affine_matrix))
-        aff = aff.to(x.device)
+        aff = _torch_affine(affine_matrix, x)
         out = []
         for b, feats in enumerate(regroup(x, lens)):
             N = lens[b]
@@ -339,8 +343,7 @@ class Where2commFusion(nn.Module):
         """fusion_in_one.py:442-484 as written (the CPU, gradient and unsupported-shape path)."""
         _, C, H, W = x.shape
         lens = record_len_to_list(record_len)
-        aff = affine_matrix if isinstance(affine_matrix, torch.Tensor) else torch.from_numpy(np.asarray(affine_matrix))
-        aff = aff.to(x.device)
+        aff = _torch_affine(affine_matrix, x)
         out = []
         for b, feats in enumerate(regroup(x, lens)):
             N = lens[b]
@@ -427,8 +430,7 @@ class Who2comFusion(nn.Module):
         """fusion_in_one.py:493-539 as written (the CPU, gradient and unsupported-shape path)."""
         _, C, H, W = x.shape
         lens = record_len_to_list(record_len)
-        aff = affine_matrix if isinstance(affine_matrix, torch.Tensor) else torch.from_numpy(np.asarray(affine_matrix))
-        aff = aff.to(x.device)
+        aff = _torch_affine(affine_matrix, x)
         out = []
         for b, feats in enumerate(regroup(x, lens)):
             N = lens[b]
@@ -505,8 +507,7 @@ class V2VNetFusion(nn.Module):
         """fusion_in_one.py:238-318 as written (the CPU, gradient and unsupported-shape path)."""
         _, C, H, W = x.shape
         lens = record_len_to_list(record_len)
-        aff = affine_matrix if isinstance(affine_matrix, torch.Tensor) else torch.from_numpy(np.asarray(affine_matrix))
-        aff = aff.to(x.device)
+        aff = _torch_affine(affine_matrix, x)
         B, L = aff.shape[:2]
         split_x = regroup(x, lens)
         roi_mask = torch.zeros((B, L, L, 1, H, W)).to(x)
@@ -687,8 +688,7 @@ def fuse_levels(fusion_net, feature_list, record_len, affine_matrix):
     if max(lens) > MS_MAX_AGENTS:
         raise ValueError(f"multiscale fusion: a scene has {max(lens)} agents, more than the {MS_MAX_AGENTS} it is built for")
     if not ms_fused_ok(fusion_net, feature_list, lens):
-        aff = affine_matrix if isinstance(affine_matrix, torch.Tensor) else torch.from_numpy(np.asarray(affine_matrix))
-        aff = aff.to(feature_list[0].device)
+        aff = _torch_affine(affine_matrix, feature_list[0])
         return [fuse_level_torch(m, x, lens, aff) for m, x in zip(fusion_net, feature_list)]
     aff, f64 = _host_affine(affine_matrix)
     sqrt_dims = [m.sqrt_dim for m in fusion_net] if mode == "att" else None

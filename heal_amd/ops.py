@@ -597,6 +597,17 @@ def _crop_host(crop, n):
     return c, c.ctypes.data_as(ctypes.c_void_p)
 
 
+def _level_crops_host(crops, L, n):
+    """The crop table [L, n, 4] of a pyramid: crops[l] = per-agent (h0,h1,w0,w1) | None; a missing level or agent keeps everything."""
+    if crops is None or all(c is None for c in crops):
+        return None, ctypes.c_void_p(0)
+    carr = np.zeros((L, n, 4), dtype=np.int32)
+    for l, c in enumerate(crops):
+        if c is not None:
+            carr[l] = np.asarray([ci if ci is not None else (0, 0, 0, 0) for ci in c], dtype=np.int32).reshape(n, 4)
+    return carr, carr.ctypes.data_as(ctypes.c_void_p)
+
+
 def warp_fuse(feats, occ, affine_rows, grid_f64=True, crop=None):
     """K5 fused.  feats [n,C,H,W], occ [n,1,H,W] logits, affine_rows [n,2,3] (host array, or a CUDA tensor that is then
     read on the device at run time) -> [C,H,W]."""
@@ -628,13 +639,7 @@ def warp_fuse_levels(feats_list, occ_list, affine_rows, grid_f64=True, crops=Non
         outs.append(torch.empty((C, H, W), dtype=torch.float32, device=f.device))
         nbytes += 4.0 * H * W * (n * (C + 1) + C)
     a, ap, adev = _affine_args(affine_rows, n)
-    cp, carr = ctypes.c_void_p(0), None
-    if crops is not None and any(c is not None for c in crops):
-        carr = np.zeros((L, n, 4), dtype=np.int32)
-        for l, c in enumerate(crops):
-            if c is not None:
-                carr[l] = np.asarray([ci if ci is not None else (0, 0, 0, 0) for ci in c], dtype=np.int32).reshape(n, 4)
-        cp = carr.ctypes.data_as(ctypes.c_void_p)
+    carr, cp = _level_crops_host(crops, L, n)
     fp = _host_array([f.data_ptr() for f in feats_list], ctypes.c_void_p)
     op = _host_array([o.data_ptr() for o in occ_list], ctypes.c_void_p)
     yp = _host_array([y.data_ptr() for y in outs], ctypes.c_void_p)
@@ -691,13 +696,7 @@ def warp_fuse_levels_src(sources, shapes, affine_rows, grid_f64=True, crops=None
         chans.append(C)
         nbytes += 4.0 * C * H * W
     a, ap, adev = _affine_args(affine_rows, n)
-    cp, carr = ctypes.c_void_p(0), None
-    if crops is not None and any(c is not None for c in crops):
-        carr = np.zeros((L, n, 4), dtype=np.int32)
-        for l, c in enumerate(crops):
-            if c is not None:
-                carr[l] = np.asarray([ci if ci is not None else (0, 0, 0, 0) for ci in c], dtype=np.int32).reshape(n, 4)
-        cp = carr.ctypes.data_as(ctypes.c_void_p)
+    carr, cp = _level_crops_host(crops, L, n)
     yp = _host_array([y.data_ptr() for y in outs], ctypes.c_void_p)
     with _Timed("warp_fuse_levels", 0.0, nbytes, kernel_events=True):
         _capi.call("heal_warp_fuse_levels_src", L, ctypes.cast(desc, ctypes.c_void_p), n, _host_array(chans, ctypes.c_int32),

@@ -145,6 +145,16 @@ def rotation_rows(n, seed, reach=0.6):
     return np.stack(rows)
 
 
+def device_rows_case(seed=3):
+    """The pose set of the device-row checks -> (n, H, W, rows): 3 agents on a 13 x 21 map (neither extent a multiple of any tile),
+    the ego's identity and two rotations whose footprints lie partly on the map and partly off it (asserted)."""
+    n, H, W = 3, 13, 21
+    rows = rotation_rows(n, seed)
+    r = reached(rows, H, W)
+    assert r[0].all() and all(r[a].any() and not r[a].all() for a in (1, 2))
+    return n, H, W, rows
+
+
 def off_map_rows(n, whole=1, partial=2):
     """Identity rows, but agent `whole` translated by 3 maps (no ego pixel reaches it: every wave skips it) and agent `partial` by
     0.9 of a map along x only (the first tenth of every row reaches it: some waves in full, some in part, most not at all)."""

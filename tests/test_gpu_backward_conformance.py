@@ -114,7 +114,7 @@ def test_k5_collisions_add_up_exactly():
 
 
 def test_k5_device_poses():
-    """The affine rows as a CUDA float64 tensor (the affine_dev branch of load_affine): within the bound on the n = 5 data of the
+    """The affine rows as a CUDA float64 tensor (the device branch of affine_row, warp_taps.h): within the bound on the n = 5 data of the
     instantiation test, and on the exact fixture bit-equal to the host-rows result (atomic order cannot matter there)."""
     n, H, W, C = 5, 16, 8, 5
     feats, occ, gout = R.k5_ints(20 + n, n, C, H, W)

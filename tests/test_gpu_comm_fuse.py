@@ -51,13 +51,13 @@ def fixture(n, C, levels, pose, seed):
     return dict(feats=feats, masks=masks, rows=POSES[pose](n, seed), sqrt_dims=sd)
 
 
-def launch(fx, mode, masks, feats=None, what="masked"):
+def launch(fx, mode, masks, feats=None, what="masked", rows=None, grid_f64=True):
     """One launch into poisoned destinations, operands behind poisoned guards -> list of float32 numpy [C, H, W]."""
     op = Operands()
     xs = [op.put(f) for f in (fx["feats"] if feats is None else feats)]
     ms = None if masks is None else [op.put(m) for m in masks]
     outs = [op.out(f.shape[1:]) for f in fx["feats"]]
-    res = ops.warp_att_fuse_levels(xs, fx["rows"], True, mode, fx["sqrt_dims"], outs=outs, masks=ms)
+    res = ops.warp_att_fuse_levels(xs, fx["rows"] if rows is None else rows, grid_f64, mode, fx["sqrt_dims"], outs=outs, masks=ms)
     assert all(a.data_ptr() == b.data_ptr() for a, b in zip(res, outs))
     op.check(what)
     return [o.cpu().numpy() for o in outs]
@@ -94,6 +94,20 @@ def test_masked_entry_equals_the_unmasked_entry_on_premultiplied_maps(n, C, leve
                 ref = CR.masked_att(f, m, fx["rows"], fx["sqrt_dims"][l])
                 worst.add(f"pix{ref['layout'][0]}", R.max_ratio(got[l], ref["out"], ref["B"]), f"level {l} {f.shape}")
     worst.done()
+
+
+@pytest.mark.parametrize("grid_f64", [True, False])
+def test_masked_entry_device_rows_equal_host_rows(grid_f64):
+    """The rows as a float64 CUDA tensor (read by the kernel at run time) give the bits of the rows passed by value: the file's
+    smallest rotated fixture with more than one agent, three levels in one launch."""
+    fx = fixture(3, 6, 3, "rotated", 7)
+    dev_rows = torch.from_numpy(fx["rows"]).to(DEV)
+    for mode in ("att", "max"):
+        host = launch(fx, mode, fx["masks"], what=f"host rows {mode}", grid_f64=grid_f64)
+        got = launch(fx, mode, fx["masks"], what=f"device rows {mode}", rows=dev_rows, grid_f64=grid_f64)
+        for l in range(len(host)):
+            assert float(np.abs(host[l]).max()) > 0
+            assert torch.equal(torch.from_numpy(got[l]), torch.from_numpy(host[l])), (mode, l)
 
 
 def test_masks_are_checked_like_the_feature_maps_before_the_launch(monkeypatch):

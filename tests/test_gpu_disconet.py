@@ -9,6 +9,7 @@ import torch
 
 from heal_amd import _capi, ops
 from tests.backward_refs import shift_rows          # noqa: F401  (tests/test_gpu_where2comm.py imports it from here)
+from tests.coalign_refs import device_rows_case
 from tests.golden.disco_fill import fill_disco
 from tests.test_disconet_cpu import CASES, E2E_RANGE, TOL, case_inputs, e2e_data, e2e_hypes, make_disco, rel_err
 
@@ -178,6 +179,19 @@ def test_disco_fuse_odd_map_against_fp64():
     assert rel_err(scores.cpu().double().numpy(), want.numpy()) <= 1e-5
     ref = (torch.softmax(want, dim=0)[:, None] * nbr).sum(0)
     assert rel_err(out.cpu().double().numpy(), ref.numpy()) <= 1e-5
+
+
+@pytest.mark.parametrize("grid_f64", [True, False])
+def test_disco_fuse_device_rows_equal_host_rows(grid_f64):
+    """The rows as a float64 CUDA tensor (read by the kernel at run time) give the bits of the rows passed by value."""
+    n, H, W, rows = device_rows_case()
+    fx = disco_fixture(n, 8, H, W, seed=21)
+    frag = ops.mfma_a_fragments(fx[2])
+    with torch.no_grad():
+        host = ops.disco_fuse(fx[0], rows, grid_f64, fx[1], frag, *fx[3:], return_scores=True)
+        devr = ops.disco_fuse(fx[0], torch.from_numpy(rows).to(DEV), grid_f64, fx[1], frag, *fx[3:], return_scores=True)
+    assert float(host[0].abs().max()) > 0 and float(host[1].abs().max()) > 0
+    assert torch.equal(devr[0], host[0]) and torch.equal(devr[1], host[1])
 
 
 def test_disco_fuse_rejects_bad_inputs():

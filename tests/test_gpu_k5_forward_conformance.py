@@ -214,6 +214,10 @@ def test_levels_src_against_the_reference_on_the_padded_stack(form):
     assert within("heal_warp_fuse_levels_src", got, ref["out"], R.bound(R.k5_forward_k(4)["out"], ref["T"]), form=form)
     assert plus_zero_where_all_masked(got, ref["count"]) and float(np.abs(ref["out"]).max()) > 0
     assert torch.equal(got, run_levels([padded])[0])
+    for grid_f64 in (True, False):      # the rows as a CUDA tensor, read at run time: the bits of the rows passed by value
+        host = got if grid_f64 else ops.warp_fuse_levels_src([level], [shape], padded["rows"], False, [padded["crop"]])[0]
+        devr = ops.warp_fuse_levels_src([level], [shape], rows_arg(padded["rows"], True), grid_f64, [padded["crop"]])[0]
+        assert torch.equal(devr, host), grid_f64
 
 
 # ======================================================================================================= split form
@@ -284,6 +288,7 @@ def test_warp_agents_pm_ragged():
             got = ops.warp_agents_pm(dev(feats), fx["rows"], grid_f64)
             want = R.sample_f32(feats, fx["rows"], grid_f64).transpose(0, 2, 3, 1)
             assert got.shape == want.shape and torch.equal(got.cpu(), torch.from_numpy(np.ascontiguousarray(want)))
+            assert torch.equal(ops.warp_agents_pm(dev(feats), rows_arg(fx["rows"], True), grid_f64), got)     # rows read on the device
 
 
 # ======================================================================================================= repeatability

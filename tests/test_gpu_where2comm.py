@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from heal_amd import _capi, ops
+from tests.coalign_refs import device_rows_case
 from tests.golden.w2c_fill import fill_w2c
 from tests.test_gpu_disconet import shift_rows
 from tests.test_where2comm_cpu import (CASES, TOL, WHO_CASES, case_inputs, e2e_data, e2e_hypes, make_w2c, make_who, rel_err)
@@ -177,6 +178,18 @@ def test_warp_mha_fuse_odd_map_against_fp64():
           f"logits {err_l:.3e} (torch fp32 {float((l32.cpu().double() - want_l).abs().max()) / float(want_l.abs().max()):.3e}), "
           f"warped ego {err_e:.3e} (torch fp32 {float((ego32.cpu().double() - want_ego).abs().max()):.3e})")
     assert err_hip <= 4 * err_t32, (err_hip, err_t32)
+
+
+@pytest.mark.parametrize("grid_f64", [True, False])
+def test_warp_mha_fuse_device_rows_equal_host_rows(grid_f64):
+    """The rows as a float64 CUDA tensor (read by the kernel at run time) give the bits of the rows passed by value."""
+    n, H, W, rows = device_rows_case()
+    fx = mha_fixture(n, 8, 2, H, W, seed=21)
+    with torch.no_grad():
+        host = ops.warp_mha_fuse(*fx, 2, rows, grid_f64, return_logits=True)
+        devr = ops.warp_mha_fuse(*fx, 2, torch.from_numpy(rows).to(DEV), grid_f64, return_logits=True)
+    assert len(host) == 3 and all(float(t.abs().max()) > 0 for t in host)
+    assert all(torch.equal(d, h) for d, h in zip(devr, host))
 
 
 def test_warp_mha_fuse_rejects_bad_inputs():
