@@ -23,6 +23,7 @@ HEADER_CENTER = os.path.join(os.path.dirname(HERE), "include", "heal_amd_center.
 HEADER_COMM = os.path.join(os.path.dirname(HERE), "include", "heal_amd_comm.h")
 HEADER_UNC = os.path.join(os.path.dirname(HERE), "include", "heal_amd_unc.h")
 HEADER_ROI = os.path.join(os.path.dirname(HERE), "include", "heal_amd_roi.h")
+HEADER_ALIGN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_align.h")
 
 _lib = None
 
@@ -160,6 +161,15 @@ def signatures_roi():
         return parse_prototypes(f.read())
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_align():
+    """{name: (restype, argtypes)} of include/heal_amd_align.h: the SDTA aligner's cross-covariance attention folded into one
+    pointwise weight per image (heal_xca_weights with its host-side support, parts and workspace rules).  Every build exports
+    them; like signatures_ext() they are outside the versioned inference ABI."""
+    with open(HEADER_ALIGN) as f:
+        return parse_prototypes(f.read())
+
+
 def declared_symbols(experimental=False):
     """Function names declared in include/heal_amd.h (the shipped C ABI), or with experimental=True in
     include/heal_amd_experimental.h."""
@@ -196,7 +206,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**signatures(), **signatures_train(), **signatures_ext(), **signatures_train_attn(),
                                   **signatures_train_bn(), **signatures_train_warp(), **signatures_center(),
-                                  **signatures_comm(), **signatures_unc(), **signatures_roi()}.items():
+                                  **signatures_comm(), **signatures_unc(), **signatures_roi(), **signatures_align()}.items():
             if not hasattr(L, name):
                 continue  # declared but not built yet -> surfaces in call() / the symbol test
             f = getattr(L, name)

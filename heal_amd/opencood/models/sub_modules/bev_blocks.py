@@ -649,17 +649,21 @@ class ConvNeXt(nn.Module):
 
 
 class AlignNet(nn.Module):
-    """feature_alignnet.py:12-39; the HEAL configs use 'identity' and 'convnext'."""
+    """feature_alignnet.py:12-39; the HEAL configs use 'identity' and 'convnext'.  The other six aligners live in aligners.py."""
 
     def __init__(self, args):
         super().__init__()
+        from heal_amd.opencood.models.sub_modules import aligners        # (it imports this module)
         name = args["core_method"]
         if name == "identity":
             self.channel_align = nn.Identity()
         elif name == "convnext":
             self.channel_align = ConvNeXt(args["args"])
+        elif name in aligners.ALIGNERS:
+            self.channel_align = aligners.ALIGNERS[name](args["args"])
         else:
-            raise NotImplementedError(f"aligner '{name}' is outside the hot-path scope (SURVEY 2, row 6)")
+            raise NotImplementedError(f"aligner '{name}': the reference has identity, convnext, "
+                                      f"{', '.join(sorted(aligners.ALIGNERS))}")
         if args.get("spatial_align", False):
             raise NotImplementedError
 

@@ -3207,9 +3207,13 @@ def _out_like(out, shape, device, who, name="out"):
     return _out_or_empty(out, shape, device, f"{who} ({name})" if name != "out" else who)
 
 
-def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixel_major=False, out=None, roi=None):
+def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixel_major=False, out=None, roi=None,
+            fragments=None):
     """Pointwise convolution with fused prologue / epilogue: act(W (in_scale . x) + bias (+ residual));
     act 0 none | 1 ReLU | 2 SiLU; stride 1 | 2.  x [n,Cin,H,W] f32 cuda, w [Cout,Cin,1,1], in_scale [n,Cin].
+    fragments: the conv1x1_fragments layout of `w`, made by the caller (xca_fragments).  For a weight that a kernel wrote on the
+    device during this forward: such a tensor has no parameter behind it and no version that moves when it is rewritten, so it must
+    not go through the weight-derived cache.  The launch is then heal_conv1x1 itself (no split-K, no opt-in kernel).
     pixel_major=True: the result comes back as [n, Ho*Wo, Cout] (a pixel's channels contiguous) instead of NCHW.
     out: optional destination (NCHW result only), e.g. the batch slice of a stage's output that an agent chunk fills.
     roi: per-image output boxes [(y0, y1, x0, x1)] * n (heal_conv1x1_roi; NCHW result only): 64-pixel tiles that hold no pixel of
@@ -3225,7 +3229,7 @@ def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixe
         raise _capi.HealAmdError(f"conv1x1: unsupported shape Cin={cin} Cout={cout} HxW={H}x{W} stride={stride}")
     if (out is not None or roi is not None) and pixel_major:
         raise _capi.HealAmdError("conv1x1: `out` and `roi` are for the NCHW result")
-    nprod = arith_products()
+    nprod = arith_products() if fragments is None else 0
     if (nprod and stride == 1 and not pixel_major and in_scale is None and w.dtype == torch.float32
             and _capi.query("heal_conv1x1_split_supported", cin, cout, H, W)):
         y = _out_or_empty(out, (n, cout, H, W), x.device, "conv1x1")
@@ -3239,7 +3243,7 @@ def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixe
             _capi.call("heal_conv1x1_split", _ptr(x), _ptr(frag), _ptr(bias) if bias is not None else None,
                        _ptr(residual) if residual is not None else None, n, cin, cout, H, W, int(act), nprod, _ptr(y), _stream())
         return y
-    if (stride == 1 and not pixel_major and in_scale is None and conv1x1_tiled_ok(n, cin, cout, H * W)
+    if (fragments is None and stride == 1 and not pixel_major and in_scale is None and conv1x1_tiled_ok(n, cin, cout, H * W)
             and w.dtype == torch.float32):
         y = _out_or_empty(out, (n, cout, H, W), x.device, "conv1x1")
         if residual is not None:
@@ -3252,7 +3256,12 @@ def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixe
             _capi.call("heal_conv1x1_tiled", _ptr(x), _ptr(wr), _ptr(bias) if bias is not None else None,
                        _ptr(residual) if residual is not None else None, n, cin, cout, H, W, int(act), 0, 0, 0, _ptr(y), _stream())
         return y
-    frag = conv1x1_fragments(w)
+    if fragments is None:
+        frag = conv1x1_fragments(w)
+    else:
+        frag = _need(fragments, torch.float32, "fragments")
+        if frag.numel() != ((cout + 63) // 64 * 64) * ((cin + 31) // 32 * 32):
+            raise _capi.HealAmdError(f"conv1x1: `fragments` has {frag.numel()} elements for a {cout} x {cin} weight")
     if pixel_major:
         if residual is not None or cout % 4 != 0:
             raise _capi.HealAmdError("conv1x1: pixel-major output needs Cout % 4 == 0 and takes no residual")
@@ -3265,7 +3274,7 @@ def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixe
             raise _capi.HealAmdError("conv1x1: residual shape mismatch")
     if in_scale is not None:
         in_scale = _need(in_scale.reshape(n, cin), torch.float32, "in_scale")
-    ksplit = conv1x1_ksplit(n, cin, cout, H * W) if (stride == 1 and not pixel_major) else 1
+    ksplit = conv1x1_ksplit(n, cin, cout, H * W) if (stride == 1 and not pixel_major and fragments is None) else 1
     if ksplit > 1:
         nbytes = _capi.query("heal_conv1x1_splitk_workspace", n, cout, H, W, ksplit)
         ws = _workspace("conv1x1_splitk", nbytes, x.device)
@@ -4037,6 +4046,72 @@ def layernorm_nchw(x, gamma, beta, eps):
     _capi.call("heal_layernorm_nchw", _ptr(x), _ptr(_need(gamma, torch.float32, "gamma")),
                _ptr(_need(beta, torch.float32, "beta")), n, C, H * W, float(eps), _ptr(y), _stream())
     return y
+
+
+def align_fused_enabled():
+    """HEAL_ALIGN_FUSED as the library reads it (heal_align_fused_enabled: the variable is one of the library's own, declared as such
+    in heal_amd/switches.py): False for "0" -- the aligners of AlignNet beyond ConvNeXt (sdta, resnet1x1, resnet3x3, scaligner, cbam,
+    fanet) then run as the reference's torch composition on the device (A/B)."""
+    v = int(_capi.lib().heal_align_fused_enabled())
+    if v < 0:
+        raise _capi.HealAmdError("HEAL_ALIGN_FUSED is not a valid setting: expected 0 or 1")
+    return v == 1
+
+
+XCA_CALLS = {"weights": 0}      # heal_xca_weights calls so far (tests: the gradient path must not take the kernel)
+
+
+def xca_supported(C, heads, N):
+    """Shapes heal_xca_weights takes: d = C / heads in {16, 32}, 16-byte pixel rows (N % 4 == 0), N >= 64."""
+    return bool(_capi.lib().heal_xca_supported(int(C), int(heads), int(N)))
+
+
+def xca_parts(B, heads, N):
+    """(parts, pixels of one part) of the Gram pass for this grid (heal_xca_parts / heal_xca_range): the summation shape the
+    tests' error bound needs."""
+    return int(_capi.lib().heal_xca_parts(int(B), int(heads), int(N))), int(_capi.lib().heal_xca_range(int(B), int(heads), int(N)))
+
+
+def xca_weights(qkv, temperature, proj_w_scaled, heads, want_attn=False, want_stats=False):
+    """Cross-covariance attention folded into one pointwise weight per image (heal_xca_weights, include/heal_amd_align.h).
+    qkv [B, 3C, H, W] (or [B, 3C, N]) f32 cuda, channel s C + h d + i = row i of head h of q / k / v; temperature [heads] (any
+    trailing 1-dims); proj_w_scaled [C, C] = gamma_xca (.) W_proj.
+    -> (W [B, C, C] with x + gamma_xca * xca(.) = x + W[b] v_b + gamma_xca (.) b_proj,
+        A [B, heads, d, d] or None (want_attn),
+        stats [B, heads, d d + 2 d] or None (want_stats): the Gram matrix, then the squared norms of the q rows and of the k rows)."""
+    who = "xca_weights"
+    qkv = _need(qkv, torch.float32, "qkv")
+    if qkv.dim() not in (3, 4) or int(qkv.shape[1]) % 3:
+        raise _capi.HealAmdError(f"{who}: qkv must be [B, 3C, H, W] or [B, 3C, N], got {tuple(qkv.shape)}")
+    B, C = int(qkv.shape[0]), int(qkv.shape[1]) // 3
+    N = int(qkv.numel()) // max(B * 3 * C, 1)
+    heads = int(heads)
+    if heads < 1 or not xca_supported(C, heads, N) or not 1 <= B <= 65535:
+        raise _capi.HealAmdError(f"{who}: unsupported shape B={B} C={C} heads={heads} N={N}: d = C / heads must be 16 or 32, "
+                                 "N % 4 == 0 and N >= 64")
+    temperature = _need(temperature.reshape(-1), torch.float32, "temperature")
+    pw = _need(proj_w_scaled, torch.float32, "proj_w_scaled")
+    if temperature.numel() != heads or tuple(pw.shape) != (C, C) or temperature.device != qkv.device or pw.device != qkv.device:
+        raise _capi.HealAmdError(f"{who}: temperature must hold {heads} values and proj_w_scaled be [{C}, {C}] on {qkv.device}")
+    d, dev = C // heads, qkv.device
+    W = torch.empty((B, C, C), dtype=torch.float32, device=dev)
+    A = torch.empty((B, heads, d, d), dtype=torch.float32, device=dev) if want_attn else None
+    stats = torch.empty((B, heads, d * d + 2 * d), dtype=torch.float32, device=dev) if want_stats else None
+    ws = _workspace("xca_weights", _capi.query("heal_xca_workspace", B, C, heads, N), dev)
+    XCA_CALLS["weights"] += 1
+    with _Timed(f"xca_weights_{C}", 2.0 * B * d * C * N, 8.0 * B * C * N, kernel_events=True):
+        _capi.call("heal_xca_weights", _ptr(qkv), _ptr(temperature), _ptr(pw), B, C, heads, N, _ptr(ws), ws.numel(), _ptr(W),
+                   _ptr(A), _ptr(stats), _stream())
+    return W, A, stats
+
+
+def xca_fragments(W):
+    """[B, C, C] device-made pointwise weights (xca_weights) -> their conv1x1_fragments layout in one copy: [B, C/16, C/16, 4, 16, 4],
+    element [b][mt][kc][q][r][j] = W[b][16 mt + r][16 kc + 4 j + q] (lane 16 q + r, four k-steps per lane).  C % 64 == 0 (no padding)."""
+    B, C = int(W.shape[0]), int(W.shape[1])
+    if C % 64 or int(W.shape[2]) != C:
+        raise _capi.HealAmdError(f"xca_fragments: weights must be [B, C, C] with C % 64 == 0, got {tuple(W.shape)}")
+    return W.reshape(B, C // 16, 16, C // 16, 4, 4).permute(0, 1, 3, 5, 2, 4).contiguous()
 
 
 def se_gate(mean, w_reduce, b_reduce, w_expand, b_expand, scale=1.0, tiles=1):

@@ -91,6 +91,7 @@ SWITCHES = {
     "HEAL_COLLECTIVE": Switch("choice", "gather", ("gather", "all_gather", "p2p"), "python"),
     "HEAL_SPLIT": Switch("choice", "levels", ("levels", "compressed"), "python"),
     # csrc/
+    "HEAL_ALIGN_FUSED": _LIBRARY,       # heal_align_fused_enabled(); the aligners ask the library (ops.align_fused_enabled)
     "HEAL_C1_CFG": _LIBRARY,
     "HEAL_C3_TH": _LIBRARY,
     "HEAL_CANVAS_CG": _LIBRARY,
