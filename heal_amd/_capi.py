@@ -24,6 +24,7 @@ HEADER_COMM = os.path.join(os.path.dirname(HERE), "include", "heal_amd_comm.h")
 HEADER_UNC = os.path.join(os.path.dirname(HERE), "include", "heal_amd_unc.h")
 HEADER_ROI = os.path.join(os.path.dirname(HERE), "include", "heal_amd_roi.h")
 HEADER_ALIGN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_align.h")
+HEADER_SSFA = os.path.join(os.path.dirname(HERE), "include", "heal_amd_ssfa.h")
 
 _lib = None
 
@@ -170,6 +171,15 @@ def signatures_align():
         return parse_prototypes(f.read())
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_ssfa():
+    """{name: (restype, argtypes)} of include/heal_amd_ssfa.h: the dense neck of the SECOND + SSFA detectors -- the 3x3 stride-2
+    transposed convolution (heal_deconv3x3_s2) and the attention blend (heal_ssfa_blend) with their host-side support rules, and
+    the reader of HEAL_SSFA_FUSED.  Every build exports them; like signatures_ext() they are outside the versioned inference ABI."""
+    with open(HEADER_SSFA) as f:
+        return parse_prototypes(f.read())
+
+
 def declared_symbols(experimental=False):
     """Function names declared in include/heal_amd.h (the shipped C ABI), or with experimental=True in
     include/heal_amd_experimental.h."""
@@ -206,7 +216,8 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**signatures(), **signatures_train(), **signatures_ext(), **signatures_train_attn(),
                                   **signatures_train_bn(), **signatures_train_warp(), **signatures_center(),
-                                  **signatures_comm(), **signatures_unc(), **signatures_roi(), **signatures_align()}.items():
+                                  **signatures_comm(), **signatures_unc(), **signatures_roi(), **signatures_align(),
+                                  **signatures_ssfa()}.items():
             if not hasattr(L, name):
                 continue  # declared but not built yet -> surfaces in call() / the symbol test
             f = getattr(L, name)

@@ -78,6 +78,7 @@ def _deps():
     hdrs.append(os.path.join(inc, "heal_amd_unc.h"))        # the uncertainty detector's criterion and decode: part of every build
     hdrs.append(os.path.join(inc, "heal_amd_roi.h"))        # the region-of-interest convolution launches: part of every build
     hdrs.append(os.path.join(inc, "heal_amd_align.h"))      # the aligners' cross-covariance attention weights: part of every build
+    hdrs.append(os.path.join(inc, "heal_amd_ssfa.h"))       # SSFA's transposed convolution and attention blend: part of every build
     if EXPERIMENTAL:
         hdrs.append(os.path.join(inc, "heal_amd_experimental.h"))
     return hdrs

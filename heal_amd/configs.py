@@ -8,7 +8,7 @@ import copy
 
 import yaml
 
-from heal_amd.opencood.hypes_yaml.yaml_utils import load_general_params, load_point_pillar_params
+from heal_amd.opencood.hypes_yaml.yaml_utils import load_general_params, load_point_pillar_params, load_second_params
 
 FULL_RANGE = [-102.4, -102.4, -3, 102.4, 102.4, 1]
 ANCHOR_YAW = [0, 90]
@@ -340,6 +340,47 @@ def lidar_uncertainty(lidar_range=FULL_RANGE, dim=3, dir_head=True):
     if dir_head:
         h["loss"]["args"]["dir"] = base["dir"]
     return load_general_params(h)
+
+
+SSFA_RANGE = [-140.8, -40, -3, 140.8, 40, 1]
+
+
+def second_ssfa(lidar_range=SSFA_RANGE, uncertainty_dim=None, dir_head=True):
+    """The SECOND + SSFA detectors.  uncertainty_dim None: core_method second_ssfa (second_ssfa.py:15-57) with CIA-SSD's `head` block
+    (box, class, IoU and, with dir_head, direction maps) and the VoxelPostprocessor, whose post_process rescores with `iou_preds`.
+    uncertainty_dim 2 | 3 | 7: core_method second_ssfa_uncertainty (second_ssfa_uncertainty.py:16-86), the SECOND flavour of
+    CoAlign's first stage, with `anchor_num` / `uncertainty_dim` / `dir_args`, point_pillar_uncertainty_loss and the
+    UncertaintyVoxelPostprocessor as in lidar_uncertainty.  0.1 m voxels, the BEV map at stride 8 (100 x 352 for the default
+    +-140.8 m x +-40 m range).  The reference ships no YAML for either model: the KEY NAMES are the ones its code reads."""
+    if uncertainty_dim is not None:
+        h = lidar_uncertainty(lidar_range, uncertainty_dim, dir_head)
+    else:
+        h = _common(lidar_range, 1)
+        if not dir_head:
+            h["postprocess"].pop("dir_args")
+    h["preprocess"]["args"] = {"voxel_size": [0.1, 0.1, 0.1], "max_points_per_voxel": 5, "max_voxel_train": 36000,
+                               "max_voxel_test": 70000}
+    h["postprocess"]["anchor_args"]["feature_stride"] = 8
+    h["yaml_parser"] = "load_second_params"
+    args = {"lidar_range": list(lidar_range), "voxel_size": [0.1, 0.1, 0.1], "mean_vfe": {"num_point_features": 4},
+            "spconv": {"num_features_in": 4, "num_features_out": 64}, "map2bev": {"feature_num": 128},
+            "ssfa": {"feature_num": 128}}
+    if uncertainty_dim is not None:
+        args.update({"anchor_num": 2, "uncertainty_dim": uncertainty_dim})
+        if dir_head:
+            args["dir_args"] = copy.deepcopy(DIR_ARGS)
+        h["name"] = "heal_amd_second_ssfa_uncertainty"
+        h["model"] = {"core_method": "second_ssfa_uncertainty", "args": args}
+    else:
+        args["head"] = {"num_input": 128, "num_pred": 14, "num_cls": 2, "num_iou": 2, "use_dir": bool(dir_head), "num_dir": 4}
+        h["name"] = "heal_amd_second_ssfa"
+        h["model"] = {"core_method": "second_ssfa", "args": args}
+        h["loss"]["core_method"] = "point_pillar_loss"
+        for k in ("depth", "pyramid"):
+            h["loss"]["args"].pop(k)
+        if not dir_head:
+            h["loss"]["args"].pop("dir")
+    return load_second_params(h)
 
 
 def lidar_centerpoint_where2comm(agg="ATTEN", multi_scale=True, backbone="resnet", communication=True, lidar_range=FULL_RANGE,

@@ -193,7 +193,7 @@ class VoxelPostprocessor:
         """Late fusion (voxel_postprocessor.py:277-405 with several cavs): every cav's candidates are decoded, projected
         with its own transformation matrix and pooled before the filters and ONE rotated NMS.  Same steps, in the
         reference's order, as tensor ops on the device + heal_nms_quads; the single-cav hot path above stays on the
-        fused kernel."""
+        fused kernel.  Also the path of every output with an `iou_preds` head, one cav or several."""
         from heal_amd.opencood.utils import box_utils
         from heal_amd.opencood.utils.common_utils import limit_period
         boxes3d_list, scores_list = [], []
@@ -204,8 +204,8 @@ class VoxelPostprocessor:
             cls = out['cls_preds'] if 'cls_preds' in out else out['psm']
             reg = out['reg_preds'] if 'reg_preds' in out else out['rm']
             dirp = out.get('dir_preds', out.get('dm'))
-            if 'iou_preds' in out:
-                raise NotImplementedError("iou_preds rescoring is not used by the HEAL configs")
+            if dirp is not None and dirp.dim() != 4:     # cia_ssd_utils.Head without use_dir: a zero tensor [N, 1, 2], no map
+                dirp = None
             prob = torch.sigmoid(cls.permute(0, 2, 3, 1)).reshape(1, -1)
             if reg.dim() == 4:      # anchor-based: PointPillars, SECOND
                 box3d = self.delta_to_boxes3d(reg, cav['anchor_box'] if isinstance(cav['anchor_box'], torch.Tensor)
@@ -223,6 +223,10 @@ class VoxelPostprocessor:
                 rot = limit_period(boxes3d[..., 6] - dir_args['dir_offset'], 0, period)
                 boxes3d[..., 6] = rot + dir_args['dir_offset'] + period * labels.to(dirp.dtype)
                 boxes3d[..., 6] = limit_period(boxes3d[..., 6], 0.5, 2 * np.pi)
+            if 'iou_preds' in out and len(boxes3d) != 0:      # IoU-aware rescoring (:338-342): score * ((iou + 1) / 2) ** 4
+                iou = torch.sigmoid(out['iou_preds'].permute(0, 2, 3, 1).contiguous()).reshape(1, -1)
+                iou = (torch.clamp(iou, min=0.0, max=1.0) + 1) * 0.5
+                scores = scores * torch.pow(iou[0][mask], 4)
             if len(boxes3d) != 0:
                 corners = box_utils.boxes_to_corners_3d(boxes3d, order=self.params['order'])
                 tfm = cav['transformation_matrix']
@@ -319,8 +323,8 @@ class VoxelPostprocessor:
         cls = out['cls_preds'] if 'cls_preds' in out else out['psm']
         reg = out['reg_preds'] if 'reg_preds' in out else out['rm']
         dirp = out.get('dir_preds', out.get('dm'))
-        if 'iou_preds' in out:
-            raise NotImplementedError("iou_preds rescoring is not used by the HEAL configs")
+        if 'iou_preds' in out:      # an IoU head (second_ssfa): the tensor path, which rescores after the direction correction
+            return self._post_process_multi(data_dict, output_dict)
         tfm = cav['transformation_matrix']
         tfm = tfm.detach().cpu().numpy() if isinstance(tfm, torch.Tensor) else np.asarray(tfm)
         dir_args = self.params.get('dir_args', {'dir_offset': 0.7853, 'num_bins': 2})

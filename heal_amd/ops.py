@@ -4114,6 +4114,120 @@ def xca_fragments(W):
     return W.reshape(B, C // 16, 16, C // 16, 4, 4).permute(0, 1, 3, 5, 2, 4).contiguous()
 
 
+def ssfa_fused_enabled():
+    """HEAL_SSFA_FUSED as the library reads it (heal_ssfa_fused_enabled: the variable is one of the library's own, declared as such
+    in heal_amd/switches.py): False for "0" -- SSFA then runs as the reference's torch composition on the device (A/B)."""
+    v = int(_capi.lib().heal_ssfa_fused_enabled())
+    if v < 0:
+        raise _capi.HealAmdError("HEAL_SSFA_FUSED is not a valid setting: expected 0 or 1")
+    return v == 1
+
+
+SSFA_CALLS = {"deconv": 0, "blend": 0}      # kernel calls so far (tests: refusals launch nothing, the gradient path takes neither)
+
+
+def deconv3x3_s2_supported(cin, cout, H, W):
+    """Shapes heal_deconv3x3_s2 takes: cin and cout multiples of 32 in 32 .. 2048, any H, W >= 1 (up to 65535 tiles of 8 x 16)."""
+    return bool(_capi.lib().heal_deconv3x3_s2_supported(int(cin), int(cout), int(H), int(W)))
+
+
+def _deconv3x3_s2_pack(w):
+    cin, cout = int(w.shape[0]), int(w.shape[1])
+    return (w.detach().reshape(cin // 8, 2, 4, cout // 16, 16, 9).permute(3, 0, 5, 2, 4, 1).contiguous()
+            .reshape(cout // 16, cin // 8, 9, 64, 2))
+
+
+def deconv3x3_s2_fragments(w):
+    """A ConvTranspose2d weight [Cin, Cout, 3, 3] in heal_deconv3x3_s2's fragment order [Cout/16, Cin/8, 9, 64, 2]: element
+    [mt][kc][3 ky + kx][lane][j] = w[8 kc + 4 j + lane // 16][16 mt + lane % 16][ky][kx].  Cached per weight (heal_amd.derived)."""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or int(w.shape[0]) % 8 or int(w.shape[1]) % 16:
+        raise _capi.HealAmdError(f"deconv3x3_s2_fragments: weight must be [Cin % 8 == 0, Cout % 16 == 0, 3, 3], got {tuple(w.shape)}")
+    return _derived("deconv3x3_s2_fragments", (w,), lambda: _deconv3x3_s2_pack(w))
+
+
+def deconv3x3_s2(x, w_frag_or_w, bias=None, relu=True, residual=None):
+    """ConvTranspose2d(k 3, stride 2, padding 1, output_padding 1) with fused bias, ReLU and residual (heal_deconv3x3_s2,
+    include/heal_amd_ssfa.h): x [n,Cin,H,W] f32 cuda; the weight [Cin,Cout,3,3] or its deconv3x3_s2_fragments; bias [Cout];
+    residual [n,R,2H,2W], added AFTER the ReLU to the first R <= Cout output channels -> [n,Cout,2H,2W]."""
+    who = "deconv3x3_s2"
+    x = _need(x, torch.float32, "x")
+    if x.dim() != 4:
+        raise _capi.HealAmdError(f"{who}: x must be [n, Cin, H, W], got {tuple(x.shape)}")
+    n, cin, H, W = (int(v) for v in x.shape)
+    w = w_frag_or_w
+    if not isinstance(w, torch.Tensor) or w.dim() not in (4, 5):
+        raise _capi.HealAmdError(f"{who}: the weight must be [Cin, Cout, 3, 3] or its fragments [Cout/16, Cin/8, 9, 64, 2]")
+    if w.dim() == 4:
+        if int(w.shape[0]) != cin or tuple(w.shape[2:]) != (3, 3):
+            raise _capi.HealAmdError(f"{who}: weight {tuple(w.shape)} does not fit the input {tuple(x.shape)}")
+        cout = int(w.shape[1])
+    else:
+        cout = 16 * int(w.shape[0])
+        if tuple(w.shape[1:]) != (cin // 8, 9, 64, 2) or cin % 8:
+            raise _capi.HealAmdError(f"{who}: fragments {tuple(w.shape)} do not fit the input {tuple(x.shape)}")
+    if not deconv3x3_s2_supported(cin, cout, H, W) or not 1 <= n <= 65535:
+        raise _capi.HealAmdError(f"{who}: unsupported shape n={n} Cin={cin} Cout={cout} HxW={H}x{W}: Cin and Cout must be "
+                                 "multiples of 32 in 32 .. 2048")
+    frag = _need(deconv3x3_s2_fragments(w) if w.dim() == 4 else w, torch.float32, "weight")
+    bias = _need_bias(bias, cout, who)
+    res_channels = 0
+    if residual is not None:
+        residual = _need(residual, torch.float32, "residual")
+        res_channels = int(residual.shape[1]) if residual.dim() == 4 else -1
+        if (residual.dim() != 4 or tuple(residual.shape) != (n, res_channels, 2 * H, 2 * W) or not 1 <= res_channels <= cout
+                or residual.device != x.device):
+            raise _capi.HealAmdError(f"{who}: residual {tuple(residual.shape)} must be [{n}, 1 .. {cout}, {2 * H}, {2 * W}] "
+                                     f"on {x.device}")
+    if frag.device != x.device or (bias is not None and bias.device != x.device):
+        raise _capi.HealAmdError(f"{who}: weight and bias must be on {x.device}")
+    y = torch.empty((n, cout, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
+    with _Timed(f"deconv3x3_s2_{cin}_{cout}", 2.0 * 9 * n * cin * cout * H * W,
+                4.0 * n * (cin * H * W + (cout + res_channels) * 4 * H * W), kernel_events=True):
+        _capi.call("heal_deconv3x3_s2", _ptr(x), _ptr(frag), _ptr(bias), _ptr(residual), res_channels, n, cin, cout, H, W,
+                   int(bool(relu)), _ptr(y), _stream())
+    SSFA_CALLS["deconv"] += 1
+    return y
+
+
+def ssfa_blend_supported(C, HW):
+    """Shapes heal_ssfa_blend takes: C in {64, 128}, 16-byte pixel rows (HW % 4 == 0)."""
+    return bool(_capi.lib().heal_ssfa_blend_supported(int(C), int(HW)))
+
+
+def ssfa_blend(a, b, wa, ba, wb, bb, want_weights=False):
+    """SSFA's two-way attention in one pass (heal_ssfa_blend, include/heal_amd_ssfa.h): a, b [n,C,H,W] f32 cuda; wa, wb [C] (any
+    trailing 1-dims) and ba, bb (a one-element device tensor, or a number) the w_0 / w_1 convolutions with their BatchNorm folded.
+    pa = 1 / (1 + exp((wb . b + bb) - (wa . a + ba)));  -> a pa + b (1 - pa), and with want_weights also pa [n,1,H,W]."""
+    who = "ssfa_blend"
+    a, b = _need(a, torch.float32, "a"), _need(b, torch.float32, "b")
+    if a.dim() != 4 or a.shape != b.shape or a.device != b.device:
+        raise _capi.HealAmdError(f"{who}: a and b must be two [n, C, H, W] maps of one shape on one device, got "
+                                 f"{tuple(a.shape)} and {tuple(b.shape)}")
+    n, C, H, W = (int(v) for v in a.shape)
+    if not ssfa_blend_supported(C, H * W) or not 1 <= n <= 65535:
+        raise _capi.HealAmdError(f"{who}: unsupported shape n={n} C={C} HxW={H}x{W}: C must be 64 or 128 and H W a multiple of 4")
+    vec = []
+    for t, name in ((wa, "wa"), (wb, "wb")):
+        t = _need(t, torch.float32, name).reshape(-1)
+        if t.numel() != C or t.device != a.device:
+            raise _capi.HealAmdError(f"{who}: {name} must hold {C} values on {a.device}")
+        vec.append(t)
+    for t, name in ((ba, "ba"), (bb, "bb")):
+        if not isinstance(t, torch.Tensor):
+            t = torch.full((1,), float(t), dtype=torch.float32, device=a.device)
+        t = _need(t, torch.float32, name).reshape(-1)
+        if t.numel() != 1 or t.device != a.device:
+            raise _capi.HealAmdError(f"{who}: {name} must be one value on {a.device}")
+        vec.append(t)
+    out = torch.empty_like(a)
+    pa = torch.empty((n, 1, H, W), dtype=torch.float32, device=a.device) if want_weights else None
+    with _Timed(f"ssfa_blend_{C}", 6.0 * n * C * H * W, 12.0 * n * C * H * W, kernel_events=True):
+        _capi.call("heal_ssfa_blend", _ptr(a), _ptr(b), _ptr(vec[0]), _ptr(vec[1]), _ptr(vec[2]), _ptr(vec[3]), n, C, H * W,
+                   _ptr(out), _ptr(pa), _stream())
+    SSFA_CALLS["blend"] += 1
+    return (out, pa) if want_weights else out
+
+
 def se_gate(mean, w_reduce, b_reduce, w_expand, b_expand, scale=1.0, tiles=1):
     """Squeeze-excite gate: mean [n,C] (any trailing 1-dims), w_reduce [S,C,1,1], w_expand [C,S,1,1] -> gate [n,C].
     tiles = T, scale = 1/(H*W): `mean` holds the per-tile sums [n,C,T] of depthwise_conv(channel_sums=True)."""

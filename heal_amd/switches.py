@@ -107,6 +107,7 @@ SWITCHES = {
     "HEAL_PFN_1PW": _LIBRARY,
     "HEAL_PS_DBG": _LIBRARY,
     "HEAL_PYRAMID_ROI": _LIBRARY,       # heal_roi_enabled(); the lean walk asks the library (ops.pyramid_roi_enabled)
+    "HEAL_SSFA_FUSED": _LIBRARY,        # heal_ssfa_fused_enabled(); SSFA asks the library (ops.ssfa_fused_enabled)
     "HEAL_SPLIT_DBG": _LIBRARY,
     "HEAL_SPLIT_TILE": _LIBRARY,
     "HEAL_SP_CONV": _LIBRARY,
