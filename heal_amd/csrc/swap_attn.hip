@@ -5,126 +5,55 @@
 // dilated grid (grid mode: pixel (w1 H / ws + x, w2 W / ws + y)), in the reference's agent-major token order (l w1 w2).  Keys of
 // agents >= n_valid are masked to -inf by the reference (Regroup's padding); queries are not masked.
 //
-// Same transposed MFMA scheme as k_window_attn (window_attn.hip): S^T = K Q^T with K of the group in LDS and Q from global, the
+// The transposed MFMA scheme and its blocks are in attn_tiles.h: S^T = K Q^T with K of the group in LDS and Q from global, the
 // scores of one query in one lane column, the unnormalised probabilities used as they lie as the B operand of O^T = V^T P^T.
 // With ws = 4 a 16-key MFMA tile is exactly one agent's 16 keys: a masked agent is a whole key tile that is neither loaded nor
 // multiplied, which is exactly the -inf semantics (exp(-inf) = 0) -- and leaves whatever its K / V hold out of the result.
 // One block per (group, head) with one wave per agent: wave l owns the 16 queries of agent l.
-#include "common.h"
+#include "attn_tiles.h"
 #include "../../include/heal_amd.h"
 
 namespace heal {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-constexpr int SWAP_WS = 4;           // window size: 16 tokens per agent and group
+constexpr int SWAP_WS = 4;           // window size: 16 tokens per agent and group (AgentGroupTokens)
 constexpr int SWAP_MAX_AGENTS = HEAL_AGENT_WINDOW_MAX_AGENTS;
 
 template <int L, int D>
 __global__ __launch_bounds__(64 * L) void k_agent_window_attn(
     const float* __restrict__ qkv /*[L,H,W,3,m,D]*/, const float* __restrict__ bias /*[m,T,T] or null*/, int n_valid, int H,
     int W, int m, int grid_mode, float scale, float* __restrict__ out /*[L,H,W,m*D]*/) {
-    constexpr int WS = SWAP_WS, T = 16 * L, NB = D / 16, DQ = D / 4;
-    constexpr int KSTR = D + 4, VSTR = D + 4;            // row strides (words): 16-B aligned; 4 VSTR = 16 (mod 64)
-    __shared__ __attribute__((aligned(16))) float sK[T * KSTR];
-    __shared__ __attribute__((aligned(16))) float sV[T * VSTR];
+    constexpr int WS = SWAP_WS, T = 16 * L, NB = D / 16;
+    constexpr int STR = D + 4;                           // row stride (words) of the LDS tiles (attn_tiles.h)
+    __shared__ __attribute__((aligned(16))) float sK[T * STR];
+    __shared__ __attribute__((aligned(16))) float sV[T * STR];
     const int ngy = W / WS;
     const int gx = blockIdx.x / ngy, gy = blockIdx.x - gx * ngy, h = blockIdx.y;
-    const int sh = H / WS, sw = W / WS;
+    const AgentGroupTokens tok{gx, gy, grid_mode, H, W};
     const int MD = m * D;
     const size_t C3 = (size_t)3 * MD;
-    // token t = (l, w1, w2) of this group -> offset of its row (pixel-major inside agent l's map)
-    auto pix = [&](int t) -> size_t {
-        const int l = t >> 4, w1 = (t >> 2) & 3, w2 = t & 3;
-        const int y = grid_mode ? w1 * sh + gx : gx * WS + w1;
-        const int x = grid_mode ? w2 * sw + gy : gy * WS + w2;
-        return ((size_t)l * H + y) * W + x;
-    };
     const float* base = qkv + (size_t)h * D;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int lk = lane >> 4, ln = lane & 15;
-    // Q of this wave's agent, requested together with K / V; lane (lk, ln): query ln, d = lk * DQ ..
-    float4 qf[DQ / 4];
-    const size_t qpix = pix(wave * 16 + ln);
-    {
-        const float* qp = base + qpix * C3 + lk * DQ;
-#pragma unroll
-        for (int i = 0; i < DQ / 4; ++i) qf[i] = *reinterpret_cast<const float4*>(qp + 4 * i);
-    }
-    // stage K and V of the valid agents only (the masked key tiles are never read)
-    for (int e = threadIdx.x; e < n_valid * 16 * (D / 4); e += 64 * L) {
-        const int t = e / (D / 4), c4 = e - t * (D / 4);
-        const float* row = base + pix(t) * C3;
-        *reinterpret_cast<float4*>(&sK[t * KSTR + c4 * 4]) = *reinterpret_cast<const float4*>(row + MD + c4 * 4);
-        *reinterpret_cast<float4*>(&sV[t * VSTR + c4 * 4]) = *reinterpret_cast<const float4*>(row + 2 * MD + c4 * 4);
-    }
+    // Q of this wave's agent, requested together with K / V
+    float4 qf[NB];
+    const size_t qpix = tok(wave * 16 + ln);
+    load_frag<D>(base + qpix * C3, lk, qf);
+    // K and V of the valid agents only (the masked key tiles are never read)
+    stage_rows<D, 64 * L>(tok, n_valid * 16, base + MD, C3, base + 2 * MD, C3, sK, sV);
     __syncthreads();
-    // ---- S^T = K Q^T: tile cb = the 16 keys of agent cb (rows) x this wave's 16 queries (columns) ------------------------------
     f32x4 s[L];
-#pragma unroll
-    for (int cb = 0; cb < L; ++cb) {
-        s[cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (cb < n_valid) {
-            const float* kp = &sK[(cb * 16 + ln) * KSTR + lk * DQ];
-#pragma unroll
-            for (int i = 0; i < DQ / 4; ++i) {
-                const float4 kf = *reinterpret_cast<const float4*>(kp + 4 * i);
-                s[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.x, qf[i].x, s[cb], 0, 0, 0);
-                s[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.y, qf[i].y, s[cb], 0, 0, 0);
-                s[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.z, qf[i].z, s[cb], 0, 0, 0);
-                s[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.w, qf[i].w, s[cb], 0, 0, 0);
-            }
-        }
-    }
-    // ---- scale, bias, softmax over the valid keys of query ln: this lane's 4 per tile + the other three lane groups ---------------
-    const float* brow = bias ? bias + ((size_t)h * T + wave * 16 + ln) * T + lk * 4 : nullptr;
-    float mx = -INFINITY;
-#pragma unroll
-    for (int cb = 0; cb < L; ++cb) {
-        if (cb < n_valid) {
-            float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (brow) bv = *reinterpret_cast<const float4*>(brow + cb * 16);
-            s[cb][0] = s[cb][0] * scale + bv.x; s[cb][1] = s[cb][1] * scale + bv.y;
-            s[cb][2] = s[cb][2] * scale + bv.z; s[cb][3] = s[cb][3] * scale + bv.w;
-            mx = fmaxf(fmaxf(mx, fmaxf(s[cb][0], s[cb][1])), fmaxf(s[cb][2], s[cb][3]));
-        }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float sum = 0.f;
-#pragma unroll
-    for (int cb = 0; cb < L; ++cb)
-        if (cb < n_valid) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = expf(s[cb][r] - mx);
-                s[cb][r] = e;
-                sum += e;
-            }
-        }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    const float inv = 1.f / sum;
-    // ---- O^T = V^T P^T: reduction step (cb, r) = key cb * 16 + lk * 4 + r; B = the (unnormalised) probabilities as they lie ----------
+    float mx, inv;
+    query_scores<L, D>(sK, qf, bias ? bias + ((size_t)h * T + wave * 16 + ln) * T + lk * 4 : nullptr, scale, n_valid, lk, ln, s, mx, inv);
+    // ---- O^T = V^T P^T over the valid key tiles: B = the (unnormalised) probabilities as they lie ------------------------------------
     f32x4 o[NB];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) o[nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    zero_tiles(o);
 #pragma unroll
     for (int cb = 0; cb < L; ++cb)
         if (cb < n_valid) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float* vp = &sV[(cb * 16 + lk * 4 + r) * VSTR + ln];
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb)
-                    o[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[nb * 16], s[cb][r], o[nb], 0, 0, 0);
-            }
+            for (int r = 0; r < 4; ++r) col_accumulate<D>(sV, cb, r, lk, ln, s[cb][r], o);
         }
-    // ---- D layout of O^T: channels nb * 16 + lk * 4 + {0..3} of query ln -> one 16-B store per tile ---------------------------------
-    float* op = out + qpix * MD + (size_t)h * D + lk * 4;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-        *reinterpret_cast<float4*>(op + nb * 16) = make_float4(o[nb][0] * inv, o[nb][1] * inv, o[nb][2] * inv, o[nb][3] * inv);
+    store_tiles(out + qpix * MD + (size_t)h * D + lk * 4, o, inv);
 }
 
 // out[p, c] = (1 / L) sum_l x[l, p, c]: the agent mean of CoBEVT's mlp_head (Reduce('b m d h w -> b d h w', 'mean'), padded agents

@@ -8,20 +8,19 @@
 //   phase 1, query-owned (the forward's scheme): wave l holds the 16 queries of agent l, recomputes S^T = K Q^T tile by tile, forms
 //     dP^T = V dO^T per key tile, keeps (max, 1 / sum, sum_j P_j dP_j) of its queries in LDS, forms dS^T, adds dS^T to its share of dbias (registers,
 //     the forward's s[cb] layout) and accumulates dQ^T += K^T dS^T;
-//   phase 2, key-owned (k_window_attn_bwd_kv's scheme): wave l < n_valid holds the 16 keys of agent l, rebuilds the P / dS tiles of every
-//     query tile from the statistics and accumulates dV^T += dO^T P and dK^T += Q^T dS; wave l >= n_valid writes the zeros of its
-//     masked agent's dK / dV rows.
+//   phase 2, key-owned (the tile body of k_window_attn_bwd_kv: row_tile, key_tile_accumulate): wave l < n_valid holds the 16 keys of agent l, rebuilds the
+//     P / dS tiles of every query tile from the statistics and accumulates dV^T += dO^T P and dK^T += Q^T dS; wave l >= n_valid writes
+//     the zeros of its masked agent's dK / dV rows.
 // A masked agent is a whole 16-key tile that is neither staged nor multiplied.  Every token belongs to one group: plain stores only.
 // dbias leaves the block once, as a partial of its part; k_sum_parts adds the partials in part order (no atomics: bit-equal runs).
-#include "common.h"
+// The MFMA scheme and the blocks both phases are built from are in attn_tiles.h.
+#include "attn_tiles.h"
 #include "../../include/heal_amd.h"
 #include "../../include/heal_amd_train_attn.h"
 
 namespace heal {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-constexpr int SWAPB_WS = 4;
+constexpr int SWAPB_WS = 4;             // 16 tokens per agent and group (AgentGroupTokens)
 constexpr int SWAPB_BLOCKS = 1024;      // blocks the parts policy aims at: a few per CU at 46 KB of LDS (L = 5) each
 
 template <int L, int D>
@@ -35,16 +34,16 @@ __global__ __launch_bounds__(64 * L) void k_agent_window_attn_bwd(
     const float* __restrict__ gout /*[L,H,W,m*D]*/, int n_valid, int H, int W, int m,
     int grid_mode, float scale, int parts, float* __restrict__ gqkv /*[L,H,W,3,m,D]*/,
     float* __restrict__ gbias_parts /*[parts,m,T,T] (grad_bias itself for one part) or null*/) {
-    constexpr int WS = SWAPB_WS, T = 16 * L, NB = D / 16, DQ = D / 4;
-    constexpr int STR = D + 4;                           // row stride (words): 16-B aligned; 4 STR = 16 (mod 64)
+    constexpr int WS = SWAPB_WS, T = 16 * L, NB = D / 16;
+    constexpr int STR = D + 4;                           // row stride (words) of the LDS tiles (attn_tiles.h)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* sQ = lds;
     float* sK = sQ + T * STR;
     float* sV = sK + T * STR;
     float* sG = sV + T * STR;
     float4* sSt = reinterpret_cast<float4*>(sG + T * STR);      // (max, 1 / sum, sum_j P_j dP_j) of every query
-    const int ngy = W / WS, sh = H / WS, sw = W / WS;
-    const int G = sh * sw;
+    const int ngy = W / WS;
+    const int G = (H / WS) * ngy;
     const int part = blockIdx.x, h = blockIdx.y;
     // contiguous range of this part: G % parts leading parts hold one group more
     const int gbase = G / parts, grem = G - gbase * parts;
@@ -52,30 +51,25 @@ __global__ __launch_bounds__(64 * L) void k_agent_window_attn_bwd(
     const int g1 = g0 + gbase + (part < grem ? 1 : 0);
     const int MD = m * D;
     const size_t C3 = (size_t)3 * MD;
+    const float* qbase = qkv + (size_t)h * D;            // q of this head; k at + MD, v at + 2 MD
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int lk = lane >> 4, ln = lane & 15;
     const int tq = wave * 16 + ln;                       // this lane's token: a query in phase 1, a key in phase 2
     const float* brow = bias ? bias + ((size_t)h * T + tq) * T + lk * 4 : nullptr;        // phase 1: keys cb * 16 + lk * 4 ..
-    const float* bcol = bias ? bias + (size_t)h * T * T + tq : nullptr;                   // phase 2: + query * T
+    const size_t bcol = (size_t)h * T * T + tq;          // phase 2: bias[bcol + query * T]
     f32x4 db[L];
-#pragma unroll
-    for (int cb = 0; cb < L; ++cb) db[cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    zero_tiles(db);
 
     for (int g = g0; g < g1; ++g) {
         const int gx = g / ngy, gy = g - gx * ngy;
-        // token t = (l, w1, w2) of this group -> offset of its row (pixel-major inside agent l's map)
-        auto pix = [&](int t) -> size_t {
-            const int l = t >> 4, w1 = (t >> 2) & 3, w2 = t & 3;
-            const int y = grid_mode ? w1 * sh + gx : gx * WS + w1;
-            const int x = grid_mode ? w2 * sw + gy : gy * WS + w2;
-            return ((size_t)l * H + y) * W + x;
-        };
-        const size_t tpix = pix(tq);
-        // stage Q and dO of every agent, K and V of the valid agents only (the masked key tiles are never read)
+        const AgentGroupTokens tok{gx, gy, grid_mode, H, W};
+        const size_t tpix = tok(tq);
+        // stage Q and dO of every agent, K and V of the valid agents only (the masked key tiles are never read): one walk over the
+        // tokens (two stage_rows calls, one per pair, measured 1 - 2 % slower per launch at L = 5)
         for (int e = threadIdx.x; e < T * (D / 4); e += 64 * L) {
             const int t = e / (D / 4), c4 = e - t * (D / 4);
-            const size_t p = pix(t);
-            const float* row = qkv + p * C3 + (size_t)h * D + c4 * 4;
+            const size_t p = tok(t);
+            const float* row = qbase + p * C3 + c4 * 4;
             *reinterpret_cast<float4*>(&sQ[t * STR + c4 * 4]) = *reinterpret_cast<const float4*>(row);
             *reinterpret_cast<float4*>(&sG[t * STR + c4 * 4]) =
                 *reinterpret_cast<const float4*>(gout + p * MD + (size_t)h * D + c4 * 4);
@@ -87,55 +81,12 @@ __global__ __launch_bounds__(64 * L) void k_agent_window_attn_bwd(
         __syncthreads();
         // ================= phase 1: the 16 queries of agent `wave` =====================================================================
         {
-            float4 qf[DQ / 4], gf[DQ / 4];
-#pragma unroll
-            for (int i = 0; i < DQ / 4; ++i) {
-                qf[i] = *reinterpret_cast<const float4*>(&sQ[tq * STR + lk * DQ + 4 * i]);
-                gf[i] = *reinterpret_cast<const float4*>(&sG[tq * STR + lk * DQ + 4 * i]);
-            }
-            // ---- S^T = K Q^T, scale, bias, softmax over the valid keys: the forward, normalised ------------------------------------
+            float4 qf[NB], gf[NB];
+            load_frag<D>(&sQ[tq * STR], lk, qf);
+            load_frag<D>(&sG[tq * STR], lk, gf);
             f32x4 s[L];
-#pragma unroll
-            for (int cb = 0; cb < L; ++cb) {
-                s[cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (cb < n_valid) {
-                    const float* kp = &sK[(cb * 16 + ln) * STR + lk * DQ];
-#pragma unroll
-                    for (int i = 0; i < DQ / 4; ++i) {
-                        const float4 kf = *reinterpret_cast<const float4*>(kp + 4 * i);
-                        s[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.x, qf[i].x, s[cb], 0, 0, 0);
-                        s[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.y, qf[i].y, s[cb], 0, 0, 0);
-                        s[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.z, qf[i].z, s[cb], 0, 0, 0);
-                        s[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf.w, qf[i].w, s[cb], 0, 0, 0);
-                    }
-                }
-            }
-            float mx = -INFINITY;
-#pragma unroll
-            for (int cb = 0; cb < L; ++cb)
-                if (cb < n_valid) {
-                    float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (brow) bv = *reinterpret_cast<const float4*>(brow + cb * 16);
-                    s[cb][0] = s[cb][0] * scale + bv.x; s[cb][1] = s[cb][1] * scale + bv.y;
-                    s[cb][2] = s[cb][2] * scale + bv.z; s[cb][3] = s[cb][3] * scale + bv.w;
-                    mx = fmaxf(fmaxf(mx, fmaxf(s[cb][0], s[cb][1])), fmaxf(s[cb][2], s[cb][3]));
-                }
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            float sum = 0.f;
-#pragma unroll
-            for (int cb = 0; cb < L; ++cb)
-                if (cb < n_valid) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float e = expf(s[cb][r] - mx);
-                        s[cb][r] = e;
-                        sum += e;
-                    }
-                }
-            sum += __shfl_xor(sum, 16, 64);
-            sum += __shfl_xor(sum, 32, 64);
-            const float inv = 1.f / sum;
+            float mx, inv;
+            query_scores<L, D>(sK, qf, brow, scale, n_valid, lk, ln, s, mx, inv);
             // ---- dP^T = V dO^T per valid key tile, and the row term D = sum_j P_j dP_j = dO . O from these same tiles: what is
             //      subtracted below is the mean of the very values it is subtracted from, so the rows of dS sum to zero to rounding --
             f32x4 dp[L];
@@ -143,26 +94,14 @@ __global__ __launch_bounds__(64 * L) void k_agent_window_attn_bwd(
 #pragma unroll
             for (int cb = 0; cb < L; ++cb)
                 if (cb < n_valid) {
-                    dp[cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                    const float* vp = &sV[(cb * 16 + ln) * STR + lk * DQ];
-#pragma unroll
-                    for (int i = 0; i < DQ / 4; ++i) {
-                        const float4 vf = *reinterpret_cast<const float4*>(vp + 4 * i);
-                        dp[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.x, gf[i].x, dp[cb], 0, 0, 0);
-                        dp[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.y, gf[i].y, dp[cb], 0, 0, 0);
-                        dp[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.z, gf[i].z, dp[cb], 0, 0, 0);
-                        dp[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf.w, gf[i].w, dp[cb], 0, 0, 0);
-                    }
+                    dp[cb] = row_tile<D>(sV, cb, lk, ln, gf);
                     dsum += (s[cb][0] * dp[cb][0] + s[cb][1] * dp[cb][1]) + (s[cb][2] * dp[cb][2] + s[cb][3] * dp[cb][3]);
                 }
-            dsum += __shfl_xor(dsum, 16, 64);            // the four lane groups hold four keys of every tile of query ln
-            dsum += __shfl_xor(dsum, 32, 64);
-            dsum *= inv;
+            dsum = lk_sum(dsum) * inv;                   // the four lane groups hold four keys of every tile of query ln
             if (lk == 0) sSt[tq] = make_float4(mx, inv, dsum, 0.f);
             // ---- per valid key tile: dS^T = P^T o (dP^T - D), dQ^T += K^T dS^T -------------------------------------------------------
             f32x4 dq[NB];
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) dq[nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            zero_tiles(dq);
 #pragma unroll
             for (int cb = 0; cb < L; ++cb)
                 if (cb < n_valid) {
@@ -173,100 +112,49 @@ __global__ __launch_bounds__(64 * L) void k_agent_window_attn_bwd(
                         db[cb][r] += ds[r];
                     }
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float* kp = &sK[(cb * 16 + lk * 4 + r) * STR + ln];
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb)
-                            dq[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(kp[nb * 16], ds[r], dq[nb], 0, 0, 0);
-                    }
+                    for (int r = 0; r < 4; ++r) col_accumulate<D>(sK, cb, r, lk, ln, ds[r], dq);
                 }
-            // D layout of dQ^T: channels nb * 16 + lk * 4 + {0..3} of query ln
-            float* gp = gqkv + tpix * C3 + (size_t)h * D + lk * 4;
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-                *reinterpret_cast<float4*>(gp + nb * 16) =
-                    make_float4(dq[nb][0] * scale, dq[nb][1] * scale, dq[nb][2] * scale, dq[nb][3] * scale);
+            store_tiles(gqkv + tpix * C3 + (size_t)h * D + lk * 4, dq, scale);
         }
         __syncthreads();                                 // the statistics of every query are in LDS
-        // ================= phase 2: the 16 keys of agent `wave` ========================================================================
+        // ================= phase 2: the 16 keys of agent `wave` (queries are not masked: every agent's tile) ============================
         {
             float* gk = gqkv + tpix * C3 + MD + (size_t)h * D + lk * 4;
             if (wave < n_valid) {
-                float4 kf[DQ / 4], vf[DQ / 4];
-#pragma unroll
-                for (int i = 0; i < DQ / 4; ++i) {
-                    kf[i] = *reinterpret_cast<const float4*>(&sK[tq * STR + lk * DQ + 4 * i]);
-                    vf[i] = *reinterpret_cast<const float4*>(&sV[tq * STR + lk * DQ + 4 * i]);
-                }
+                float4 kf[NB], vf[NB];
+                load_frag<D>(&sK[tq * STR], lk, kf);
+                load_frag<D>(&sV[tq * STR], lk, vf);
                 f32x4 dk[NB], dv[NB];
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) { dk[nb] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[nb] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+                zero_tiles(dk);
+                zero_tiles(dv);
 #pragma unroll
                 for (int cb = 0; cb < L; ++cb) {
-                    // score and dP tiles of queries cb * 16 .. + 15 (rows) x this wave's 16 keys (columns): lane (lk, ln) holds queries
-                    // cb * 16 + lk * 4 + {0..3} of key ln.  Queries are not masked: every agent's tile.
-                    f32x4 sc = (f32x4){0.f, 0.f, 0.f, 0.f}, dp = (f32x4){0.f, 0.f, 0.f, 0.f};
-                    const float* qp = &sQ[(cb * 16 + ln) * STR + lk * DQ];
-                    const float* gp = &sG[(cb * 16 + ln) * STR + lk * DQ];
-#pragma unroll
-                    for (int i = 0; i < DQ / 4; ++i) {
-                        const float4 qv = *reinterpret_cast<const float4*>(qp + 4 * i);
-                        const float4 gv = *reinterpret_cast<const float4*>(gp + 4 * i);
-                        sc = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.x, kf[i].x, sc, 0, 0, 0);
-                        sc = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.y, kf[i].y, sc, 0, 0, 0);
-                        sc = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.z, kf[i].z, sc, 0, 0, 0);
-                        sc = __builtin_amdgcn_mfma_f32_16x16x4f32(qv.w, kf[i].w, sc, 0, 0, 0);
-                        dp = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.x, vf[i].x, dp, 0, 0, 0);
-                        dp = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.y, vf[i].y, dp, 0, 0, 0);
-                        dp = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.z, vf[i].z, dp, 0, 0, 0);
-                        dp = __builtin_amdgcn_mfma_f32_16x16x4f32(gv.w, vf[i].w, dp, 0, 0, 0);
-                    }
+                    const f32x4 sc = row_tile<D>(sQ, cb, lk, ln, kf), dp = row_tile<D>(sG, cb, lk, ln, vf);
                     f32x4 pr, ds;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int q = cb * 16 + lk * 4 + r;
                         const float4 stq = sSt[q];                               // (max, 1 / sum, D) of query q
-                        const float bv = bcol ? bcol[(size_t)q * T] : 0.f;
+                        const float bv = bias ? bias[bcol + (size_t)q * T] : 0.f;
                         pr[r] = expf(sc[r] * scale + bv - stq.x) * stq.y;
                         ds[r] = pr[r] * (dp[r] - stq.z);
                     }
-                    // dV^T += dO^T P and dK^T += Q^T dS: reduction step r takes query cb * 16 + lk * 4 + r from lane group lk
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float* ga = &sG[(cb * 16 + lk * 4 + r) * STR + ln];
-                        const float* qa = &sQ[(cb * 16 + lk * 4 + r) * STR + ln];
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) {
-                            dv[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[nb * 16], pr[r], dv[nb], 0, 0, 0);
-                            dk[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[nb * 16], ds[r], dk[nb], 0, 0, 0);
-                        }
-                    }
+                    key_tile_accumulate<D, false>(sQ, sG, cb, lk, ln, pr, ds, dk, dv);
                 }
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) {
-                    *reinterpret_cast<float4*>(gk + nb * 16) =
-                        make_float4(dk[nb][0] * scale, dk[nb][1] * scale, dk[nb][2] * scale, dk[nb][3] * scale);
-                    *reinterpret_cast<float4*>(gk + MD + nb * 16) = make_float4(dv[nb][0], dv[nb][1], dv[nb][2], dv[nb][3]);
-                }
+                store_tiles(gk, dk, scale);
+                store_tiles(gk + MD, dv, 1.f);
             } else {
                 // a masked agent: no query attends to its keys
-                const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) {
-                    *reinterpret_cast<float4*>(gk + nb * 16) = z;
-                    *reinterpret_cast<float4*>(gk + MD + nb * 16) = z;
-                }
+                f32x4 z[NB];
+                zero_tiles(z);
+                store_tiles(gk, z, 1.f);
+                store_tiles(gk + MD, z, 1.f);
             }
         }
         __syncthreads();                                 // the next group's staging overwrites the tiles
     }
     // ---- this part's share of dbias: db[cb][r] = sum over its groups of dS[query tq][key cb * 16 + lk * 4 + r]; zeros for masked keys ------
-    if (gbias_parts) {
-        float* gb = gbias_parts + (((size_t)part * m + h) * T + tq) * T + lk * 4;
-#pragma unroll
-        for (int cb = 0; cb < L; ++cb)
-            *reinterpret_cast<float4*>(gb + cb * 16) = make_float4(db[cb][0], db[cb][1], db[cb][2], db[cb][3]);
-    }
+    if (gbias_parts) store_tiles(gbias_parts + (((size_t)part * m + h) * T + tq) * T + lk * 4, db, 1.f);
 }
 
 // out[i] = parts[0][i] + parts[1][i] + ...: the partials in part order.  One float4 per thread.
