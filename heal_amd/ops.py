@@ -831,13 +831,14 @@ DISCO_MAX_AGENTS = WARP_MAX_AGENTS
 DISCO_WIDTHS = (128, 32, 8)        # PixelWeightLayer: 2C -> 128 -> 32 -> 8 -> 1
 
 
-def disco_fuse(feats, affine_rows, grid_f64, e0, w1n_frag, w2, b2, w3, b3, w4, b4, return_scores=False):
+def disco_fuse(feats, affine_rows, grid_f64, e0, w1n_frag, w2, b2, w3, b3, w4, b4, return_scores=False, out=None, scores=None):
     """DiscoNet's fusion of one scene in ONE launch (heal_disco_fuse; fusion_in_one.py:153-201): every agent warped into the ego
     frame, one logit per (agent, pixel) from the PixelWeightLayer over cat(warped neighbour, unwarped ego), softmax over agents,
     weighted sum.  BatchNorm folded by the caller, layer 1 split by input half:
     feats [n,C,H,W] fp32 (1..8 agents, C % 4 == 0), affine_rows [n,2,3] (host array or CUDA tensor read at run time),
     e0 [128,H,W] = W1e x_0 + b1, w1n_frag = mfma_a_fragments(W1n [128,C]) [8,C/4,64], w2 [32,128], b2 [32], w3 [8,32], b3 [8],
-    w4 [8], b4 [1] -> out [C,H,W], or (out, scores [n,H,W] post-ReLU logits) with return_scores."""
+    w4 [8], b4 [1] -> out [C,H,W], or (out, scores [n,H,W] post-ReLU logits) with return_scores.  `out` / `scores`: the caller's
+    destinations (contiguous f32 tensors of those shapes on feats' device; `scores` only with return_scores), written in place."""
     who = "disco_fuse"
     feats = _need(feats, torch.float32, "feats")
     if feats.dim() != 4:
@@ -848,9 +849,12 @@ def disco_fuse(feats, affine_rows, grid_f64, e0, w1n_frag, w2, b2, w3, b3, w4, b
     if C % 4 or C < 4:
         raise _capi.HealAmdError(f"{who}: C must be a positive multiple of the MFMA k-step 4 (got {C})")
     m1, m2, m3 = DISCO_WIDTHS
+    if scores is not None and not return_scores:
+        raise _capi.HealAmdError(f"{who}: `scores` given without return_scores")
+    out = _out_like(out, (C, H, W), feats.device, who)
+    scores = _out_like(scores, (n, H, W), feats.device, who, "scores") if return_scores else None
     if n == 1 and not return_scores and all(t is None for t in (e0, w1n_frag, w2, b2, w3, b3, w4, b4)):
         # the softmax of one logit is exactly 1: the warped map, no PixelWeightLayer operands
-        out = torch.empty((C, H, W), dtype=torch.float32, device=feats.device)
         a, ap, adev = _affine_args(affine_rows, n)
         with _Timed(f"disco_fuse_c{C}", 2.0 * C * H * W, 8.0 * C * H * W, kernel_events=True):
             _capi.call("heal_disco_fuse", _ptr(feats), n, C, H, W, ap, adev, int(bool(grid_f64)), *([None] * 8), _ptr(out), None,
@@ -872,8 +876,6 @@ def disco_fuse(feats, affine_rows, grid_f64, e0, w1n_frag, w2, b2, w3, b3, w4, b
     w4 = _need_channels(w4, m3, "w4", who)
     b4 = _need_channels(b4, 1, "b4", who)
     w2_frag = _derived("disco_w2_fragments", (w2,), lambda: mfma_a_fragments(w2))
-    out = torch.empty((C, H, W), dtype=torch.float32, device=feats.device)
-    scores = torch.empty((n, H, W), dtype=torch.float32, device=feats.device) if return_scores else None
     a, ap, adev = _affine_args(affine_rows, n)
     flops = 2.0 * n * H * W * (m1 * C + m2 * m1 + m3 * m2 + m3) + 2.0 * n * C * H * W
     # compulsory traffic: every agent's map once, the ego term, the fused map (and the logits when asked for)
@@ -887,14 +889,17 @@ def disco_fuse(feats, affine_rows, grid_f64, e0, w1n_frag, w2, b2, w3, b3, w4, b
 W2C_MAX_AGENTS = _limit("HEAL_WARP_MAX_AGENTS")       # heal_warp_mha_fuse (include/heal_amd_ext.h)
 
 
-def warp_mha_fuse(q_map, kv_map, x_ego, bq, bk, bv, heads, affine_rows, grid_f64=True, scale=None, return_logits=False):
+def warp_mha_fuse(q_map, kv_map, x_ego, bq, bk, bv, heads, affine_rows, grid_f64=True, scale=None, return_logits=False, outs=None,
+                  logits=None):
     """Where2comm's fusion of one scene between its projections and its out-projection in ONE launch (heal_warp_mha_fuse;
     fusion_in_one.py:431-484): the projected maps of every agent sampled in the ego frame, the projection biases added after
     sampling, multi-head attention of the ego pixel over ALL agents (no key mask), and the warped ego map (the residual).
     q_map [C,H,W] = Wq x_0 and kv_map [n,2C,H,W] = [Wk; Wv] x_j: projections of the UNWARPED maps without bias; x_ego [C,H,W] the
     ego's unwarped map; bq, bk, bv [C]; 1..W2C_MAX_AGENTS agents, C % heads == 0; affine_rows [n,2,3] (host array or CUDA tensor
     read at run time); scale: the factor on q (None: 1 / sqrt(C / heads))
-    -> (ctx [C,H,W], ego_warped [C,H,W]), and the scaled logits [n,heads,H,W] with return_logits."""
+    -> (ctx [C,H,W], ego_warped [C,H,W]), and the scaled logits [n,heads,H,W] with return_logits.  `outs` = (ctx, ego_warped) /
+    `logits`: the caller's destinations (contiguous f32 tensors of those shapes on q_map's device; `logits` only with
+    return_logits), written in place."""
     who = "warp_mha_fuse"
     q_map = _need(q_map, torch.float32, "q_map")
     kv_map = _need(kv_map, torch.float32, "kv_map")
@@ -918,9 +923,13 @@ def warp_mha_fuse(q_map, kv_map, x_ego, bq, bk, bv, heads, affine_rows, grid_f64
     a, ap, adev = _affine_args(affine_rows, n)
     scale = float((C // heads) ** -0.5 if scale is None else scale)
     dev = q_map.device
-    ctx = torch.empty((C, H, W), dtype=torch.float32, device=dev)
-    ego_warped = torch.empty((C, H, W), dtype=torch.float32, device=dev)
-    logits = torch.empty((n, heads, H, W), dtype=torch.float32, device=dev) if return_logits else None
+    if outs is not None and (not isinstance(outs, (list, tuple)) or len(outs) != 2):
+        raise _capi.HealAmdError(f"{who}: `outs` must be the pair (ctx, ego_warped)")
+    if logits is not None and not return_logits:
+        raise _capi.HealAmdError(f"{who}: `logits` given without return_logits")
+    ctx = _out_like(None if outs is None else outs[0], (C, H, W), dev, who, "outs[0]")
+    ego_warped = _out_like(None if outs is None else outs[1], (C, H, W), dev, who, "outs[1]")
+    logits = _out_like(logits, (n, heads, H, W), dev, who, "logits") if return_logits else None
     flops = 2.0 * H * W * C * (2 * n + 1) + 8.0 * H * W * C * (2 * n + 2)      # the dot products and sums; 4 taps per sample
     # compulsory traffic: Q, the ego map and every agent's K and V once, the context and the warped ego (and the logits when asked)
     nbytes = 4.0 * H * W * ((2 * n + 2) * C + 2 * C + (n * heads if return_logits else 0))

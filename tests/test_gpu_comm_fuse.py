@@ -68,10 +68,13 @@ def same(a, b):
     return torch.equal(torch.from_numpy(np.ascontiguousarray(a)), torch.from_numpy(np.ascontiguousarray(b)))
 
 
-@pytest.mark.parametrize("pose", sorted(POSES))
-@pytest.mark.parametrize("levels", [1, 3])
-@pytest.mark.parametrize("C", [6, 64])
-@pytest.mark.parametrize("n", [1, 3, 8])
+# every agent count: k_warp_att_fuse_masked<NA> is instantiated apart from the unmasked kernel.  1, 3 and 8 on every axis; the counts
+# between them on the smallest case that still crosses a level boundary under a rotation.
+MASKED_CASES = ([(n, C, levels, pose) for n in (1, 3, 8) for C in (6, 64) for levels in (1, 3) for pose in sorted(POSES)]
+                + [(n, 6, 3, "rotated") for n in (2, 4, 5, 6, 7)])
+
+
+@pytest.mark.parametrize("n,C,levels,pose", MASKED_CASES)
 def test_masked_entry_equals_the_unmasked_entry_on_premultiplied_maps(n, C, levels, pose):
     fx = fixture(n, C, levels, pose, 7)
     pre = [CR.premultiply(f, m) for f, m in zip(fx["feats"], fx["masks"])]

@@ -56,13 +56,17 @@ def message_fp64(xs, w, mask, e, res, mode):
 
 
 @pytest.mark.parametrize("mode", ["mean", "max"])
-@pytest.mark.parametrize("N", [1, 3, 5, 8])
+@pytest.mark.parametrize("N", range(1, 9))
 def test_v2v_message_exact(mode, N):
     for (H, W, cin, cout, n_ego, th, split, use_res, zero) in [
             (13, 11, 24, 80, 2, None, None, True, None),      # odd map, channel tails, default tile / split
             (16, 16, 16, 64, 1, "4", 1, False, 0),            # one ego, an all-zero mask agent
             (9, 20, 8, 72, 2, "16", None, True, N - 1),       # 16-row tiles, zero mask on the last agent
-            (17, 18, 16, 64, 1, "8", N, False, None)]:        # the agent split at its maximum (N partials + reduce)
+            (17, 18, 16, 64, 1, "8", N, False, None),         # the agent split at its maximum (N partials + reduce)
+            (3, 5, 12, 20, 2, None, None, True, None),        # cin = 8 + 4: a partial second chunk; cout below one 64-row block
+            (1, 1, 3, 65, 1, "4", None, False, None),         # cin below one chunk; cout one row into a second block; a 1 x 1 map
+            (3, 5, 3, 65, 1, "16", N, True, None),            # the same channel edges through the split path
+            (1, 1, 12, 20, 2, "8", None, True, 0)]:           # a 1 x 1 map with a partial chunk and an all-zero mask agent
         xs, w, mask, e, res = message_fixture(n_ego, N, cin, cout, H, W, seed=100 * N + H, zero_agent=zero)
         old = os.environ.get("HEAL_V2V_TH")
         if th:
@@ -78,6 +82,22 @@ def test_v2v_message_exact(mode, N):
                     os.environ["HEAL_V2V_TH"] = old
         want = message_fp64(xs, w, mask, e, res if use_res else None, mode)
         assert torch.equal(got, want), (mode, N, H, W, th, split, float((got - want).abs().max()))
+
+
+@pytest.mark.parametrize("mode", ["mean", "max"])
+@pytest.mark.parametrize("N,nsplit", [(5, 3), (7, 4)])
+def test_v2v_message_uneven_split_exact(mode, N, nsplit):
+    """Agent splits of unequal length (5 = 2 + 2 + 1, 7 = 2 + 2 + 2 + 1) on the integer fixture: bit for bit the fp64 evaluation,
+    and the bits of the unsplit launch; an odd map, a partial channel chunk and a Cout tail."""
+    for H, W, cin, cout, n_ego, use_res in [(13, 11, 12, 65, 2, True), (3, 5, 24, 20, 1, False)]:
+        xs, w, mask, e, res = message_fixture(n_ego, N, cin, cout, H, W, seed=1000 * N + nsplit + H, zero_agent=N - 1)
+        res = res if use_res else None
+        with torch.no_grad():
+            got = ops.v2v_message(xs, mask, e, w, res, mode, nsplit=nsplit)
+            one = ops.v2v_message(xs, mask, e, w, res, mode, nsplit=1)
+        want = message_fp64(xs, w, mask, e, res, mode)
+        assert torch.equal(got, want), (mode, N, nsplit, H, W, float((got - want).abs().max()))
+        assert torch.equal(one, want), (mode, N, H, W)
 
 
 def test_v2v_message_split_equals_unsplit():
