@@ -95,7 +95,7 @@ def signatures_train():
 @functools.lru_cache(maxsize=None)
 def signatures_ext():
     """{name: (restype, argtypes)} of include/heal_amd_ext.h: inference entry points added outside the versioned table of
-    signatures() (heal_warp_mha_fuse).  Every build exports them."""
+    signatures() (heal_warp_mha_fuse; the scan and radix-sort primitives as test surfaces).  Every build exports them."""
     with open(HEADER_EXT) as f:
         return parse_prototypes(f.read())
 

@@ -29,9 +29,13 @@ inline size_t sort_scratch_words(int64_t n) {
     return (size_t)(tiles * SORT_BINS) + scan_scratch_words(tiles * SORT_BINS) + 64;
 }
 
-// Stable ascending sort on the low `key_bits` bits of the keys.  Buffers [0] hold the input;
-// the function ping-pongs between [0] and [1] and returns (through *result_buf) which of the two
-// holds the sorted output.
+// Stable ascending sort on the low 9 * ceil(key_bits / 9) bits of the keys (all 32 when that reaches
+// 32): the last digit is a full 9-bit digit, so key bits between key_bits and the next multiple of 9
+// take part in the order.  The key bits above that and the values are carried along unchanged.
+// Pairs whose compared bits are equal keep their input order.  Buffers [0] hold the input; the
+// function ping-pongs between [0] and [1] and returns (through *result_buf) which of the two holds
+// the sorted output: ceil(key_bits / 9) % 2, and 0 for n <= 1 (nothing is launched).
+// tests/test_gpu_prims.py pins this contract through heal_radix_sort_pairs.
 int radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], int n, int key_bits, int* result_buf,
                      int* scratch, hipStream_t s);
 

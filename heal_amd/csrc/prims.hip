@@ -1,7 +1,7 @@
 // Device-wide scan and stable radix sort (see prims.h).  gfx950, wave = 64.
 #include <stdlib.h>
 #include "prims.h"
-#include "../../include/heal_amd.h"
+#include "../../include/heal_amd_ext.h"
 
 namespace heal {
 
@@ -271,4 +271,30 @@ int heal_next_launch_events(void* start_event, void* stop_event) {
 int heal_abi_version(void) { return HEAL_AMD_ABI_VERSION; }
 const char* heal_last_error(void) { return heal::err_buf(); }
 int heal_fill_bytes(void* dst, int byte, size_t bytes, void* stream) { return heal::fill_bytes(dst, byte, bytes, (hipStream_t)stream); }
+
+// the primitives as entry points of their own (include/heal_amd_ext.h): test surfaces, no kernels of their own
+size_t heal_scan_exclusive_workspace(int n) { return heal::scan_scratch_words(n < 0 ? 0 : n) * sizeof(int); }
+int heal_scan_exclusive(const int32_t* in, int32_t* out, int n, int32_t* total, void* ws, size_t ws_bytes, void* stream) {
+    HEAL_REQUIRE(n >= 0, "heal_scan_exclusive: n = %d is negative", n);
+    HEAL_REQUIRE(n == 0 || (in != nullptr && out != nullptr), "heal_scan_exclusive: null operand (in %p, out %p)", (const void*)in, (void*)out);
+    HEAL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 3) == 0, "heal_scan_exclusive: the workspace must be a non-null, 4-byte aligned pointer (%p)", ws);
+    HEAL_REQUIRE(ws_bytes >= heal_scan_exclusive_workspace(n), "heal_scan_exclusive: workspace of %zu bytes, %zu needed for n = %d",
+                 ws_bytes, heal_scan_exclusive_workspace(n), n);
+    return heal::scan_exclusive(in, out, n, total, (int*)ws, (hipStream_t)stream);
+}
+size_t heal_radix_sort_pairs_workspace(int n) { return heal::sort_scratch_words(n < 0 ? 0 : n) * sizeof(int); }
+int heal_radix_sort_pairs(uint32_t* keys0, uint32_t* keys1, uint32_t* vals0, uint32_t* vals1, int n, int key_bits,
+                          int* result_buf_host, void* ws, size_t ws_bytes, void* stream) {
+    HEAL_REQUIRE(n >= 0, "heal_radix_sort_pairs: n = %d is negative", n);
+    HEAL_REQUIRE(key_bits >= 1 && key_bits <= 32, "heal_radix_sort_pairs: key_bits = %d outside [1, 32]", key_bits);
+    HEAL_REQUIRE(result_buf_host != nullptr, "heal_radix_sort_pairs: null result_buf_host");
+    HEAL_REQUIRE(n == 0 || (keys0 != nullptr && keys1 != nullptr && vals0 != nullptr && vals1 != nullptr),
+                 "heal_radix_sort_pairs: null operand (keys %p %p, vals %p %p)", (void*)keys0, (void*)keys1, (void*)vals0, (void*)vals1);
+    HEAL_REQUIRE(ws != nullptr && ((uintptr_t)ws & 3) == 0, "heal_radix_sort_pairs: the workspace must be a non-null, 4-byte aligned pointer (%p)", ws);
+    HEAL_REQUIRE(ws_bytes >= heal_radix_sort_pairs_workspace(n), "heal_radix_sort_pairs: workspace of %zu bytes, %zu needed for n = %d",
+                 ws_bytes, heal_radix_sort_pairs_workspace(n), n);
+    uint32_t* keys[2] = {keys0, keys1};
+    uint32_t* vals[2] = {vals0, vals1};
+    return heal::radix_sort_pairs(keys, vals, n, key_bits, result_buf_host, (int*)ws, (hipStream_t)stream);
+}
 }

@@ -4303,3 +4303,52 @@ def fill_bytes(t, byte):
         raise _capi.HealAmdError("fill_bytes: a contiguous CUDA tensor is required")
     _capi.call("heal_fill_bytes", _ptr(t), int(byte), t.numel() * t.element_size(), _stream())
     return t
+
+
+# ---- the index-building primitives of csrc/prims.hip as operators of their own (include/heal_amd_ext.h) ----------------------------
+# The model path reaches them only through their clients (the sparse convolution's rulebook, heal_bev_pool's cell sort); these
+# wrappers exist so that tests/test_gpu_prims.py can compare the primitives themselves with numpy.
+def _need_words(t, name, who):
+    """A 1-D int32 cuda tensor (made contiguous); for the sort the 32 bits of a word are an unsigned key / value."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _capi.HealAmdError(f"{who}: {name} must be a CUDA/HIP tensor (heal_amd has no CPU path)")
+    if t.dtype != torch.int32 or t.dim() != 1:
+        raise _capi.HealAmdError(f"{who}: {name} must be a 1-D torch.int32 tensor, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def scan_exclusive(x, out=None, want_total=True):
+    """Exclusive prefix sum of x [n] i32 cuda (heal_scan_exclusive): out[i] = x[0] + ... + x[i-1]; `out` may be x itself.
+    -> (out, total [1] i32 on the device) or, with want_total=False, out."""
+    x = _need_words(x, "x", "scan_exclusive")
+    n = int(x.numel())
+    if out is None:
+        out = torch.empty_like(x)
+    elif _need_words(out, "out", "scan_exclusive") is not out or int(out.numel()) != n:
+        raise _capi.HealAmdError(f"scan_exclusive: out must be a contiguous i32 tensor of {n} elements")
+    total = torch.empty((1,), dtype=torch.int32, device=x.device) if want_total else None
+    need = _capi.query("heal_scan_exclusive_workspace", n)
+    ws = _workspace("scan_exclusive", need, x.device)
+    _capi.call("heal_scan_exclusive", _ptr(x), _ptr(out), n, _ptr(total), _ptr(ws), need, _stream())
+    return (out, total) if want_total else out
+
+
+def radix_sort_pairs(keys, vals, key_bits):
+    """Stable ascending sort of the pairs (keys [n], vals [n]; i32 cuda, read as unsigned words) by the low 9 * ceil(key_bits / 9)
+    bits of the keys (heal_radix_sort_pairs; all 32 bits of a key travel with it).  The inputs are left as they are: the sort runs
+    on a ping-pong pair of its own.  -> (sorted keys, sorted vals), views of whichever half holds the result."""
+    keys = _need_words(keys, "keys", "radix_sort_pairs")
+    vals = _need_words(vals, "vals", "radix_sort_pairs")
+    n = int(keys.numel())
+    if int(vals.numel()) != n:
+        raise _capi.HealAmdError(f"radix_sort_pairs: {n} keys but {int(vals.numel())} values")
+    kbuf = torch.empty((2, n), dtype=torch.int32, device=keys.device)
+    vbuf = torch.empty((2, n), dtype=torch.int32, device=keys.device)
+    kbuf[0].copy_(keys)
+    vbuf[0].copy_(vals)
+    need = _capi.query("heal_radix_sort_pairs_workspace", n)
+    ws = _workspace("radix_sort_pairs", need, keys.device)
+    which = ctypes.c_int(-1)
+    _capi.call("heal_radix_sort_pairs", _ptr(kbuf[0]), _ptr(kbuf[1]), _ptr(vbuf[0]), _ptr(vbuf[1]), n, int(key_bits),
+               ctypes.byref(which), _ptr(ws), need, _stream())
+    return kbuf[which.value], vbuf[which.value]

@@ -32,6 +32,25 @@ int heal_warp_mha_fuse(const float* q_map, const float* kv_map, const float* x_e
                        const double* affine_host, const double* affine_dev, int grid_f64, float* ctx, float* ego_warped,
                        float* logits, void* stream);
 
+/* heal_scan_exclusive, heal_radix_sort_pairs: the two index-building primitives of csrc/prims.hip (the rulebook sort, candidate
+ *   compaction and granule scan of the sparse convolution; the cell sort of heal_bev_pool) as entry points of their own -- TEST
+ *   SURFACES: the model path reaches the primitives through their clients only.  Thin wrappers, no kernels of their own.
+ *   heal_scan_exclusive: out[i] = in[0] + ... + in[i-1] in int32 (wrapping like the additions it stands for); *total (device word,
+ *     may be NULL) = the sum of all n.  in == out is allowed.  n == 0 writes *total = 0 when total is given and launches nothing
+ *     else.  ws: heal_scan_exclusive_workspace(n) bytes, 4-byte aligned.
+ *   heal_radix_sort_pairs: STABLE ascending sort of n (key, value) pairs by the low 9 * ceil(key_bits / 9) bits of the keys (all
+ *     32 when that reaches 32: the last 9-bit digit is a full digit); the other key bits and the values are carried along.  keys0 /
+ *     vals0 hold the input, keys1 / vals1 are the second halves of the ping-pong ([n] words each, all four distinct);
+ *     *result_buf_host (HOST int, written before the function returns: it depends on key_bits alone) = 0 | 1 = the pair that holds
+ *     the result, ceil(key_bits / 9) % 2 for n > 1 and 0 for n <= 1 (nothing is launched); the other pair is left holding the input or an
+ *     intermediate pass.  1 <= key_bits <= 32.  ws: heal_radix_sort_pairs_workspace(n) bytes, 4-byte aligned.
+ *   Both refuse a negative n, null pointers (operands: when n > 0) and a workspace smaller than the query before any launch.   */
+size_t heal_scan_exclusive_workspace(int n);
+int heal_scan_exclusive(const int32_t* in, int32_t* out, int n, int32_t* total, void* ws, size_t ws_bytes, void* stream);
+size_t heal_radix_sort_pairs_workspace(int n);
+int heal_radix_sort_pairs(uint32_t* keys0, uint32_t* keys1, uint32_t* vals0, uint32_t* vals1, int n, int key_bits,
+                          int* result_buf_host, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,22 @@ def test_no_runtime_memset_or_d2d_copy_in_the_library():
     assert not hits, hits
 
 
+def test_scan_and_sort_wrappers_have_no_cpu_path_and_check_their_operands():
+    """ops.scan_exclusive / ops.radix_sort_pairs (the primitives' test surfaces) refuse host tensors; the workspace queries are host
+    arithmetic and follow csrc/prims.h: one word per 4096-element scan tile + 1; 512 histogram words per 2048-pair sort tile, the
+    scan scratch of that histogram, and 64 spare words."""
+    from heal_amd import _capi, ops
+    with pytest.raises(_capi.HealAmdError, match="CUDA/HIP"):
+        ops.scan_exclusive(torch.zeros(4, dtype=torch.int32))
+    with pytest.raises(_capi.HealAmdError, match="CUDA/HIP"):
+        ops.radix_sort_pairs(torch.zeros(4, dtype=torch.int32), torch.zeros(4, dtype=torch.int32), 10)
+    for n, words in ((0, 1), (1, 2), (4096, 2), (4097, 3), (1024 * 4096 + 1, 1026)):
+        assert _capi.query("heal_scan_exclusive_workspace", n) == 4 * words, n
+    for n, tiles in ((0, 1), (1, 1), (2048, 1), (2049, 2), (16385, 9), (100003, 49)):
+        hist = 512 * tiles
+        assert _capi.query("heal_radix_sort_pairs_workspace", n) == 4 * (hist + (hist + 4095) // 4096 + 1 + 64), n
+
+
 def test_collection_order_names_exist():
     """tests/conftest.py runs one parity test per BASELINE config FIRST (by name) and the rank-spawning file LAST: a renamed test or file
     would silently fall out of that order.  Every name in `_FIRST` must be a collected test, and they must lead the GPU collection."""

@@ -244,8 +244,12 @@ def test_ext_header_is_parsed_bound_and_exported():
     """include/heal_amd_ext.h: its prototype as written out here, bound by _capi.lib(), exported by the library; the versioned
     table, the experimental header and the training header keep their entry points."""
     from heal_amd import _capi, build, ops
-    P, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    assert _capi.signatures_ext() == {"heal_warp_mha_fuse": (I, [P] * 6 + [I] * 5 + [F, P, P, I, P, P, P, P])}
+    P, I, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+    assert _capi.signatures_ext() == {"heal_warp_mha_fuse": (I, [P] * 6 + [I] * 5 + [F, P, P, I, P, P, P, P]),
+                                      "heal_scan_exclusive_workspace": (Z, [I]),
+                                      "heal_scan_exclusive": (I, [P, P, I, P, P, Z, P]),
+                                      "heal_radix_sort_pairs_workspace": (Z, [I]),
+                                      "heal_radix_sort_pairs": (I, [P] * 4 + [I, I, P, P, Z, P])}
     assert (len(_capi.signatures(False)), len(_capi.signatures(True)), len(_capi.signatures_train())) == (126, 7, 4)
     assert not set(_capi.signatures_ext()) & (set(_capi.signatures()) | set(_capi.signatures_train()))
     assert _capi.HEADER_EXT in build._deps()                    # an edit of the header rebuilds the objects
@@ -253,6 +257,9 @@ def test_ext_header_is_parsed_bound_and_exported():
     L = _capi.lib()
     assert hasattr(L, "heal_warp_mha_fuse")
     assert L.heal_warp_mha_fuse.argtypes == _capi.signatures_ext()["heal_warp_mha_fuse"][1] and L.heal_warp_mha_fuse.restype is I
+    for name, (res, args) in _capi.signatures_ext().items():
+        assert hasattr(L, name), name
+        assert getattr(L, name).argtypes == args and getattr(L, name).restype is res, name
     assert ops.W2C_MAX_AGENTS == _capi.header_define("HEAL_WARP_MAX_AGENTS")
 
 
