@@ -93,23 +93,26 @@ LaunchEvents take_launch_events();
 // (y0, y1, x0, x1) in output pixels for each image, passed BY VALUE as a kernel argument -- no device memory, so a captured graph
 // holds the boxes as constants.  A block whose output tile holds no pixel of its image's box returns before its first load and writes
 // nothing; the test runs on block-uniform values in the prologue, before any barrier, so every wave of a block takes the same path.
+// (heal_conv1x1_box_roi: the tiles enumerate the box itself, roi_align4 below; a tile behind its last pixel returns in the same place.)
 // The kernels take the table as a template choice (`bool ROI`, default false): the plain instantiation -- what the old entry points
 // launch -- receives the empty NoRoi instead and compiles to the code it always was (no test, no larger argument block).
 constexpr int ROI_MAX_IMAGES = 8;   // == HEAL_WARP_MAX_AGENTS (checked where the header is included)
 struct RoiTable {
     int n;
     unsigned perm;   // see roi_spread
+    int by_box;      // k_conv1x1: the tiles enumerate the (aligned) boxes, not the images (roi_align4)
     int box[ROI_MAX_IMAGES][4];
 };
-inline RoiTable no_roi() { RoiTable r; r.n = 0; r.perm = 1; return r; }
+inline RoiTable no_roi() { RoiTable r; r.n = 0; r.perm = 1; r.by_box = 0; return r; }
 struct NoRoi {};
 template <bool ROI> struct RoiArg { using type = NoRoi; };
 template <> struct RoiArg<true> { using type = RoiTable; };
 // Workgroups go to the 8 XCDs round-robin and xcd_block() hands every XCD one CONTIGUOUS range of the logical block order, image index
 // slowest: the tiles a ROI skips (whole images' borders) would all fall to a few XCDs, which then idle while the others set the kernel's
-// time.  A ROI launch therefore walks its G (tile, image) pairs in the order L -> L * perm mod G, perm coprime to G and near G / phi:
-// every contiguous range of L holds an even sample of all images and all tile positions.  Blocks that share a pair (the Cout chunks
-// of a pixel tile, the super-groups of a 3x3 tile) stay together.  perm == 1: identity.
+// time.  A pointwise ROI launch therefore walks its G (tile, image) pairs in the order L -> L * perm mod G, perm coprime to G and near
+// G / phi: every contiguous range of L holds an even sample of all images and all tile positions.  Blocks that share a pair (the Cout
+// chunks of a pixel tile) stay together.  perm == 1: identity.  (The 3x3 ROI launch, whose neighbouring tiles share halo pixels, turns
+// the image index with the super-group instead: gconv_small.hip.)
 inline unsigned roi_spread(unsigned G) {
     if (G < 16 || G >= 65536) return 1;            // (L * perm stays below 2^32)
     auto gcd = [](unsigned a, unsigned b) { while (b) { const unsigned t = a % b; a = b; b = t; } return a; };
@@ -131,6 +134,18 @@ inline const char* roi_from_host(const int32_t* roi_host, int n, int Ho, int Wo,
             return "ROI box outside the output map";
     }
     return nullptr;
+}
+// The box rule of heal_conv1x1_box_roi (Wo % 4 == 0): a launch's 64-pixel tiles enumerate each image's ALIGNED box -- its rows, its columns
+// rounded outward to multiples of 4 (inside the map, since Wo % 4 == 0) -- row by row, so every float4 of the kernel lies in one row of
+// the box and stays 16-B aligned.  An empty box becomes all zeros: no pixel, every tile of the image leaves.
+inline void roi_align4(RoiTable* r) {
+    r->by_box = 1;
+    for (int i = 0; i < r->n; ++i) {
+        int* b = r->box[i];
+        if (b[0] >= b[1] || b[2] >= b[3]) { b[0] = b[1] = b[2] = b[3] = 0; continue; }
+        b[2] &= ~3;
+        b[3] = (b[3] + 3) & ~3;
+    }
 }
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

@@ -22,10 +22,18 @@
 // returns in the prologue -- before the first load, the LDS staging and every barrier -- and writes nothing.  The test is exact for
 // a tile that lies in one output row (Wo % BN == 0: a row segment, rows AND columns are tested; Wo == BN: a whole row) and
 // conservative for a tile that spans rows (kept when any spanned row meets the box's rows; columns are not looked at).  Kept
-// blocks run the instructions of the plain launch on the same values: bit-identical results.  It is the ROI = true instantiation of the
-// kernel template (the 64 x 64 x 32 tile, both strides); heal_conv1x1 and the other entry points launch the default, ROI = false, which
-// takes no table and has no test.  Not combined with split-K, pixel-major or depth-to-space output.  A ROI launch also walks its (pixel tile,
-// image) pairs in a spread order (roi_spread, common.h): the skipped tiles are then shared evenly among the XCDs.
+// blocks compute what the plain launch computes, from the same values in the same order: bit-identical results.
+// Box rule (heal_conv1x1_box_roi, `roi.by_box`; Wo % 4 == 0): the tiles enumerate the image's box instead -- its rows, its columns rounded
+// outward to multiples of 4 (roi_align4, host) -- row by row: tile t is pixels [64 t, 64 t + 64) of that enumeration, pixel q row
+// y0 + q / bw, column xa + q % bw.  A tile that starts behind the box's last pixel returns in the prologue; the last kept tile's pixels
+// behind the box are masked like the tail of an image.  bw % 4 == 0 and xa % 4 == 0: every float4 (staging, residual, store) lies in
+// one row and is 16-B aligned.  The mapping is computed once per thread before the chunk loop (the staging float4 and the epilogue's
+// pixel group are fixed per thread); the loop body is the plain one.  A column of the GEMM is a dot product of its own: where a pixel
+// sits in the MFMA tile does not change its value.  The full box is the identity mapping.
+// Both rules are the ROI = true instantiation of the kernel template (the 64 x 64 x 32 tile, both strides); heal_conv1x1 and the other
+// entry points launch the default, ROI = false, which takes no table, has no test and maps nothing.  Not combined with split-K,
+// pixel-major or depth-to-space output.  A ROI launch also walks its (pixel tile, image) pairs in a spread order (roi_spread, common.h): the
+// skipped tiles are then shared evenly among the XCDs.
 #include <stdlib.h>
 #include "common.h"
 #include "../../include/heal_amd.h"
@@ -66,14 +74,26 @@ __global__ __launch_bounds__(256) void k_conv1x1(const float* __restrict__ x, co
         bk.z = L / gridDim.y;
     }
     const int m0 = bk.x * BM, p0 = bk.y * BN, n = bk.z % n_img, kpart = bk.z / n_img;
-    if constexpr (ROI) {   // block-uniform, before any load or barrier: leave if no pixel of the tile [p0, p0 + BN) lies in image n's box
+    // The tile is pixels [p0, p0 + BN) of an ENUMERATION of npix pixels, row by row over rows ey0 .. and columns [ex0, ex0 + bw): the
+    // whole image (plain launch, tile rule: pixel q is flattened pixel q) or image n's aligned box (box rule).
+    int ey0 = 0, ex0 = 0, bw = Wo, npix = HW;
+    if constexpr (ROI) {   // block-uniform, before any load or barrier
         const int y0 = roi.box[n][0], y1 = roi.box[n][1], x0 = roi.box[n][2], x1 = roi.box[n][3];
-        const int pl = min(p0 + BN, HW) - 1;                 // last pixel of the tile
-        const int r0 = p0 / Wo, r1 = pl / Wo;                // first and last output row the tile touches
-        bool keep = y0 < y1 && x0 < x1 && r0 < y1 && r1 >= y0;
-        if (keep && r0 == r1) keep = p0 - r0 * Wo < x1 && pl - r0 * Wo >= x0;   // one row: its column range against the box's
-        if (!keep) return;
+        if (roi.by_box) {  // box rule (the host aligned the box: roi_align4): leave if the tile starts behind the box's last pixel
+            ey0 = y0; ex0 = x0; bw = x1 - x0; npix = bw * (y1 - y0);
+            if (p0 >= npix) return;
+        } else {           // tile rule: leave if no pixel of the image's tile [p0, p0 + BN) lies in the box
+            const int pl = min(p0 + BN, HW) - 1;                 // last pixel of the tile
+            const int r0 = p0 / Wo, r1 = pl / Wo;                // first and last output row the tile touches
+            bool keep = y0 < y1 && x0 < x1 && r0 < y1 && r1 >= y0;
+            if (keep && r0 == r1) keep = p0 - r0 * Wo < x1 && pl - r0 * Wo >= x0;   // one row: its column range against the box's
+            if (!keep) return;
+        }
     }
+    auto pix = [&](int q) {   // flattened OUTPUT pixel of pixel q of the enumeration (q % 4 == 0: q .. q + 3 share a row, 16-B aligned)
+        const int r = q / bw;
+        return (ey0 + r) * Wo + ex0 + (q - r * bw);
+    };
     const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
     const int lk = l >> 4, ln = l & 15;
     const float* __restrict__ xin = x + (size_t)n * Cin * in_HW;
@@ -82,7 +102,12 @@ __global__ __launch_bounds__(256) void k_conv1x1(const float* __restrict__ x, co
     const int cbeg = kpart * cps, nchunks = min(cbeg + cps, nchunks_all);   // this block's chunk range [cbeg, nchunks)
     const float* __restrict__ scl = in_scale ? in_scale + (size_t)n * Cin : nullptr;
     const int sp = (threadIdx.x % TPR) * 4, sc = threadIdx.x / TPR;
-    const bool pix_ok = p0 + sp < HW;  // HW % 4 == 0 (checked by the host): a float4 is all-in or all-out
+    const bool pix_ok = p0 + sp < npix;  // npix % 4 == 0 (HW: checked by the host; a box: bw % 4 == 0): a float4 is all-in or all-out
+    int in_off = 0;                      // ROI: this thread's staging float4 in a channel plane of the input, computed ONCE (sp is fixed)
+    if constexpr (ROI) {
+        const int p = pix(p0 + sp), oy = p / Wo;
+        in_off = STRIDE == 1 ? p : oy * STRIDE * in_W + (p - oy * Wo) * STRIDE;
+    }
 
     f32x4 acc[MT][NT];
 #pragma unroll
@@ -97,7 +122,11 @@ __global__ __launch_bounds__(256) void k_conv1x1(const float* __restrict__ x, co
             const int ch = c * KC + sc + RPP * i;
             if (pix_ok && ch < Cin) {
                 float4 v;
-                if constexpr (STRIDE == 1) {
+                if constexpr (ROI) {
+                    const float* src = xin + (size_t)ch * in_HW + in_off;
+                    if constexpr (STRIDE == 1) v = *reinterpret_cast<const float4*>(src);
+                    else v = make_float4(src[0], src[STRIDE], src[2 * STRIDE], src[3 * STRIDE]);
+                } else if constexpr (STRIDE == 1) {
                     v = *reinterpret_cast<const float4*>(xin + (size_t)ch * HW + p0 + sp);
                 } else {  // 4 consecutive output pixels of one row (Wo % 4 == 0) -> every STRIDE-th input pixel
                     const int p = p0 + sp, oy = p / Wo, ox = p - oy * Wo;
@@ -174,7 +203,7 @@ __global__ __launch_bounds__(256) void k_conv1x1(const float* __restrict__ x, co
             for (int ks = 0; ks < KS; ++ks) a_cur[mt][ks] = a_nxt[mt][ks];
     }
 
-    if (out_pm == 1) {
+    if (!ROI && out_pm == 1) {   // (no ROI launch is pixel-major)
         // Pixel-major output y[n][pixel][Cout] (what K4's lift + BEV pool reads: one pixel's channels are one contiguous
         // row).  MFMA leaves D[row = lk*4 + r][col = ln]: a lane holds 4 CONSECUTIVE channels of one pixel -> one 16-B
         // store per (mt, nt), the four lk groups complete a 64-B run per pixel.  No residual in this layout.
@@ -208,6 +237,11 @@ __global__ __launch_bounds__(256) void k_conv1x1(const float* __restrict__ x, co
     float* __restrict__ yout = y + ((size_t)kpart * n_img + n) * Cout * HW;
     const float* __restrict__ rin = res ? res + (size_t)n * Cout * HW : nullptr;
     constexpr int NG = NT / 4;
+    int po[NG] = {};   // ROI: flattened output pixel of this lane's pixel group gq (a group behind the last one: the last one), computed ONCE
+    if constexpr (ROI) {
+#pragma unroll
+        for (int gq = 0; gq < NG; ++gq) po[gq] = pix(min(p0 + gq * 64 + 4 * ln, npix - 4));
+    }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         // residual pieces of this m-tile first (unconditional loads on clamped addresses), all in flight together
@@ -217,7 +251,8 @@ __global__ __launch_bounds__(256) void k_conv1x1(const float* __restrict__ x, co
             for (int r = 0; r < 4; ++r)
 #pragma unroll
                 for (int gq = 0; gq < NG; ++gq) {
-                    const int co = min(m0 + (wave * MT + mt) * 16 + lk * 4 + r, Cout - 1), p = min(p0 + gq * 64 + 4 * ln, HW - 4);
+                    const int co = min(m0 + (wave * MT + mt) * 16 + lk * 4 + r, Cout - 1);
+                    const int p = ROI ? po[gq] : min(p0 + gq * 64 + 4 * ln, HW - 4);
                     rq[r][gq] = *reinterpret_cast<const float4*>(rin + (size_t)co * HW + p);
                 }
         }
@@ -228,8 +263,8 @@ __global__ __launch_bounds__(256) void k_conv1x1(const float* __restrict__ x, co
             const float bv = bias ? bias[co] : 0.f;
 #pragma unroll
             for (int gq = 0; gq < NG; ++gq) {
-                const int p = p0 + gq * 64 + 4 * ln;
-                if (p >= HW) continue;                                  // HW % 4 == 0 (host): a piece is all-in or all-out
+                if (p0 + gq * 64 + 4 * ln >= npix) continue;            // npix % 4 == 0: a piece is all-in or all-out
+                const int p = ROI ? po[gq] : p0 + gq * 64 + 4 * ln;
                 float4 v = make_float4(acc[mt][4 * gq][r] + bv, acc[mt][4 * gq + 1][r] + bv, acc[mt][4 * gq + 2][r] + bv,
                                        acc[mt][4 * gq + 3][r] + bv);
                 const size_t o = (size_t)co * HW + p;
@@ -310,7 +345,7 @@ int splitk_reduce_launch(const float* partials, const float* bias, const float* 
 static int conv1x1_launch(const float* x, const float* weight_frag, const float* bias, const float* residual,
                           const float* in_scale, int n, int cin, int cout, int H, int W, int stride, int act,
                           int out_pixel_major, int d2s_k, int d2s_ctot, int d2s_coff, float* y, void* stream,
-                          int ksplit = 1, float* partials = nullptr, const int32_t* roi_host = nullptr) {
+                          int ksplit = 1, float* partials = nullptr, const int32_t* roi_host = nullptr, bool roi_box = false) {
     HEAL_REQUIRE(n >= 1 && H >= 1 && W >= 1 && cin >= 1 && cout >= 1, "conv1x1: bad shape");
     HEAL_REQUIRE(stride == 1 || stride == 2, "conv1x1: stride must be 1 or 2 (got %d)", stride);
     const int kpad = (cin + 31) / 32 * 32, mpad = (cout + 63) / 64 * 64;  // dims of the zero-padded fragment layout
@@ -328,6 +363,7 @@ static int conv1x1_launch(const float* x, const float* weight_frag, const float*
         HEAL_REQUIRE(ksplit == 1 && out_pixel_major == 0, "conv1x1_roi: no split-K, pixel-major or depth-to-space output with a ROI");
         const char* bad = roi_from_host(roi_host, n, Ho, Wo, &roi);
         HEAL_REQUIRE(!bad, "conv1x1_roi: %s (n = %d, output %d x %d)", bad, n, Ho, Wo);
+        if (roi_box && Wo % 4 == 0) roi_align4(&roi);   // (a width that is no multiple of 4 keeps the tile rule)
     }
     hipStream_t s = (hipStream_t)stream;
     // Tile choice (BM, BN, KC).  Measured on MI355X at the PyramidFusion shapes (scripts/conv1x1_bench.py --sweep): the
@@ -398,6 +434,14 @@ extern "C" int heal_conv1x1_roi(const float* x, const float* weight_frag, const 
     HEAL_REQUIRE(roi_host, "conv1x1_roi: null ROI table");
     return conv1x1_launch(x, weight_frag, bias, residual, in_scale, n, cin, cout, H, W, stride, act, 0, 1, 0, 0, y, stream, 1,
                           nullptr, roi_host);
+}
+
+extern "C" int heal_conv1x1_box_roi(const float* x, const float* weight_frag, const float* bias, const float* residual,
+                                    const float* in_scale, int n, int cin, int cout, int H, int W, int stride, int act,
+                                    const int32_t* roi_host, float* y, void* stream) {
+    HEAL_REQUIRE(roi_host, "conv1x1_roi: null ROI table");
+    return conv1x1_launch(x, weight_frag, bias, residual, in_scale, n, cin, cout, H, W, stride, act, 0, 1, 0, 0, y, stream, 1,
+                          nullptr, roi_host, true);
 }
 
 extern "C" int heal_roi_enabled(void) {

@@ -26,8 +26,13 @@
 // image.  A block whose TH x TW output tile (clipped to the map) holds no pixel of its image's box returns in the prologue, before
 // the first load and the barrier, and writes nothing: an exact test on rows and columns.  Kept blocks run the plain launch's
 // instructions on the same values.  It is the ROI = true instantiation of the kernel template (the default tile heights);
-// heal_grouped_small_conv3x3 launches the default, ROI = false, which takes no table and has no test.  A ROI launch also walks its (tile, image)
-// pairs in a spread order (roi_spread, common.h): the skipped tiles are then shared evenly among the XCDs.
+// heal_grouped_small_conv3x3 launches the default, ROI = false, which takes no table and has no test.
+// Block order of a ROI launch.  xcd_block() gives every XCD a contiguous range of the order (tile fastest, then super-group, then image):
+// runs of whole (super-group, image) maps, whose neighbouring tiles share their halo rows and columns through the XCD's L2.  Skipped
+// tiles all belong to a few images, so with the image slowest a few XCDs would skip everything and the others set the kernel's time.
+// The image index therefore TURNS with the super-group: (sg, z) runs image (z + sg) % n.  A bijection per tile; every run of n
+// super-groups now holds each image once, so the XCDs skip equal shares, and a map's tiles stay together as in the plain launch.  (A
+// spread over single tiles, as heal_conv1x1_roi uses, balanced the XCDs too but took the halo neighbours apart: slower than no ROI.)
 #include <stdlib.h>
 #include "common.h"
 #include "../../include/heal_amd.h"
@@ -56,11 +61,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
     __shared__ float4 sP[PR * PC * 4];       // [row][pixel][unit = channel / 4]
     __shared__ float4 sW[NSTEP * 16 / 4];    // [tap][ci][output channel of the super-group]
     Block3 bk = xcd_block();                 // x: tile, y: super-group, z: image
-    if constexpr (ROI) {                     // ROI launch: (tile, image) pairs in spread order (roi_spread): every XCD skips its share
-        const unsigned L = (bk.x + gridDim.x * bk.z) * roi.perm % (gridDim.x * gridDim.z);
-        bk.x = L % gridDim.x;
-        bk.z = L / gridDim.x;
-    }
+    if constexpr (ROI) bk.z = (bk.z + bk.y) % gridDim.z;   // ROI launch: the image index turns with the super-group (see above)
     const int sg = bk.y, n = bk.z;
     const int ty = bk.x / tiles_x, tx = bk.x - ty * tiles_x;
     const int oy0 = ty * TH, ox0 = tx * TW;
@@ -219,7 +220,6 @@ static int gconv_small_launch(const float* x, const float* weight_q, const float
         HEAL_REQUIRE(!bad, "grouped_small_conv3x3_roi: %s (n = %d, output %d x %d)", bad, n, Ho, Wo);
     }
     const int tiles_x = ceil_div(Wo, tw), tiles_y = ceil_div(Ho, th);
-    if (roi.n) roi.perm = roi_spread((unsigned)(tiles_x * tiles_y) * (unsigned)n);   // over the grid's (tile, image) pairs
     HEAL_REQUIRE(channels / 16 <= 65535 && n <= 65535, "grouped_small_conv3x3: grid limit");
     const dim3 grid(tiles_x * tiles_y, channels / 16, n);
     hipStream_t s_ = (hipStream_t)stream;

@@ -51,7 +51,8 @@ def conv3x3_enabled():
 def conv_bias_act(x, w, b, stride, padding, dilation=1, groups=1, relu=True, residual=None, out=None, roi=None):
     """conv2d + per-channel bias (+ residual) (+ ReLU); `out`: optional destination (a batch slice of a stage output).
     roi: per-image output boxes [(y0, y1, x0, x1)] * n the caller needs (inference; the fusion pyramid's stages for camera agents): the
-    pointwise and the small-group 3x3 kernels skip the tiles outside them (ops.conv1x1 / ops.grouped_conv3x3, `roi`) and leave that
+    pointwise kernel computes its boxes' pixels alone (columns rounded outward to 4: ops.conv1x1, roi_rule "box"), the small-group 3x3
+    kernel skips the tiles outside them (ops.grouped_conv3x3, `roi`), and both leave that
     part of the result UNDEFINED; every other path computes the whole map.  The ResNeXt 32-group 3x3 convolutions run on the
     hand-written stencil kernel (heal_grouped_conv3x3); everything else is a library convolution WITHOUT
     bias followed by ONE fused in-place pass (heal_bias_act) instead of separate bias / add / ReLU kernels."""
@@ -72,7 +73,7 @@ def conv_bias_act(x, w, b, stride, padding, dilation=1, groups=1, relu=True, res
     if groups == 1 and w.shape[2:] == (1, 1) and st in (1, 2) and pd == 0 and conv1x1_enabled():
         Ho, Wo = (int(x.shape[2]) - 1) // st + 1, (int(x.shape[3]) - 1) // st + 1
         if ops.conv1x1_supported(int(w.shape[1]), int(w.shape[0]), Ho * Wo, st, Wo):
-            return ops.conv1x1(x, w, b, residual, 1 if relu else 0, stride=st, out=out, roi=roi)
+            return ops.conv1x1(x, w, b, residual, 1 if relu else 0, stride=st, out=out, roi=roi, roi_rule="box")
     if (x.is_cuda and groups == 1 and tuple(w.shape[2:]) == (3, 3) and pd == 1 and dl == 1 and st in (1, 2)
             and (padding if isinstance(padding, int) else padding[1]) == 1
             and (stride if isinstance(stride, int) else stride[1]) == st and conv3x3_enabled()):

@@ -2996,6 +2996,21 @@ def pyramid_roi_enabled():
     return bool(_capi.query("heal_roi_enabled"))
 
 
+def conv1x1_box_tiles(box, Ho, Wo):
+    """Host mirror of heal_conv1x1_box_roi's tiles for one image (include/heal_amd_roi.h): int64 [tiles, 64], row t the flattened
+    output pixels y * Wo + x that workgroup tile t computes and writes, in the kernel's order; -1 where the last tile reaches behind
+    the box.  tiles = ceil(bw * bh / 64) of the image's ceil(Ho * Wo / 64); an empty box has none.  Wo % 4 == 0."""
+    y0, y1, x0, x1 = (int(v) for v in box)
+    if Wo % 4:
+        raise ValueError("the box rule needs an output width that is a multiple of 4")
+    if y0 >= y1 or x0 >= x1:
+        return np.zeros((0, 64), dtype=np.int64)
+    xa, xb = x0 // 4 * 4, -(-x1 // 4) * 4
+    bw, npix = xb - xa, (xb - xa) * (y1 - y0)
+    q = np.arange(-(-npix // 64) * 64, dtype=np.int64)
+    return np.where(q < npix, (y0 + q // bw) * Wo + xa + q % bw, -1).reshape(-1, 64)
+
+
 def _roi_table(roi, n, Ho, Wo, who):
     """Per-image output boxes [(y0, y1, x0, x1)] * n -> the host int32 [n, 4] array of the *_roi entry points (keep it alive over the
     call).  The table travels by value in the kernel arguments: under graph capture the boxes are constants of the graph."""
@@ -3217,7 +3232,7 @@ def _out_like(out, shape, device, who, name="out"):
 
 
 def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixel_major=False, out=None, roi=None,
-            fragments=None):
+            fragments=None, roi_rule="tile"):
     """Pointwise convolution with fused prologue / epilogue: act(W (in_scale . x) + bias (+ residual));
     act 0 none | 1 ReLU | 2 SiLU; stride 1 | 2.  x [n,Cin,H,W] f32 cuda, w [Cout,Cin,1,1], in_scale [n,Cin].
     fragments: the conv1x1_fragments layout of `w`, made by the caller (xca_fragments).  For a weight that a kernel wrote on the
@@ -3227,7 +3242,11 @@ def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixe
     out: optional destination (NCHW result only), e.g. the batch slice of a stage's output that an agent chunk fills.
     roi: per-image output boxes [(y0, y1, x0, x1)] * n (heal_conv1x1_roi; NCHW result only): 64-pixel tiles that hold no pixel of
     their image's box are not computed and their part of the result keeps what the buffer held (uninitialised memory for a new
-    one).  The split-K and the opt-in kernels take no ROI: they compute the whole map."""
+    one).  The split-K and the opt-in kernels take no ROI: they compute the whole map.
+    roi_rule: "tile" (above) | "box" (heal_conv1x1_box_roi): the tiles enumerate each image's box, its columns rounded outward to
+    multiples of 4; exactly those pixels are computed and written (conv1x1_box_tiles is the host's count of it)."""
+    if roi_rule not in ("tile", "box"):
+        raise _capi.HealAmdError(f"conv1x1: roi_rule must be 'tile' or 'box' (got {roi_rule!r})")
     x = _need(x, torch.float32, "x")
     n, cin, H, W = (int(v) for v in x.shape)
     cout = int(w.shape[0])
@@ -3296,7 +3315,11 @@ def conv1x1(x, w, bias=None, residual=None, act=0, in_scale=None, stride=1, pixe
     table = _roi_table(roi, n, Ho, Wo, "conv1x1") if roi is not None else None
     with _Timed(f"conv1x1_{cin}_{cout}" + ("_s2" if stride == 2 else ""), 2.0 * n * cin * cout * Ho * Wo,
                 4.0 * n * (cin * Ho * Wo + cout * Ho * Wo * (2 if residual is not None else 1)), kernel_events=True):
-        if table is not None:
+        if table is not None and roi_rule == "box":
+            _capi.call("heal_conv1x1_box_roi", _ptr(x), _ptr(frag), _ptr(bias) if bias is not None else None,
+                       _ptr(residual) if residual is not None else None, _ptr(in_scale) if in_scale is not None else None,
+                       n, cin, cout, H, W, int(stride), int(act), ctypes.c_void_p(table.ctypes.data), _ptr(y), _stream())
+        elif table is not None:
             _capi.call("heal_conv1x1_roi", _ptr(x), _ptr(frag), _ptr(bias) if bias is not None else None,
                        _ptr(residual) if residual is not None else None, _ptr(in_scale) if in_scale is not None else None,
                        n, cin, cout, H, W, int(stride), int(act), 0, ctypes.c_void_p(table.ctypes.data), _ptr(y), _stream())

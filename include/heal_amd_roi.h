@@ -34,6 +34,17 @@ int heal_conv1x1_roi(const float* x, const float* weight_frag, const float* bias
                      const float* in_scale, int n, int cin, int cout, int H, int W, int stride, int act,
                      int out_pixel_major, const int32_t* roi_host, float* y, void* stream);
 
+/* heal_conv1x1_box_roi: the same convolution (NCHW output) with the BOX rule: the launch's 64-pixel tiles enumerate each image's
+ *   ALIGNED box instead of the image.  For the box (y0, y1, x0, x1): xa = x0 rounded down to 4, xb = x1 rounded up to 4 (inside the
+ *   map, as Wo % 4 == 0), bw = xb - xa, bh = y1 - y0.  Tile t of the image covers the box-relative pixels q in [64 t, 64 t + 64),
+ *   pixel q being row y0 + q / bw, column xa + q % bw; the ceil(bw bh / 64) tiles with 64 t < bw bh run, the others leave as above.
+ *   Exactly the pixels of the aligned box are computed and written -- bit-identical to heal_conv1x1 -- and NOTHING outside it: a
+ *   narrow box costs its own pixels, not the rows it touches.  The full box is the plain launch (same addresses); an empty box skips
+ *   the image.  An output width that is no multiple of 4 (stride 1 only) keeps heal_conv1x1_roi's tile rule.                      */
+int heal_conv1x1_box_roi(const float* x, const float* weight_frag, const float* bias, const float* residual,
+                         const float* in_scale, int n, int cin, int cout, int H, int W, int stride, int act,
+                         const int32_t* roi_host, float* y, void* stream);
+
 /* heal_grouped_small_conv3x3_roi: heal_grouped_small_conv3x3 (4, 8 or 16 channels per group, stride 1 | 2) with a ROI.
  *   Tiles: TH x TW output pixels (x one 16-channel super-group), TH x TW = 16 x 32 (4 channels per group, stride 1), 8 x 32 (8 or 16
  *   per group, stride 1) or 8 x 16 (stride 2), clipped to the map; a tile is skipped when it holds no pixel of the box -- exact.    */
