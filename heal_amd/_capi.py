@@ -25,6 +25,7 @@ HEADER_UNC = os.path.join(os.path.dirname(HERE), "include", "heal_amd_unc.h")
 HEADER_ROI = os.path.join(os.path.dirname(HERE), "include", "heal_amd_roi.h")
 HEADER_ALIGN = os.path.join(os.path.dirname(HERE), "include", "heal_amd_align.h")
 HEADER_SSFA = os.path.join(os.path.dirname(HERE), "include", "heal_amd_ssfa.h")
+HEADER_POSE = os.path.join(os.path.dirname(HERE), "include", "heal_amd_pose.h")
 
 _lib = None
 
@@ -180,6 +181,15 @@ def signatures_ssfa():
         return parse_prototypes(f.read())
 
 
+@functools.lru_cache(maxsize=None)
+def signatures_pose():
+    """{name: (restype, argtypes)} of include/heal_amd_pose.h: CoAlign's agent-object pose graph -- clustering of every agent's
+    boxes and the Levenberg-Marquardt solve for a batch of samples (heal_pose_graph_align with its host-side support and
+    workspace rules).  Every build exports them; like signatures_ext() they are outside the versioned inference ABI."""
+    with open(HEADER_POSE) as f:
+        return parse_prototypes(f.read())
+
+
 def declared_symbols(experimental=False):
     """Function names declared in include/heal_amd.h (the shipped C ABI), or with experimental=True in
     include/heal_amd_experimental.h."""
@@ -217,7 +227,7 @@ def lib():
         for name, (res, args) in {**signatures(), **signatures_train(), **signatures_ext(), **signatures_train_attn(),
                                   **signatures_train_bn(), **signatures_train_warp(), **signatures_center(),
                                   **signatures_comm(), **signatures_unc(), **signatures_roi(), **signatures_align(),
-                                  **signatures_ssfa()}.items():
+                                  **signatures_ssfa(), **signatures_pose()}.items():
             if not hasattr(L, name):
                 continue  # declared but not built yet -> surfaces in call() / the symbol test
             f = getattr(L, name)

@@ -79,6 +79,7 @@ def _deps():
     hdrs.append(os.path.join(inc, "heal_amd_roi.h"))        # the region-of-interest convolution launches: part of every build
     hdrs.append(os.path.join(inc, "heal_amd_align.h"))      # the aligners' cross-covariance attention weights: part of every build
     hdrs.append(os.path.join(inc, "heal_amd_ssfa.h"))       # SSFA's transposed convolution and attention blend: part of every build
+    hdrs.append(os.path.join(inc, "heal_amd_pose.h"))       # the agent-object pose graph (box alignment): part of every build
     if EXPERIMENTAL:
         hdrs.append(os.path.join(inc, "heal_amd_experimental.h"))
     return hdrs

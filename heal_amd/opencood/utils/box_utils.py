@@ -1,6 +1,8 @@
 """Host mirror of the opencood/utils/box_utils.py functions on the hot path (the fused operator
 heal_decode_nms implements the same chain inside VoxelPostprocessor.post_process).  Same names, argument meaning and
 return types; tensor math in torch with the reference's operation order, rotated NMS on the GPU (heal_nms_quads)."""
+import sys
+
 import numpy as np
 import torch
 
@@ -50,6 +52,31 @@ def corner_to_standup_box_torch(box_corner):
     """box_utils.py:251-275."""
     return torch.stack([box_corner[:, :, 0].min(1).values, box_corner[:, :, 1].min(1).values,
                         box_corner[:, :, 0].max(1).values, box_corner[:, :, 1].max(1).values], 1).float()
+
+
+def corner_to_center(corner3d, order='lwh'):
+    """box_utils.py:25-84: (N,8,3) corners -> (N,7) [x,y,z,l,w,h,yaw] ('lwh') or [x,y,z,h,w,l,yaw] ('hwl'), numpy, dtype kept.
+    The centre is the mean of corners 0, 3, 5, 6; l, w, h are means of four edge lengths; the yaw is the PLAIN mean of four
+    arctan2 (not a circular mean: edges that straddle +-pi average to a yaw near 0)."""
+    assert corner3d.ndim == 3
+    n = corner3d.shape[0]
+    c = corner3d
+
+    def edge(i, j):
+        return np.sqrt(np.sum((c[:, i, [0, 1]] - c[:, j, [0, 1]]) ** 2, axis=1, keepdims=True))
+
+    def heading(i, j):
+        return np.arctan2(c[:, i, 1] - c[:, j, 1], c[:, i, 0] - c[:, j, 0])
+    xyz = np.mean(c[:, [0, 3, 5, 6], :], axis=1)
+    h = abs(np.mean(c[:, 4:, 2] - c[:, :4, 2], axis=1, keepdims=True))
+    l = (edge(0, 3) + edge(2, 1) + edge(4, 7) + edge(5, 6)) / 4
+    w = (edge(0, 1) + edge(2, 3) + edge(4, 5) + edge(6, 7)) / 4
+    theta = (heading(1, 2) + heading(0, 3) + heading(5, 6) + heading(4, 7))[:, np.newaxis] / 4
+    if order == 'lwh':
+        return np.concatenate([xyz, l, w, h, theta], axis=1).reshape(n, 7)
+    if order == 'hwl':
+        return np.concatenate([xyz, h, w, l, theta], axis=1).reshape(n, 7)
+    sys.exit('Unknown order')
 
 
 def project_box3d(box3d, transformation_matrix):

@@ -95,3 +95,33 @@ def get_pairwise_transformation(base_data_dict, max_cav, proj_first):
             if i != j:
                 pairwise[i, j] = np.linalg.solve(t_list[j], t_list[i])
     return pairwise
+
+
+def pose_to_tfm(pose):
+    """transformation_utils.py:94-162: poses [N,3] (x, y, yaw) or [N,6] (x, y, z, roll, yaw, pitch), degrees, CARLA convention
+    -> [N,4,4].  A numpy pose goes through check_numpy_to_torch and the identity it is written into is torch.eye's default
+    dtype: the result is FLOAT32 whatever the input's precision (the box alignment's world frame inherits this)."""
+    from heal_amd.opencood.utils.common_utils import check_numpy_to_torch
+    pose, is_np = check_numpy_to_torch(pose)
+    n = pose.shape[0]
+    tfm = torch.eye(4, device=pose.device).view(1, 4, 4).repeat(n, 1, 1)
+    if pose.shape[1] == 3:
+        yaw = torch.deg2rad(pose[:, 2])
+        tfm[:, 0, 0], tfm[:, 0, 1] = torch.cos(yaw), -torch.sin(yaw)
+        tfm[:, 1, 0], tfm[:, 1, 1] = torch.sin(yaw), torch.cos(yaw)
+        tfm[:, 0, 3], tfm[:, 1, 3] = pose[:, 0], pose[:, 1]
+    elif pose.shape[1] == 6:
+        c_y, s_y = torch.cos(torch.deg2rad(pose[:, 4])), torch.sin(torch.deg2rad(pose[:, 4]))
+        c_r, s_r = torch.cos(torch.deg2rad(pose[:, 3])), torch.sin(torch.deg2rad(pose[:, 3]))
+        c_p, s_p = torch.cos(torch.deg2rad(pose[:, 5])), torch.sin(torch.deg2rad(pose[:, 5]))
+        tfm[:, 0, 3], tfm[:, 1, 3], tfm[:, 2, 3] = pose[:, 0], pose[:, 1], pose[:, 2]
+        tfm[:, 0, 0] = c_p * c_y
+        tfm[:, 0, 1] = c_y * s_p * s_r - s_y * c_r
+        tfm[:, 0, 2] = -c_y * s_p * c_r - s_y * s_r
+        tfm[:, 1, 0] = s_y * c_p
+        tfm[:, 1, 1] = s_y * s_p * s_r + c_y * c_r
+        tfm[:, 1, 2] = -s_y * s_p * c_r + c_y * s_r
+        tfm[:, 2, 0] = s_p
+        tfm[:, 2, 1] = -c_p * s_r
+        tfm[:, 2, 2] = c_p * c_r
+    return tfm.numpy() if is_np else tfm

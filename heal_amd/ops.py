@@ -4375,3 +4375,113 @@ def radix_sort_pairs(keys, vals, key_bits):
     _capi.call("heal_radix_sort_pairs", _ptr(kbuf[0]), _ptr(kbuf[1]), _ptr(vbuf[0]), _ptr(vbuf[1]), n, int(key_bits),
                ctypes.byref(which), _ptr(ws), need, _stream())
     return kbuf[which.value], vbuf[which.value]
+
+
+# ---- CoAlign's agent-object pose graph (include/heal_amd_pose.h) ---------------------------------------------------------------
+POSE_CALLS = {"align": 0}                    # kernel calls so far (tests: a refusal launches nothing)
+POSE_STATS = ("landmarks", "edges", "iterations", "status", "chi2_initial", "chi2_final", "lambda", "trials")
+_POSE_OPTION_BITS = (("landmark_SE2", "HEAL_POSE_LANDMARK_SE2", True), ("adaptive_landmark", "HEAL_POSE_ADAPTIVE_LANDMARK", False),
+                     ("normalize_uncertainty", "HEAL_POSE_NORMALIZE_UNCERTAINTY", False),
+                     ("abandon_hard_cases", "HEAL_POSE_ABANDON_HARD_CASES", False),
+                     ("drop_hard_boxes", "HEAL_POSE_DROP_HARD_BOXES", False), ("drop_unsure_edge", "HEAL_POSE_DROP_UNSURE_EDGE", False))
+
+
+def pose_graph_limits():
+    """(HEAL_POSE_MAX_AGENTS, HEAL_POSE_MAX_BOXES): per sample, read from include/heal_amd_pose.h."""
+    return (_capi.header_define("HEAL_POSE_MAX_AGENTS", _capi.HEADER_POSE), _capi.header_define("HEAL_POSE_MAX_BOXES", _capi.HEADER_POSE))
+
+
+def pose_graph_supported(max_agents_per_sample, max_boxes_per_sample):
+    return bool(_capi.lib().heal_pose_graph_supported(int(max_agents_per_sample), int(max_boxes_per_sample)))
+
+
+def pose_graph_align(corners_list, lidar_pose, uncertainty_list, record_len, return_stats=False, **box_align_args):
+    """CoAlign's box alignment for a batch of samples in one call (heal_pose_graph_align, include/heal_amd_pose.h): the device
+    counterpart of box_align_v2.box_alignment_relative_np.
+      corners_list      per agent (all samples, in order) a CUDA tensor [n_i, 8, 3] of box corners in the agent's own frame, fp32 or
+                        fp64 (fp32 is converted); None or an empty tensor for an agent without boxes
+      lidar_pose        [sum(record_len), 6] x, y, z, roll, yaw, pitch in degrees (tensor or array, moved to the boxes' device)
+      uncertainty_list  per agent [n_i, 3] log sigma^2 of (x, y, yaw), or None (no uncertainties)
+      record_len        agents per sample; the first agent of a sample is its ego
+      box_align_args    the reference's options: landmark_SE2, adaptive_landmark, normalize_uncertainty, abandon_hard_cases,
+                        drop_hard_boxes, drop_unsure_edge, use_uncertainty, thres, yaw_var_thres, max_iterations
+    -> refined [sum(record_len), 3] f64: x, y, yaw in degrees.  return_stats=True: (refined, stats, cluster_of_box) with stats a
+    dict of [samples] tensors named POSE_STATS and cluster_of_box i32 [total boxes] (-1 or the landmark within its sample).
+    A sample beyond HEAL_POSE_MAX_AGENTS / HEAL_POSE_MAX_BOXES raises before anything is launched.  No CPU path: the numpy
+    function is the host path."""
+    who = "pose_graph_align"
+    args = dict(box_align_args)
+    options = 0
+    for name, define, default in _POSE_OPTION_BITS:
+        if bool(args.pop(name, default)):
+            options |= _capi.header_define(define, _capi.HEADER_POSE)
+    use_unc = bool(args.pop("use_uncertainty", True))
+    thres, yaw_var_thres = float(args.pop("thres", 1.5)), float(args.pop("yaw_var_thres", 0.2))
+    max_iterations = int(args.pop("max_iterations", 1000))
+    if args:
+        raise _capi.HealAmdError(f"{who}: unknown option(s) {sorted(args)}")
+    rec = [int(v) for v in (record_len.tolist() if hasattr(record_len, "tolist") else record_len)]
+    total_agents = sum(rec)
+    if not rec or min(rec) < 1 or len(corners_list) != total_agents:
+        raise _capi.HealAmdError(f"{who}: record_len {rec} does not split {len(corners_list)} agents into samples of at least one")
+    device = next((c.device for c in corners_list if isinstance(c, torch.Tensor) and c.is_cuda), None)
+    if device is None and isinstance(lidar_pose, torch.Tensor) and lidar_pose.is_cuda:
+        device = lidar_pose.device
+    if device is None:
+        raise _capi.HealAmdError(f"{who}: needs CUDA/HIP tensors (heal_amd has no CPU path; the host path is "
+                                 "box_align_v2.box_alignment_relative_np)")
+    counts, parts = [], []
+    for a, c in enumerate(corners_list):
+        k = 0 if c is None else int(len(c))
+        if k:
+            if not isinstance(c, torch.Tensor) or not c.is_cuda or c.device != device or tuple(c.shape[1:]) != (8, 3):
+                raise _capi.HealAmdError(f"{who}: corners_list[{a}] must be a [n, 8, 3] tensor on {device}")
+            if c.dtype not in (torch.float32, torch.float64):
+                raise _capi.HealAmdError(f"{who}: corners_list[{a}] must be float32 or float64, got {c.dtype}")
+            parts.append(c.detach().to(torch.float64).reshape(k, 24))
+        counts.append(k)
+    M = sum(counts)
+    unc = None
+    if use_unc and uncertainty_list is not None:
+        if len(uncertainty_list) != total_agents:
+            raise _capi.HealAmdError(f"{who}: {len(uncertainty_list)} uncertainty entries for {total_agents} agents")
+        uparts = []
+        for a, u in enumerate(uncertainty_list):
+            k = 0 if u is None else int(len(u))
+            if k != counts[a]:
+                raise _capi.HealAmdError(f"{who}: uncertainty_list[{a}] has {k} rows for {counts[a]} boxes")
+            if k:
+                if not isinstance(u, torch.Tensor) or u.device != device or tuple(u.shape[1:]) != (3,):
+                    raise _capi.HealAmdError(f"{who}: uncertainty_list[{a}] must be a [n, 3] tensor on {device}")
+                uparts.append(u.detach().to(torch.float64))
+        unc = torch.cat(uparts).contiguous() if uparts else torch.zeros((0, 3), dtype=torch.float64, device=device)
+    pose = torch.as_tensor(lidar_pose).detach().to(device=device, dtype=torch.float64).contiguous()
+    if tuple(pose.shape) != (total_agents, 6):
+        raise _capi.HealAmdError(f"{who}: lidar_pose has shape {tuple(pose.shape)}, want [{total_agents}, 6]")
+    S = len(rec)
+    agent_off = np.concatenate([[0], np.cumsum(rec)]).astype(np.int32)
+    box_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    per_sample = [int(box_off[agent_off[s + 1]] - box_off[agent_off[s]]) for s in range(S)]
+    max_agents, max_boxes = max(rec), max(per_sample)
+    if not pose_graph_supported(max_agents, max_boxes):
+        lim = pose_graph_limits()
+        raise _capi.HealAmdError(f"{who}: a sample of {max_agents} agents and {max_boxes} boxes is out of range (at most {lim[0]} "
+                                 f"agents and {lim[1]} boxes per sample)")
+    need = _capi.query("heal_pose_graph_workspace", S, total_agents, M)
+    if need == 0:
+        raise _capi.HealAmdError(f"{who}: unsupported batch ({S} samples, {total_agents} agents, {M} boxes)")
+    corners = torch.cat(parts).contiguous() if parts else torch.zeros((0, 24), dtype=torch.float64, device=device)
+    offsets = torch.from_numpy(np.concatenate([box_off, agent_off])).to(device)
+    refined = torch.empty((total_agents, 3), dtype=torch.float64, device=device)
+    cluster = torch.empty((M,), dtype=torch.int32, device=device) if return_stats else None
+    nstat = _capi.header_define("HEAL_POSE_STATS", _capi.HEADER_POSE)
+    stats = torch.empty((S, nstat), dtype=torch.float64, device=device) if return_stats else None
+    ws = _workspace("pose_graph_align", need, device)
+    with _Timed(f"pose_graph_align_s{S}"):
+        _capi.call("heal_pose_graph_align", _ptr(corners), _ptr(offsets), _ptr(offsets[total_agents + 1:]), _ptr(pose), _ptr(unc), S,
+                   total_agents, M, max_agents, max_boxes, options, thres, yaw_var_thres, max_iterations, _ptr(refined),
+                   _ptr(cluster), _ptr(stats), _ptr(ws), need, _stream())
+    POSE_CALLS["align"] += 1
+    if not return_stats:
+        return refined
+    return refined, {name: stats[:, k] for k, name in enumerate(POSE_STATS)}, cluster
